@@ -85,7 +85,53 @@ def parse():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="multi-rank code-path rehearsal on a single GPU: every rank uses device 0 and the gloo backend "
                          "(not a measurement)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0) to DIR/<name>.npy: "
+                         "every loss, and a fixed sample of the updated parameters and momentum buffers (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_SAMPLE_PER_TENSOR = 4096   # elements per parameter tensor in the dumped samples (fixed indices, seeded)
+
+
+def dump_outputs(out_dir, losses, total, model, opt):
+    """What one timed step hands its caller, as float32 .npy files (a few MB): every loss of the last step under its
+    own name (loss_cls, loss_mask, ...) and `total_loss` (their sum, the tensor the backward ran from);
+    `params_sample` and `momentum_sample`: the parameters and SGD momentum buffers after the last update (zeros for a
+    parameter that never had a gradient), DUMP_SAMPLE_PER_TENSOR elements of every trainable parameter in
+    named_parameters() order, at indices drawn from one generator seeded with 0 (all of a smaller tensor, in order).
+    The indices depend only on the model's parameter shapes, so two builds dump the same elements."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+    for k, v in losses.items():
+        save(k, v)
+    save("total_loss", total)
+    rng = np.random.default_rng(0)
+    params, bufs = [], []
+    for p in model.parameters():
+        if not p.requires_grad:
+            continue
+        numel = p.numel()
+        if numel > DUMP_SAMPLE_PER_TENSOR:
+            idx = np.sort(rng.choice(numel, DUMP_SAMPLE_PER_TENSOR, replace=False))
+            idx = torch.from_numpy(idx).to(p.device)
+        else:
+            idx = torch.arange(numel, device=p.device)
+        buf = opt.state.get(p, {}).get("momentum_buffer")
+        if buf is None:
+            buf = torch.zeros_like(p)
+        params.append(p.detach().reshape(-1)[idx])
+        bufs.append(buf.detach().reshape(-1)[idx])
+    save("params_sample", torch.cat(params))
+    save("momentum_sample", torch.cat(bufs))
 
 
 def build(device, depth=50):
@@ -430,6 +476,7 @@ def main():
     # one process per GPU; this repo's own bucketed reduce-scatter + all-gather over RCCL, overlapped with the backward
     net = dp.wrap_data_parallel(model, device)
     opt = make_optimizer(model)
+    last_losses = {}
 
     def step():
         losses = net(inputs)
@@ -437,6 +484,8 @@ def main():
         total.backward()
         opt.step()
         opt.zero_grad(set_to_none=True)
+        last_losses.clear()
+        last_losses.update(losses)
         return total
 
     def fence():
@@ -452,6 +501,8 @@ def main():
     dt = time.perf_counter() - t0
     dt = dp.max_over_ranks(dt, device)
     loss_value = float(last.detach())
+    if rank == 0 and args.dump_outputs:   # before the extra legs below step the model again
+        dump_outputs(args.dump_outputs, last_losses, last, model, opt)
 
     out, detail = None, {}
     if rank == 0:

@@ -18,6 +18,8 @@ Sources of truth
     the keep list depends only on the greedy visiting order and the suppress rule, which is what it pins.
   * moi_pool_oracle.npz: MOIPool has no runnable reference -> vectors come from
     our restatement (oracle/c/pool_ops.inc); "parity unpinned", they pin regressions only.
+  * roi_align_fresh_ref.json: SHA-256 digests of the REFERENCE's compiled ROIAlign / ROIAlignRotated results on the
+    seeded inputs of tests/test_oracle_pooling.py: fresh_calls().
 """
 import os
 import sys
@@ -158,9 +160,24 @@ def main():
         cases[name] = dict(boxes=b, scores=sc, keep=keep.astype(np.int64), thr=np.array([thr], np.float64))
     np.savez_compressed(os.path.join(HERE, "nms_ref.npz"),
                         **{"%s__%s" % (k, f): v for k, d in cases.items() for f, v in d.items()})
+    fresh_reference_digests(ref)
     for f in sorted(os.listdir(HERE)):
-        if f.endswith(".npz"):
+        if f.endswith((".npz", ".json")):
             print(f, os.path.getsize(os.path.join(HERE, f)))
+
+
+def fresh_reference_digests(ref):
+    import json
+
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_oracle_pooling import FRESH_REF, digest, fresh_calls
+
+    T = torch.from_numpy
+    out = {name: digest(getattr(ref, fn)(*[T(a) if isinstance(a, np.ndarray) else a for a in args]).numpy())
+           for name, fn, args in fresh_calls()}
+    with open(os.path.join(HERE, FRESH_REF), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
 
 
 if __name__ == "__main__":

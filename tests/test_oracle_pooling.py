@@ -2,7 +2,8 @@
 
   1. against the known answers the reference's own tests hold (kat_reference_tests.npz),
   2. against committed vectors produced by the reference's compiled CPU code (bit-exact),
-  3. against that compiled code itself on fresh random inputs, when oracle/_ref is present,
+  3. against that compiled code on seeded random inputs: the stored digests of its results, and the code itself
+     when oracle/_ref is present,
   4. self-consistency: analytic backward vs numerical differentiation in fp64 (the reference's
      gradcheck recipe, tests/layers/test_roi_align_rotated.py:107-125), rotated(0 deg) == aligned
      (tests/modeling/test_roi_pooler.py:15-60), empty inputs.
@@ -92,15 +93,16 @@ def test_roi_align_rotated_matches_reference_vectors_bit_exact(case):
     assert np.array_equal(gx, c["gx"])
 
 
-def test_against_compiled_reference_on_fresh_inputs(reference_module):
-    if reference_module is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    import torch
+FRESH_REF = "roi_align_fresh_ref.json"
 
-    ref, T = reference_module, torch.from_numpy
+
+def fresh_calls():
+    """The oracle-versus-reference comparison on seeded random inputs, one call at a time: (name, function, arguments).
+    oracle/pooling.py and the compiled reference module take the same arguments (numpy arrays there, tensors here);
+    tests/golden/make_golden.py stores a digest of every reference result in FRESH_REF."""
     rng = np.random.default_rng(7)
     for dt in (np.float32, np.float64):
-        for _ in range(6):
+        for i in range(6):
             B, Cc, H, W, M = 2, 3, int(rng.integers(5, 40)), int(rng.integers(5, 40)), 19
             x = rng.standard_normal((B, Cc, H, W)).astype(dt)
             x0, y0 = rng.uniform(-5, W * 4, M), rng.uniform(-5, H * 4, M)
@@ -109,19 +111,45 @@ def test_against_compiled_reference_on_fresh_inputs(reference_module):
             r = np.stack([b, x0, y0, x0 + w, y0 + h], 1).astype(dt)
             rr = np.stack([b, x0 + w / 2, y0 + h / 2, w, h, rng.uniform(-180, 180, M)], 1).astype(dt)
             for sr in (0, 2):
+                pre = "%s_%d_sr%d" % (np.dtype(dt).name, i, sr)
                 for al in (True, False):
-                    assert np.array_equal(
-                        P.roi_align_forward(x, r, 0.25, 7, 7, sr, al),
-                        ref.roi_align_forward(T(x), T(r), 0.25, 7, 7, sr, al).numpy())
-                y = P.roi_align_rotated_forward(x, rr, 0.25, 7, 7, sr)
-                assert np.array_equal(y, ref.roi_align_rotated_forward(T(x), T(rr), 0.25, 7, 7, sr).numpy())
-                g = rng.standard_normal(y.shape).astype(dt)
-                assert np.array_equal(
-                    P.roi_align_rotated_backward(g, rr, 0.25, 7, 7, B, Cc, H, W, sr),
-                    ref.roi_align_rotated_backward(T(g), T(rr), 0.25, 7, 7, B, Cc, H, W, sr).numpy())
-                assert np.array_equal(
-                    P.roi_align_backward(g, r, 0.25, 7, 7, B, Cc, H, W, sr, True),
-                    ref.roi_align_backward(T(g), T(r), 0.25, 7, 7, B, Cc, H, W, sr, True).numpy())
+                    yield "%s_al%d_forward" % (pre, al), "roi_align_forward", (x, r, 0.25, 7, 7, sr, al)
+                yield pre + "_rotated_forward", "roi_align_rotated_forward", (x, rr, 0.25, 7, 7, sr)
+                g = rng.standard_normal((M, Cc, 7, 7)).astype(dt)
+                yield pre + "_rotated_backward", "roi_align_rotated_backward", (g, rr, 0.25, 7, 7, B, Cc, H, W, sr)
+                yield pre + "_al1_backward", "roi_align_backward", (g, r, 0.25, 7, 7, B, Cc, H, W, sr, True)
+
+
+def digest(a):
+    """SHA-256 of an array's dtype, shape and values (-0.0 counted as 0.0, as np.array_equal does)."""
+    import hashlib
+
+    a = np.ascontiguousarray(a)
+    h = hashlib.sha256(("%s %s " % (a.dtype.str, a.shape)).encode())
+    h.update((a + a.dtype.type(0)).tobytes())
+    return h.hexdigest()
+
+
+def test_against_compiled_reference_on_fresh_inputs(reference_module):
+    """Bit-exact against the reference's compiled CPU code on seeded random inputs: against the digests of its results
+    (tests/golden/roi_align_fresh_ref.json) everywhere, and against the code itself where oracle/_ref is built."""
+    import json
+    import os
+
+    import torch
+
+    from conftest import GOLDEN
+
+    want = json.load(open(os.path.join(GOLDEN, FRESH_REF)))
+    seen = []
+    for name, fn, args in fresh_calls():
+        got = getattr(P, fn)(*args)
+        assert digest(got) == want[name], name
+        if reference_module is not None:
+            targs = [torch.from_numpy(a) if isinstance(a, np.ndarray) else a for a in args]
+            assert np.array_equal(got, getattr(reference_module, fn)(*targs).numpy()), name
+        seen.append(name)
+    assert sorted(seen) == sorted(want)
 
 
 def test_strided_grad_is_honoured():

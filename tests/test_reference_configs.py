@@ -32,15 +32,21 @@ def _flat(node, pre=""):
     return out
 
 
-SHIPPED = sorted(glob.glob(os.path.join(REF, "*PanopticSegmentation", "jtsm_*.yaml")))
+# named here rather than globbed, so the test ids do not depend on whether the reference tree is present
+SHIPPED_NAMES = ["COCO-PanopticSegmentation/jtsm_WSR_18_DC5_1x.yaml", "PascalVOC-PanopticSegmentation/jtsm_WSR_18_DC5_1x.yaml",
+                 "PascalVOC-PanopticSegmentation/jtsm_WSR_18_DC5_1x_VOC2007.yaml",
+                 "PascalVOC-PanopticSegmentation/jtsm_WSR_50_DC5_1x.yaml"]
+SHIPPED = [os.path.join(REF, n) for n in SHIPPED_NAMES]
 
 
 def test_there_are_four_shipped_jtsm_configs():
-    assert [os.path.basename(p) for p in SHIPPED] == [
+    found = sorted(glob.glob(os.path.join(REF, "*PanopticSegmentation", "jtsm_*.yaml")))
+    assert [os.path.basename(p) for p in found] == [
         "jtsm_WSR_18_DC5_1x.yaml", "jtsm_WSR_18_DC5_1x.yaml", "jtsm_WSR_18_DC5_1x_VOC2007.yaml", "jtsm_WSR_50_DC5_1x.yaml"]
+    assert found == SHIPPED
 
 
-@pytest.mark.parametrize("path", SHIPPED, ids=["/".join(p.split("/")[-2:]) for p in SHIPPED])
+@pytest.mark.parametrize("path", SHIPPED, ids=SHIPPED_NAMES)
 def test_shipped_config_builds_unchanged(path):
     from jtsm_amd.modeling import build_model
     from jtsm_amd.modeling.backbone.resnet_wsl_v2 import PooledBasicBlock, PooledBottleneckBlock
