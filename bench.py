@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — images/sec of the JTSM hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,9 +9,13 @@ One "step" = one full training step (forward, backward, gradient all-reduce, SGD
 JTSM panoptic composite on one synthetic batch per rank: BASELINE.json configs[2]
 (2 x 3x1024x1024 images, 2000 proposals and 1024 superpixels per image).  Inputs are
 resident in HBM before the timed region.  Rank 0 prints ONE JSON line; `value` is the whole-job
-images/sec (max step time over ranks).  Extra objects: `roofline` (dominant kernel, measured live with
-events on the launch stream in one extra, untimed step) and, at N=1, `cpu_baseline` (the CPU oracle
-timed on a bounded sample).
+images/sec (max step time over ranks).
+
+A plain run does only what that line needs: set up, warm up, time the steps, write the outputs (--dump-outputs)
+and print.  --full adds the extra legs after the timed steps, each of which its --no-* option drops: `roofline`
+(dominant kernel, measured live with events on the launch stream in one extra, untimed step; every kernel's table
+in the detail file) and, at N=1, `exact_fp32`, `round1_workload`, `config4_fp16` and `cpu_baseline` (the CPU
+oracle timed on a bounded sample).
 """
 import argparse
 import json
@@ -66,15 +70,21 @@ def parse():
     ap.add_argument("--size", type=int, default=1024, help="image side (BASELINE: 1024)")
     ap.add_argument("--proposals", type=int, default=2000, help="proposals per image (BASELINE: 2000)")
     ap.add_argument("--batch", type=int, default=2, help="images per GPU (BASELINE: 2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-exact", action="store_true", help="skip the exact-fp32 reference leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the extra legs: roofline step (per-kernel tables in the detail "
+                         "file), exact_fp32, round1_workload, config4_fp16, cpu_baseline; without it a run times the "
+                         "headline steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline step")
+    ap.add_argument("--no-exact", action="store_true",
+                    help="with --full: skip the exact-fp32 and round-1-workload legs")
     ap.add_argument("--cluster", type=float, default=1.0,
                     help="fraction of the proposals that are jittered copies of --objects rectangles per image "
                          "(utils/synthetic.py): gives the mask branch a realistic foreground count; 0 = the plain "
                          "uniform recipe of round 1")
     ap.add_argument("--objects", type=int, default=40, help="proposal groups per image (see --cluster)")
-    ap.add_argument("--no-config4", action="store_true", help="skip the BASELINE configs[4] extra leg (R101, fp16)")
+    ap.add_argument("--no-config4", action="store_true",
+                    help="with --full: skip the BASELINE configs[4] extra leg (R101, fp16)")
     ap.add_argument("--one-stream", action="store_true",
                     help="switch the side streams off (semantic head, weight gradients, MOIPool backward's second "
                          "gather) for the WHOLE run: per-kernel durations of a kernel trace then belong to one kernel "
@@ -91,6 +101,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # a plain run: the headline only
+        args.no_cpu_baseline = args.no_roofline = args.no_exact = args.no_config4 = True
     return args
 
 
@@ -520,10 +532,10 @@ def main():
                                 round(100 * args.cluster), args.objects),
                 "global_batch": args.batch * world, "parallelism": "dp%d" % world,
                 "math": ("split-bf16 (3 bf16 MFMA products, fp32 accumulate; <= 6e-6 rel per layer; bar 1e-4); "
-                         "see exact_fp32") if conv_math == "bf16x3" else conv_math,
+                         "see exact_fp32 with --full") if conv_math == "bf16x3" else conv_math,
                 "final_loss": round(loss_value, 5), "lr": 1e-7,
                 "foreground_rois_last_step": int(model.roi_heads.aux["fg_classes"].numel()),
-                "detail": DETAIL_PATH,
+                "detail": None if args.no_roofline and args.no_config4 else DETAIL_PATH,   # (only those legs write it)
             },
         }
         detail["config"] = {

@@ -73,3 +73,22 @@ def test_bench_line_stays_under_the_drivers_stdout_window(tmp_path, monkeypatch,
     bench.emit(out, detail)
     line = capsys.readouterr().out.strip()
     assert len(line) < 4096 and "cpu_baseline" in json.loads(line) and "roofline" in json.loads(line)
+
+
+def test_plain_bench_run_is_the_headline_only(monkeypatch):
+    """A plain run times the headline steps and nothing else; --full brings back every extra leg, and the --no-*
+    options drop single legs of a full run."""
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.no_roofline and a.no_exact and a.no_config4 and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not (a.no_roofline or a.no_exact or a.no_config4 or a.no_cpu_baseline)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.no_cpu_baseline and not (a.no_roofline or a.no_exact or a.no_config4)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0 and "--full" in out.stdout

@@ -11,32 +11,32 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 A=gpurun_out/art
 mkdir -p $A
-FAST="--no-cpu-baseline --no-roofline --no-exact --no-config4"
-PMCF="--no-cpu-baseline --no-roofline --no-exact"   # (with the configs[4] fp16 leg: its kernels' traffic rows)
+PMCF="--full --no-cpu-baseline --no-roofline --no-exact"   # (with the configs[4] fp16 leg: its kernels' traffic rows)
 case "$1" in
 pmc)
-rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $A/pmc/fetch -o p --output-format csv -- python bench.py --steps 2 --warmup 1 $FAST > $A/pmc_fetch.log 2>&1 &&
-rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $A/pmc/write -o p --output-format csv -- python bench.py --steps 2 --warmup 1 $FAST > $A/pmc_write.log 2>&1 &&
+rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $A/pmc/fetch -o p --output-format csv -- python bench.py --steps 2 --warmup 1 > $A/pmc_fetch.log 2>&1 &&
+rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $A/pmc/write -o p --output-format csv -- python bench.py --steps 2 --warmup 1 > $A/pmc_write.log 2>&1 &&
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $A/pmc4/fetch -o p --output-format csv -- python bench.py --steps 2 --warmup 1 $PMCF > $A/pmc4_fetch.log 2>&1 &&
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $A/pmc4/write -o p --output-format csv -- python bench.py --steps 2 --warmup 1 $PMCF > $A/pmc4_write.log 2>&1 &&
 python tools/pmc_traffic.py $A/pmc profiles/pmc_traffic.json $A/pmc4 && cp profiles/pmc_traffic.json $A/pmc_traffic.json &&
-rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $A/pmc/mfma -o p --output-format csv -- python bench.py --steps 2 --warmup 1 $FAST --launch-sequence $A/launch_sequence.json > $A/pmc_mfma.log 2>&1 &&
+rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $A/pmc/mfma -o p --output-format csv -- python bench.py --steps 2 --warmup 1 --launch-sequence $A/launch_sequence.json > $A/pmc_mfma.log 2>&1 &&
 (cd tools && python pmc_mfma.py ../$A/pmc/mfma ../profiles/pmc_mfma.json ../$A/launch_sequence.json) && cp profiles/pmc_mfma.json $A/pmc_mfma.json
 rm -rf $A/pmc/fetch $A/pmc/write $A/pmc/mfma $A/pmc4   # (the raw per-dispatch tables are tens of MB; the two JSON files are what is kept)
 ;;
 prof)
 # (--one-stream: a kernel's duration beside another queue's kernels measures the sharing; the roofline leg measures on
 #  one stream too, so its averages agree with this table.  kernel_stats_streams.csv: the default run, durations overlap)
-rocprofv3 --kernel-trace --stats -d $A/prof -o r --output-format csv -- python bench.py --one-stream --steps 10 --warmup 3 --no-cpu-baseline --no-exact --no-config4 > $A/prof_bench.json 2> $A/prof.log &&
+rocprofv3 --kernel-trace --stats -d $A/prof -o r --output-format csv -- python bench.py --full --one-stream --steps 10 --warmup 3 --no-cpu-baseline --no-exact --no-config4 > $A/prof_bench.json 2> $A/prof.log &&
 cp $A/prof/r_kernel_stats.csv $A/kernel_stats.csv &&
-rocprofv3 --kernel-trace --stats -d $A/prof_s -o r --output-format csv -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-exact --no-config4 --no-roofline > $A/prof_s_bench.json 2> $A/prof_s.log &&
+rocprofv3 --kernel-trace --stats -d $A/prof_s -o r --output-format csv -- python bench.py --steps 10 --warmup 3 > $A/prof_s_bench.json 2> $A/prof_s.log &&
 cp $A/prof_s/r_kernel_stats.csv $A/kernel_stats_streams.csv &&
-rocprofv3 --kernel-trace --stats -d $A/prof_u -o r --output-format csv -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-exact --no-config4 --no-roofline --cluster 0 > $A/prof_u_bench.json 2> $A/prof_u.log &&
+rocprofv3 --kernel-trace --stats -d $A/prof_u -o r --output-format csv -- python bench.py --steps 10 --warmup 3 --cluster 0 > $A/prof_u_bench.json 2> $A/prof_u.log &&
 cp $A/prof_u/r_kernel_stats.csv $A/kernel_stats_uniform.csv
 rm -rf $A/prof $A/prof_u $A/prof_s
 ;;
 bench)
-python bench.py --steps 20 --warmup 5 > $A/bench.json 2> $A/bench.err && cp gpurun_out/bench_detail.json $A/bench_detail.json
+python bench.py --full --steps 20 --warmup 5 > $A/bench.json 2> $A/bench.err &&
+cp "$(python -c 'import bench; print(bench.DETAIL_PATH)')" $A/bench_detail.json
 ;;
 side)
 python tools/stock_baseline.py --cluster 0 --warmup 25 > $A/stock_uniform.json 2> $A/stock_uniform.err &&

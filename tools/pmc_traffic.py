@@ -119,7 +119,7 @@ def main():
                     "is fabric-side traffic, an upper bound on HBM bytes",
         }
     json.dump({"command": "rocprofv3 --kernel-trace --pmc <FETCH_SIZE|WRITE_SIZE> -- python bench.py --steps 2 --warmup 1 "
-                          "--no-cpu-baseline --no-roofline --no-exact --no-config4 (the fp16 kernels' rows — \",1\" labels — from a second pair of passes that includes the configs[4] leg)", "kernels": kernels}, open(out, "w"), indent=1)
+                          "--no-cpu-baseline --no-roofline --no-exact --no-config4 (the fp16 kernels' rows — \",1\" labels — from a second pair of passes with --full --no-cpu-baseline --no-roofline --no-exact, which includes the configs[4] leg)", "kernels": kernels}, open(out, "w"), indent=1)
     print("wrote", out, len(kernels), "kernels")
 
 

@@ -1,6 +1,6 @@
 # usage: bash tools/sweeps/ab_bench_libs.sh A.so B.so ... -> bench.py (20 steps, headline leg only) with the built library, each
 # alternative swapped in, and the built one again (GPU box copy only; the tree's library is restored at the end)
-F="--no-config4 --no-exact --no-cpu-baseline --no-roofline --steps 20"
+F="--steps 20"
 cp jtsm_amd/lib/libjtsm_hip.so /tmp/libjtsm_keep.so
 timeout -k 10 300 python bench.py $F > gpurun_out/abl_base_a.json 2>> gpurun_out/abl.err
 for L in "$@"; do
