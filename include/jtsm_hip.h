@@ -146,6 +146,26 @@ int jtsm_moi_pool_backward_f32(const float* grad, const float* rois, const int32
                                float* grad_input, int B, int C, int H, int W, int M,
                                int pooled_h, int pooled_w, int layout, void* stream);
 /* ---------------------------------------------------------------------------
+ * ROILoopPool — replaces projects/WSL/wsl/layers/csrc/ROILoopPool/ROILoopPool.h:27-40
+ *   ROILoopPool_forward(input, rois, spatial_scale, pooled_h, pooled_w) -> (output, argmax)
+ *   ROILoopPool_backward(grad, rois, argmax, spatial_scale, pooled_h, pooled_w, B, C, H, W)
+ * called from projects/WSL/wsl/layers/roi_loop_pool.py:9-33 (contract: ROILoopPool_cuda.cu:10-388,
+ * spelled out in jtsm_amd/csrc/roi_loop_pool.hip).
+ * rois (R,5); output / argmax (3R,C,PH,PW) in `layout`: rows [0,R) box, [R,2R) frame (box minus
+ * the shrunken inner box), [2R,3R) context (enlarged outer box minus the box), context ratio 1.8.
+ * argmax holds the flat h*W+w of the winning cell (-1 = nothing above 0 in the bin).
+ * The backward is NHWC only (grad, argmax, grad_input channels-last) and writes every element of
+ * grad_input (no zero fill needed); it is a gather in a fixed order, so repeated calls give the
+ * same bits.  workspace: jtsm_roi_loop_pool_backward_workspace_bytes(R) bytes, 16-byte aligned.
+ * ------------------------------------------------------------------------- */
+int jtsm_roi_loop_pool_forward_f32(const float* input, const float* rois, float* output, int32_t* argmax,
+                                   int B, int C, int H, int W, int R, float spatial_scale, int pooled_h,
+                                   int pooled_w, int layout, void* stream);
+size_t jtsm_roi_loop_pool_backward_workspace_bytes(int R);
+int jtsm_roi_loop_pool_backward_f32(const float* grad, const float* rois, const int32_t* argmax,
+                                    float* grad_input, void* workspace, int B, int C, int H, int W, int R,
+                                    float spatial_scale, int pooled_h, int pooled_w, void* stream);
+/* ---------------------------------------------------------------------------
  * fp16 tensors at the pooling boundary.  The reference dispatches MOIPool on half too
  * (AT_DISPATCH_FLOATING_TYPES_AND_HALF, projects/WSL/wsl/layers/csrc/MOIPool/MOIPool_cuda.cu:400,415,484) and its
  * Python layers hand half tensors to the align operators (detectron2/layers/roi_align_rotated.py:79-85: up-cast,

@@ -6,3 +6,5 @@ from .mask_head import (ROI_MASK_HEAD_REGISTRY, MaskRCNNConvUpsampleHead, MaskRC
                         mask_rcnn_loss)
 from .roi_heads import ROI_HEADS_REGISTRY, ROIHeads, StandardROIHeads, build_roi_heads, select_foreground_proposals
 from .roi_heads_jtsm import JTSMROIHeads
+from .roi_heads_contextlocnet import ContextLocNetROIHeads
+from .fast_rcnn_wsddn import WSDDNOutputLayers
