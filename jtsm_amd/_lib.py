@@ -7,42 +7,64 @@ support").  PyTorch is used only for device memory and streams.
 """
 import ctypes as C
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JTSM_HIP_LIB") or os.path.join(_HERE, "lib", "libjtsm_hip.so")   # (override: A/B sweeps)
+HEADER = os.path.join(_HERE, "..", "include", "jtsm_hip.h")
 _lib = None
 
 NCHW, NHWC = 0, 1
 
+# C types of the header's scalar parameters and return values; any pointer is a c_void_p
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "unsigned": C.c_uint, "long": C.c_long, "size_t": C.c_size_t,
+            "int64_t": C.c_int64, "unsigned long long": C.c_ulonglong, "float": C.c_float, "double": C.c_double}
+_RETURNS = dict(_SCALARS, **{"void": None, "void*": C.c_void_p, "const char*": C.c_char_p})
+
+
+def declarations(path=HEADER):
+    """{name: (restype, argtypes)} of every jtsm_* prototype in the header: the library's signatures."""
+    txt = open(path).read()
+    txt = re.sub(r"/\*.*?\*/|//[^\n]*", " ", txt, flags=re.S)
+    txt = re.sub(r"^\s*#.*$", " ", txt, flags=re.M)
+    out = {}
+    for m in re.finditer(r"([\w\s*]+?)\b(jtsm_\w+)\s*\(([^()]*)\)\s*;", txt):
+        ret, name, params = re.sub(r"\s*\*\s*", "*", " ".join(m.group(1).split())), m.group(2), m.group(3)
+        decl = " ".join(m.group(0).split())
+        if ret not in _RETURNS:
+            raise ValueError("jtsm_amd: no ctypes mapping for the return type of `%s`" % decl)
+        argtypes = []
+        for p in params.split(","):
+            words = re.sub(r"\bconst\b", " ", p).split()
+            if "*" in p:
+                argtypes.append(C.c_void_p)
+            elif words != ["void"]:
+                t = _SCALARS.get(" ".join(words[:-1]))
+                if t is None:
+                    raise ValueError("jtsm_amd: no ctypes mapping for `%s` in `%s`" % (p.strip(), decl))
+                argtypes.append(t)
+        out[name] = (_RETURNS[ret], argtypes)
+    return out
+
 
 def lib():
-    """Load (once) and return the CDLL.  Loading does not need a GPU; compute calls do."""
+    """Load (once) and return the CDLL, every entry point typed from include/jtsm_hip.h.  Loading does not need a
+    GPU; compute calls do."""
     global _lib
     if _lib is None:
         if not os.path.isfile(LIB_PATH):
             raise RuntimeError(
                 "jtsm_amd: %s not found — build it with `python -m jtsm_amd.build` "
                 "(there is no fallback path)" % LIB_PATH)
-        _lib = C.CDLL(LIB_PATH)
-        _lib.jtsm_last_error.restype = C.c_char_p
-        _lib.jtsm_version.restype = C.c_char_p
-        _lib.jtsm_event_create.restype = C.c_void_p
-        _lib.jtsm_event_destroy.restype = None
-        _lib.jtsm_conv_set_mid_event.restype = None
-        _lib.jtsm_conv_set_splitk_fused.restype = None
-        _lib.jtsm_moi_pool_workspace_bytes.restype = C.c_size_t
-        for name in ("jtsm_mil_workspace_bytes", "jtsm_oicr_workspace_bytes", "jtsm_conv_workspace_bytes", "jtsm_conv_transpose2x2_workspace_bytes",
-                     "jtsm_group_norm_workspace_bytes", "jtsm_semseg_ce_workspace_bytes",
-                     "jtsm_conv_bf16x3_wgrad_workspace_bytes", "jtsm_conv_bf16x3_wgrad_bias_workspace_bytes", "jtsm_moi_pool_levels_workspace_bytes",
-                     "jtsm_paint_sem_seg_workspace_bytes", "jtsm_mask_bce_workspace_bytes",
-                     "jtsm_moi_pool_backward_levels_workspace_bytes", "jtsm_channel_sum_workspace_bytes",
-                     "jtsm_pool_f16_workspace_bytes", "jtsm_moi_pool_f16_workspace_bytes",
-                     "jtsm_conv_bf16x3_wgrad_group_workspace_bytes", "jtsm_image_labels_workspace_bytes",
-                     "jtsm_roi_align_backward_levels_workspace_bytes", "jtsm_roi_loop_pool_backward_workspace_bytes"):
-            if hasattr(_lib, name):
-                getattr(_lib, name).restype = C.c_size_t
+        raw = C.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in declarations().items():
+            fn = getattr(raw, name, None)
+            if fn is None:
+                raise RuntimeError("jtsm_amd: %s lacks %s, which include/jtsm_hip.h declares" % (LIB_PATH, name))
+            fn.restype, fn.argtypes = restype, argtypes
+        _lib = raw
     if TIMING is not None:
         return _TimedLib(_lib)
     return _lib
@@ -74,12 +96,12 @@ class EventSpan(object):
 
     def ms(self):
         out = C.c_float()
-        return out.value if lib().jtsm_event_elapsed_ms(C.c_void_p(self.a), C.c_void_p(self.b), C.byref(out)) == 0 else 0.0
+        return out.value if lib().jtsm_event_elapsed_ms(self.a, self.b, C.byref(out)) == 0 else 0.0
 
     def __del__(self):
         try:
             for e in (self.a, self.b):
-                lib().jtsm_event_destroy(C.c_void_p(e))
+                lib().jtsm_event_destroy(e)
         except Exception:
             pass
 
@@ -98,9 +120,9 @@ class _TimedLib(object):
             global _pending_bytes
             span = EventSpan(raw)
             st = stream()
-            raw.jtsm_event_record(C.c_void_p(span.a), st)
+            raw.jtsm_event_record(span.a, st)
             rc = fn(*args)
-            raw.jtsm_event_record(C.c_void_p(span.b), st)
+            raw.jtsm_event_record(span.b, st)
             TIMING.append((name, span, _pending_bytes))
             _pending_bytes = None
             return rc
@@ -114,8 +136,8 @@ def check(rc, what=""):
 
 
 def ptr(t):
-    """Device pointer of a tensor (or NULL for None) as c_void_p."""
-    return C.c_void_p(0 if t is None else t.data_ptr())
+    """Device pointer of a tensor as an int (None for None: NULL)."""
+    return None if t is None else t.data_ptr()
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -123,15 +145,15 @@ _device_index = None
 
 
 def stream():
-    """The current HIP stream of this process's device as a void*.  Called once per library launch (~950 per
-    training step), so it goes through torch's raw accessor (one C call) rather than building a Stream object; one
-    process drives one GPU (bench.py, DDP), whose index is looked up once."""
+    """The current HIP stream of this process's device as an int (the library's void* stream).  Called once per
+    library launch (~950 per training step), so it goes through torch's raw accessor (one C call) rather than building
+    a Stream object; one process drives one GPU (bench.py, DDP), whose index is looked up once."""
     global _device_index
     if _raw_stream is None:
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return torch.cuda.current_stream().cuda_stream
     if _device_index is None:
         _device_index = torch.cuda.current_device()
-    return C.c_void_p(_raw_stream(_device_index))
+    return _raw_stream(_device_index)
 
 
 def _check_device(t):
@@ -150,14 +172,6 @@ def require_gpu(*tensors):
                 "there is no CPU path in the product" % t.device)
         if t is not None:
             _check_device(t)
-
-
-def f32(x):
-    return C.c_float(float(x))
-
-
-def f64(x):
-    return C.c_double(float(x))
 
 
 def is_nhwc(t):

@@ -75,10 +75,10 @@ def _hl(buf):
         return None, None
     p = buf.data_ptr()
     if MATH == "f16":
-        return C.c_void_p(p), None
+        return p, None
     if getattr(buf, "_paired", False):
-        return C.c_void_p(p), C.c_void_p(p + 64)
-    return C.c_void_p(p), C.c_void_p(p + buf.numel())   # lo starts numel/2 int16 = numel bytes in
+        return p, p + 64
+    return p, p + buf.numel()   # lo starts numel/2 int16 = numel bytes in
 
 
 # Weights as PAIRED planes (csrc/conv_x3.h `x3_paired`): one K stage of a contraction is one whole 128-byte line per
@@ -102,10 +102,9 @@ def _split(t, grad=False):
     hi, lo = _hl(buf)
     L.note_bytes((6.0 if MATH == "f16" else 8.0) * t.numel())   # fp32 read, planes written
     if MATH == "f16":
-        L.check(L.lib().jtsm_split_f16_f32(L.ptr(t), hi, C.c_long(t.numel()), GRAD_SHIFT if grad else 0, L.stream()),
-                "split_f16")
+        L.check(L.lib().jtsm_split_f16_f32(L.ptr(t), hi, t.numel(), GRAD_SHIFT if grad else 0, L.stream()), "split_f16")
         return buf
-    L.check(L.lib().jtsm_split_bf16_f32(L.ptr(t), hi, lo, C.c_long(t.numel()), L.stream()), "split_bf16")
+    L.check(L.lib().jtsm_split_bf16_f32(L.ptr(t), hi, lo, t.numel(), L.stream()), "split_bf16")
     return buf
 
 
@@ -122,8 +121,8 @@ def _split_paired(w):
     buf = _planes_buf(w.numel(), w.device)
     buf._paired = True
     L.note_bytes(8.0 * w.numel())
-    L.check(L.lib().jtsm_split_bf16_paired_f32(L.ptr(w), C.c_void_p(buf.data_ptr()), C.c_long(w.numel() // k), k,
-                                               L.stream()), "split_bf16_paired")
+    L.check(L.lib().jtsm_split_bf16_paired_f32(L.ptr(w), L.ptr(buf), w.numel() // k, k, L.stream()),
+            "split_bf16_paired")
     return buf
 
 
@@ -254,12 +253,12 @@ def _weight_planes(w, transposed=False, scale=None):
     if transposed:
         _split_transposed_into(e.buf, w, scale)
     elif e.buf._paired:
-        L.check(lib.jtsm_split_bf16_paired_f32(L.ptr(w), hi, C.c_long(w.shape[0]), w.numel() // w.shape[0], L.stream()),
+        L.check(lib.jtsm_split_bf16_paired_f32(L.ptr(w), hi, w.shape[0], w.numel() // w.shape[0], L.stream()),
                 "split_bf16_paired")
     elif MATH == "f16":
-        L.check(lib.jtsm_split_f16_f32(L.ptr(w), hi, C.c_long(w.numel()), 0, L.stream()), "split_f16")
+        L.check(lib.jtsm_split_f16_f32(L.ptr(w), hi, w.numel(), 0, L.stream()), "split_f16")
     else:
-        L.check(lib.jtsm_split_bf16_f32(L.ptr(w), hi, lo, C.c_long(w.numel()), L.stream()), "split_bf16")
+        L.check(lib.jtsm_split_bf16_f32(L.ptr(w), hi, lo, w.numel(), L.stream()), "split_bf16")
     e.version = w._version
     return e.buf
 
@@ -298,8 +297,8 @@ def refresh_weight_planes():
                 _WTABLES.clear()
             _WTABLES[tkey] = tab
         L.note_bytes((6.0 if MATH == "f16" else 8.0) * sum(e.w.numel() for _, e in stale))
-        L.check(L.lib().jtsm_split_bf16_multi_f32(L.ptr(tab[0]), len(stale), C.c_long(tab[1]), int(transposed),
-                                                  L.stream()), "split_bf16_multi")
+        L.check(L.lib().jtsm_split_bf16_multi_f32(L.ptr(tab[0]), len(stale), tab[1], int(transposed), L.stream()),
+                "split_bf16_multi")
         for _, e in stale:
             e.version = e.w._version
 
@@ -371,7 +370,7 @@ def _scratch(nbytes, device):
         return None
     # (one buffer per STREAM: launches of one stream run in order, and a side stream — the queued weight gradients, the
     # semantic head — must not fold its slabs through the buffer the compute stream's contractions are using)
-    key = (device, L.stream().value)
+    key = (device, L.stream())
     buf = _SCRATCH.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = _SCRATCH[key] = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)
@@ -417,7 +416,7 @@ class LaunchSpan(object):
 
     def _ms(self, x, y):
         out = C.c_float()
-        return out.value if L.lib().jtsm_event_elapsed_ms(C.c_void_p(x), C.c_void_p(y), C.byref(out)) == 0 else None
+        return out.value if L.lib().jtsm_event_elapsed_ms(x, y, C.byref(out)) == 0 else None
 
     def kernel_ms(self):
         """The contraction kernel alone (falls back to the whole call if the hook did not fire)."""
@@ -431,7 +430,7 @@ class LaunchSpan(object):
         try:
             lib = L.lib()
             for e in (self.a, self.mid, self.b):
-                lib.jtsm_event_destroy(C.c_void_p(e))
+                lib.jtsm_event_destroy(e)
         except Exception:
             pass
 
@@ -453,11 +452,11 @@ def _timed(variant, flops, call, shape=None, extra_elems=0, out_elems=0, planes=
     lib = L.lib()
     span = LaunchSpan()
     st = L.stream()
-    lib.jtsm_event_record(C.c_void_p(span.a), st)
-    lib.jtsm_conv_set_mid_event(C.c_void_p(span.mid))
+    lib.jtsm_event_record(span.a, st)
+    lib.jtsm_conv_set_mid_event(span.mid)
     rc = call()
     lib.jtsm_conv_set_mid_event(None)
-    lib.jtsm_event_record(C.c_void_p(span.b), st)
+    lib.jtsm_event_record(span.b, st)
     if variant is not None:
         variant.segment = SEGMENT
     LAUNCH_LOG.append((variant, flops, span, shape, finish_bytes))
@@ -551,19 +550,19 @@ def conv2d_forward(x, w, stride=1, pad=0, dil=1, scale=None, bias=None, residual
         if MATH == "f16":
             L.check(_timed(_x3_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_f16(
                 xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), int(bool(relu)),
-                L.ptr(ws), C.c_size_t(nbytes), L.stream()), pl.desc, _numel(residual), y.numel(), ybuf is not None),
+                L.ptr(ws), nbytes, L.stream()), pl.desc, _numel(residual), y.numel(), ybuf is not None),
                     "conv2d_forward_f16")
         else:
             L.check(_timed(_x3_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_bf16x3(
                 xh, xl, wh, wl, L.ptr(y), yh, yl, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), int(bool(relu)),
-                L.ptr(ws), C.c_size_t(nbytes), L.stream()), pl.desc, _numel(residual), y.numel(), ybuf is not None),
+                L.ptr(ws), nbytes, L.stream()), pl.desc, _numel(residual), y.numel(), ybuf is not None),
                     "conv2d_forward_bf16x3")
         if ybuf is not None:
             planes_put(y, ybuf)
         return y
     L.check(_timed(_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_f32(
         L.ptr(x), L.ptr(w), L.ptr(y), pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), int(bool(relu)),
-        L.ptr(ws), C.c_size_t(nbytes), L.stream()), pl.desc, _numel(residual), y.numel()), "conv2d_forward")
+        L.ptr(ws), nbytes, L.stream()), pl.desc, _numel(residual), y.numel()), "conv2d_forward")
     return y
 
 
@@ -599,19 +598,19 @@ def conv2d_backward_data(dy, w, x_shape, stride=1, pad=0, dil=1, kscale=None, ac
         if MATH == "f16":
             L.check(_timed(_x3_variant(s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_f16(
                 gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(accumulate), L.ptr(relu_mask), GRAD_SHIFT, L.ptr(ws),
-                C.c_size_t(nbytes), L.stream()), pl.desc, _numel(accumulate) + _numel(relu_mask), dx.numel(),
+                nbytes, L.stream()), pl.desc, _numel(accumulate) + _numel(relu_mask), dx.numel(),
                     dbuf is not None), "conv2d_backward_data_f16")
         else:
             L.check(_timed(_x3_variant(s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_bf16x3(
                 gh, gl, wh, wl, L.ptr(dx), dh, dl, pl.ref, L.ptr(accumulate), L.ptr(relu_mask), L.ptr(ws),
-                C.c_size_t(nbytes), L.stream()), pl.desc, _numel(accumulate) + _numel(relu_mask), dx.numel(),
+                nbytes, L.stream()), pl.desc, _numel(accumulate) + _numel(relu_mask), dx.numel(),
                     dbuf is not None), "conv2d_backward_data_bf16x3")
         if dbuf is not None:
             planes_put(dx, dbuf)
         return dx
     L.check(_timed(_variant(s, 1, kscale is not None), pl.flops, lambda: lib.jtsm_conv2d_backward_data_f32(
         L.ptr(dy), L.ptr(w), L.ptr(dx), pl.ref, L.ptr(kscale), L.ptr(accumulate), L.ptr(relu_mask),
-        L.ptr(ws), C.c_size_t(nbytes), L.stream()), pl.desc, _numel(accumulate) + _numel(relu_mask), dx.numel()),
+        L.ptr(ws), nbytes, L.stream()), pl.desc, _numel(accumulate) + _numel(relu_mask), dx.numel()),
             "conv2d_backward_data")
     return dx
 
@@ -647,11 +646,11 @@ def conv2d_backward_weight(dy, x, w_shape, stride=1, pad=0, dil=1, row_scale=Non
         ws = _scratch(nbytes, x.device)
         if MATH == "f16":
             L.check(_timed(_x3_variant(s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_f16(
-                gh, xh, L.ptr(out), pl.ref, L.ptr(row_scale), int(fresh), GRAD_SHIFT, L.ptr(ws), C.c_size_t(nbytes),
+                gh, xh, L.ptr(out), pl.ref, L.ptr(row_scale), int(fresh), GRAD_SHIFT, L.ptr(ws), nbytes,
                 L.stream()), pl.desc, 0, out.numel()), "conv2d_backward_weight_f16")
         else:
             L.check(_timed(_x3_variant(s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_bf16x3(
-                gh, gl, xh, xl, L.ptr(out), pl.ref, L.ptr(row_scale), int(fresh), L.ptr(ws), C.c_size_t(nbytes),
+                gh, gl, xh, xl, L.ptr(out), pl.ref, L.ptr(row_scale), int(fresh), L.ptr(ws), nbytes,
                 L.stream()), pl.desc, 0, out.numel()), "conv2d_backward_weight_bf16x3")
         return out
     if bias_out is not None:
@@ -731,11 +730,11 @@ def conv_transpose2x2_backward_data(g, w, relu_mask=None, emit_planes=False):
     lib = L.lib()
     if MATH == "f16":
         L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_f16(
-            gh, wh, L.ptr(dx), dh, n, h, wd, i, o, L.ptr(relu_mask), None, GRAD_SHIFT, L.ptr(ws), C.c_size_t(nbytes),
+            gh, wh, L.ptr(dx), dh, n, h, wd, i, o, L.ptr(relu_mask), None, GRAD_SHIFT, L.ptr(ws), nbytes,
             L.stream()), pl.desc, _numel(relu_mask), dx.numel(), dbuf is not None), "conv_transpose2x2_backward_data_f16")
     else:
         L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_bf16x3(
-            gh, gl, wh, wl, L.ptr(dx), dh, dl, n, h, wd, i, o, L.ptr(relu_mask), None, L.ptr(ws), C.c_size_t(nbytes),
+            gh, gl, wh, wl, L.ptr(dx), dh, dl, n, h, wd, i, o, L.ptr(relu_mask), None, L.ptr(ws), nbytes,
             L.stream()), pl.desc, _numel(relu_mask), dx.numel(), dbuf is not None),
                 "conv_transpose2x2_backward_data_bf16x3")
     if dbuf is not None:
@@ -811,18 +810,18 @@ def planes_forward(x, w, stride=1, pad=0, dil=1, bias=None, relu=False, fp32=Fal
         assert MATH == "f16" and residual is None and tuple(residual_plane.shape) == oshape
         rh = _hl(residual_plane.buf)[0]
         L.check(_timed(_x3_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_res16_f16(
-            xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), rh, int(bool(relu)), L.ptr(ws),
-            C.c_size_t(nbytes), L.stream()), pl.desc, 0.5 * n_out, n_out, yp is not None, bool(fp32)),
+            xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), rh, int(bool(relu)), L.ptr(ws), nbytes,
+            L.stream()), pl.desc, 0.5 * n_out, n_out, yp is not None, bool(fp32)),
                 "conv2d_forward_res16_f16")
     elif MATH == "f16":
         L.check(_timed(_x3_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_f16(
             xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), int(bool(relu)), L.ptr(ws),
-            C.c_size_t(nbytes), L.stream()), pl.desc, _numel(residual), n_out, yp is not None, bool(fp32)),
+            nbytes, L.stream()), pl.desc, _numel(residual), n_out, yp is not None, bool(fp32)),
                 "conv2d_forward_f16")
     else:
         L.check(_timed(_x3_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_bf16x3(
             xh, xl, wh, wl, L.ptr(y), yh, yl, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), int(bool(relu)),
-            L.ptr(ws), C.c_size_t(nbytes), L.stream()), pl.desc, _numel(residual), n_out, yp is not None, bool(fp32)),
+            L.ptr(ws), nbytes, L.stream()), pl.desc, _numel(residual), n_out, yp is not None, bool(fp32)),
                 "conv2d_forward_bf16x3")
     if both:
         return y, yp
@@ -904,11 +903,11 @@ def _planes_backward_data_colsum(g, w, x_shape, stride, pad, dil, gate, kscale, 
     if MATH == "f16":
         L.check(_timed(_x3_variant(pl.s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_colsum_f16(
             gh, wh, None, dh, pl.ref, L.ptr(row_scale), None, None, gate_h, GRAD_SHIFT, L.ptr(part), L.ptr(ws),
-            C.c_size_t(nbytes), L.stream()), pl.desc, extra, dp.numel, True, False), "conv2d_backward_data_colsum_f16")
+            nbytes, L.stream()), pl.desc, extra, dp.numel, True, False), "conv2d_backward_data_colsum_f16")
     else:
         L.check(_timed(_x3_variant(pl.s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_colsum_bf16x3(
             gh, gl, wh, wl, None, dh, dl, pl.ref, L.ptr(row_scale), None, None, gate_h, L.ptr(part), L.ptr(ws),
-            C.c_size_t(nbytes), L.stream()), pl.desc, extra, dp.numel, True, False), "conv2d_backward_data_colsum_bf16x3")
+            nbytes, L.stream()), pl.desc, extra, dp.numel, True, False), "conv2d_backward_data_colsum_bf16x3")
     bias_out.take(part)
     return dp, True
 
@@ -950,15 +949,15 @@ def _planes_backward_data(g, w, x_shape, stride=1, pad=0, dil=1, gate=None, fp32
         assert MATH == "f16" and accumulate is None and into is None and tuple(accumulate_plane.shape) == tuple(x_shape)
         ah = _hl(accumulate_plane.buf)[0]
         L.check(_timed(_x3_variant(s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_acc16_f16(
-            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), ah, gate_h, GRAD_SHIFT, L.ptr(ws), C.c_size_t(nbytes),
+            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), ah, gate_h, GRAD_SHIFT, L.ptr(ws), nbytes,
             L.stream()), pl.desc, extra + 0.5 * n_in, n_in, dp is not None, fp32), "conv2d_backward_data_acc16_f16")
     elif MATH == "f16":
         L.check(_timed(_x3_variant(s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_ex_f16(
-            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), L.ptr(accumulate), None, gate_h, GRAD_SHIFT, L.ptr(ws), C.c_size_t(nbytes), L.stream()),
+            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), L.ptr(accumulate), None, gate_h, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream()),
             pl.desc, extra, n_in, dp is not None, fp32), "conv2d_backward_data_ex_f16")
     else:
         L.check(_timed(_x3_variant(s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_ex_bf16x3(
-            gh, gl, wh, wl, L.ptr(dx), dh, dl, pl.ref, L.ptr(row_scale), L.ptr(accumulate), None, gate_h, L.ptr(ws), C.c_size_t(nbytes),
+            gh, gl, wh, wl, L.ptr(dx), dh, dl, pl.ref, L.ptr(row_scale), L.ptr(accumulate), None, gate_h, L.ptr(ws), nbytes,
             L.stream()), pl.desc, extra, n_in, dp is not None, fp32), "conv2d_backward_data_ex_bf16x3")
     if both:
         return dx, dp
@@ -990,11 +989,11 @@ def planes_backward_weight(g, x, w, stride=1, pad=0, dil=1, w_shape=None, row_sc
     lib = L.lib()
     if MATH == "f16":
         L.check(_timed(_x3_variant(s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_f16(
-            gh, xh, L.ptr(out), pl.ref, L.ptr(row_scale), 1, GRAD_SHIFT, L.ptr(ws), C.c_size_t(nbytes), L.stream()),
+            gh, xh, L.ptr(out), pl.ref, L.ptr(row_scale), 1, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream()),
             pl.desc, 0, out.numel()), "conv2d_backward_weight_f16")
     else:
         L.check(_timed(_x3_variant(s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_bf16x3(
-            gh, gl, xh, xl, L.ptr(out), pl.ref, L.ptr(row_scale), 1, L.ptr(ws), C.c_size_t(nbytes), L.stream()),
+            gh, gl, xh, xl, L.ptr(out), pl.ref, L.ptr(row_scale), 1, L.ptr(ws), nbytes, L.stream()),
             pl.desc, 0, out.numel()), "conv2d_backward_weight_bf16x3")
     return out
 
@@ -1260,7 +1259,6 @@ def flush_deferred_weight_gradients():
             ptr_t = C.c_void_p * n
             gh, gl = zip(*[_hl(g.buf) for g, *_ in part])
             xh, xl = zip(*[_hl(x.buf) for _, x, *_ in part])
-            val = lambda v: v.value if isinstance(v, C.c_void_p) else v   # noqa: E731
             dws = ptr_t(*[o.data_ptr() for o in outs])
             scales = ptr_t(*[(it[6].data_ptr() if it[6] is not None else None) for it in part])
             nbytes = lib.jtsm_conv_bf16x3_wgrad_group_workspace_bytes(pl.ref, n)
@@ -1278,12 +1276,11 @@ def flush_deferred_weight_gradients():
             desc = pl.desc[:-1] + (pl.desc[-1] * n,) if pl.desc is not None else None
             if MATH == "f16":
                 call = lambda: lib.jtsm_conv2d_backward_weight_group_f16(      # noqa: E731
-                    n, ptr_t(*[val(v) for v in gh]), ptr_t(*[val(v) for v in xh]), dws, scales, pl.ref, GRAD_SHIFT,
-                    L.ptr(ws), C.c_size_t(nbytes), L.stream())
+                    n, ptr_t(*gh), ptr_t(*xh), dws, scales, pl.ref, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream())
             else:
                 call = lambda: lib.jtsm_conv2d_backward_weight_group_bf16x3(   # noqa: E731
-                    n, ptr_t(*[val(v) for v in gh]), ptr_t(*[val(v) for v in gl]), ptr_t(*[val(v) for v in xh]),
-                    ptr_t(*[val(v) for v in xl]), dws, scales, pl.ref, L.ptr(ws), C.c_size_t(nbytes), L.stream())
+                    n, ptr_t(*gh), ptr_t(*gl), ptr_t(*xh), ptr_t(*xl), dws, scales, pl.ref, L.ptr(ws), nbytes,
+                    L.stream())
             L.check(_timed(variant, pl.flops * n, call, desc, 0, outs[0].numel() * n), "conv2d_backward_weight_group")
             for (g, x, w, *_), o in zip(part, outs):
                 _deliver_grad(w, o)
@@ -1298,9 +1295,8 @@ def planes_channel_sum(g, grad=True):
     ws = _scratch(nbytes, g.device)
     gh, gl = _hl(g.buf)
     L.note_bytes((2.0 if MATH == "f16" else 4.0) * g.numel)
-    L.check(L.lib().jtsm_channel_sum_planes(gh, gl, L.ptr(out), C.c_long(rows), ch,
-                                                  GRAD_SHIFT if (grad and MATH == "f16") else 0, L.ptr(ws),
-                                                  C.c_size_t(nbytes), L.stream()), "channel_sum_planes")
+    L.check(L.lib().jtsm_channel_sum_planes(gh, gl, L.ptr(out), rows, ch, GRAD_SHIFT if (grad and MATH == "f16") else 0,
+                                            L.ptr(ws), nbytes, L.stream()), "channel_sum_planes")
     return out
 
 
@@ -1321,7 +1317,7 @@ def planes_channel_sum_multi(gs, grad=True):
     L.note_bytes((2.0 if MATH == "f16" else 4.0) * sum(g.numel for g in gs))
     L.check(L.lib().jtsm_channel_sum_planes_multi(his, los, optr, rows, n, ch,
                                                   GRAD_SHIFT if (grad and MATH == "f16") else 0, L.ptr(ws),
-                                                  C.c_size_t(nbytes), L.stream()), "channel_sum_planes_multi")
+                                                  nbytes, L.stream()), "channel_sum_planes_multi")
     return [outs[i] for i in range(n)]
 
 
@@ -1373,11 +1369,11 @@ def planes_conv_transpose2x2_backward_data(g, w, gate=None, bias_out=None):
         extra = 0.5 * dp.numel if gate is not None else 0
         if MATH == "f16":
             L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_colsum_f16(
-                gh, wh, None, dh, n, h, wd, i, o, None, gate_h, GRAD_SHIFT, L.ptr(part), L.ptr(ws), C.c_size_t(nbytes),
+                gh, wh, None, dh, n, h, wd, i, o, None, gate_h, GRAD_SHIFT, L.ptr(part), L.ptr(ws), nbytes,
                 L.stream()), pl.desc, extra, dp.numel, True, False), "conv_transpose2x2_backward_data_colsum_f16")
         else:
             L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_colsum_bf16x3(
-                gh, gl, wh, wl, None, dh, dl, n, h, wd, i, o, None, gate_h, L.ptr(part), L.ptr(ws), C.c_size_t(nbytes),
+                gh, gl, wh, wl, None, dh, dl, n, h, wd, i, o, None, gate_h, L.ptr(part), L.ptr(ws), nbytes,
                 L.stream()), pl.desc, extra, dp.numel, True, False), "conv_transpose2x2_backward_data_colsum_bf16x3")
         bias_out.take(part)
         return dp, True
@@ -1391,11 +1387,11 @@ def planes_conv_transpose2x2_backward_data(g, w, gate=None, bias_out=None):
     extra = 0.5 * dp.numel if gate is not None else 0
     if MATH == "f16":
         L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_f16(
-            gh, wh, None, dh, n, h, wd, i, o, None, gate_h, GRAD_SHIFT, L.ptr(ws), C.c_size_t(nbytes), L.stream()),
+            gh, wh, None, dh, n, h, wd, i, o, None, gate_h, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream()),
             pl.desc, extra, dp.numel, True, False), "conv_transpose2x2_backward_data_f16")
     else:
         L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_bf16x3(
-            gh, gl, wh, wl, None, dh, dl, n, h, wd, i, o, None, gate_h, L.ptr(ws), C.c_size_t(nbytes), L.stream()),
+            gh, gl, wh, wl, None, dh, dl, n, h, wd, i, o, None, gate_h, L.ptr(ws), nbytes, L.stream()),
             pl.desc, extra, dp.numel, True, False), "conv_transpose2x2_backward_data_bf16x3")
     return (dp, False) if bias_out is not None else dp
 
@@ -1464,11 +1460,11 @@ def _wgrad_bias_call(pl, gh, gl, xh, xl, out, bias_out, row_scale, fresh, device
     if MATH == "f16":
         L.check(_timed(_x3_variant(pl.s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_bias_f16(
             gh, xh, L.ptr(out), L.ptr(bias_out), pl.ref, L.ptr(row_scale), int(fresh), GRAD_SHIFT, L.ptr(ws),
-            C.c_size_t(nbytes), L.stream()), pl.desc, 0, out.numel()), "conv2d_backward_weight_bias_f16")
+            nbytes, L.stream()), pl.desc, 0, out.numel()), "conv2d_backward_weight_bias_f16")
     else:
         L.check(_timed(_x3_variant(pl.s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_bias_bf16x3(
             gh, gl, xh, xl, L.ptr(out), L.ptr(bias_out), pl.ref, L.ptr(row_scale), int(fresh), L.ptr(ws),
-            C.c_size_t(nbytes), L.stream()), pl.desc, 0, out.numel()), "conv2d_backward_weight_bias_bf16x3")
+            nbytes, L.stream()), pl.desc, 0, out.numel()), "conv2d_backward_weight_bias_bf16x3")
 
 
 class _ConvFused(Function):

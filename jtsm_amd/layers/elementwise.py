@@ -28,15 +28,14 @@ def relu_backward(dy, y, emit_planes=False):
         hi, lo = conv._hl(buf)
         L.note_bytes((14.0 if conv.MATH == "f16" else 16.0) * n)   # dy, y read; g and its planes written
         if conv.MATH == "f16":
-            L.check(L.lib().jtsm_relu_backward_split_f16(L.ptr(dy), L.ptr(y), L.ptr(g), hi, C.c_long(n), conv.GRAD_SHIFT,
+            L.check(L.lib().jtsm_relu_backward_split_f16(L.ptr(dy), L.ptr(y), L.ptr(g), hi, n, conv.GRAD_SHIFT,
                                                          L.stream()), "relu_backward_split_f16")
         else:
-            L.check(L.lib().jtsm_relu_backward_split_f32(L.ptr(dy), L.ptr(y), L.ptr(g), hi, lo, C.c_long(n),
-                                                         L.stream()), "relu_backward_split")
+            L.check(L.lib().jtsm_relu_backward_split_f32(L.ptr(dy), L.ptr(y), L.ptr(g), hi, lo, n, L.stream()),
+                    "relu_backward_split")
         conv.planes_put(g, buf)
         return g
-    L.check(L.lib().jtsm_relu_backward_f32(L.ptr(dy), L.ptr(y), L.ptr(g), C.c_long(n), L.stream()),
-            "relu_backward")
+    L.check(L.lib().jtsm_relu_backward_f32(L.ptr(dy), L.ptr(y), L.ptr(g), n, L.stream()), "relu_backward")
     return g
 
 
@@ -52,11 +51,10 @@ def channel_sum(g):
     out = torch.empty(ch, dtype=g.dtype, device=g.device)
     from . import conv
     lib = L.lib()
-    nbytes = lib.jtsm_channel_sum_workspace_bytes(C.c_long(rows), ch)
+    nbytes = lib.jtsm_channel_sum_workspace_bytes(rows, ch)
     ws = conv._scratch(nbytes, g.device)      # the contractions' scratch: same stream, in order
     L.note_bytes(4.0 * g.numel())
-    L.check(lib.jtsm_channel_sum_ws_f32(L.ptr(g), L.ptr(out), C.c_long(rows), ch, L.ptr(ws), C.c_size_t(nbytes),
-                                        L.stream()), "channel_sum")
+    L.check(lib.jtsm_channel_sum_ws_f32(L.ptr(g), L.ptr(out), rows, ch, L.ptr(ws), nbytes, L.stream()), "channel_sum")
     return out
 
 
@@ -73,7 +71,7 @@ def relu_backward_scaled(dy, y, scale):
     hi, lo = conv._hl(buf)
     L.note_bytes((14.0 if conv.MATH == "f16" else 16.0) * n)
     L.check(L.lib().jtsm_relu_backward_split_scaled_f32(
-        L.ptr(dy), L.ptr(y), L.f32(scale), L.ptr(g), hi, lo, C.c_long(n), conv.GRAD_SHIFT if conv.MATH == "f16" else 0,
+        L.ptr(dy), L.ptr(y), scale, L.ptr(g), hi, lo, n, conv.GRAD_SHIFT if conv.MATH == "f16" else 0,
         L.stream()), "relu_backward_split_scaled")
     return g, buf
 
@@ -86,7 +84,7 @@ def split_rowscale(x2d, row_scale):
     buf = conv._planes_buf(r * k, x2d.device)
     hi, lo = conv._hl(buf)
     L.note_bytes((6.0 if conv.MATH == "f16" else 8.0) * r * k)
-    L.check(L.lib().jtsm_split_rowscale_f32(L.ptr(x2d), L.ptr(row_scale), C.c_long(r), k, hi, lo, 0, L.stream()),
+    L.check(L.lib().jtsm_split_rowscale_f32(L.ptr(x2d), L.ptr(row_scale), r, k, hi, lo, 0, L.stream()),
             "split_rowscale")
     return buf
 
@@ -100,8 +98,7 @@ def dropout_split_(y, p, seed):
     buf = conv._planes_buf(n, y.device)
     hi, lo = conv._hl(buf)
     L.note_bytes((10.0 if conv.MATH == "f16" else 12.0) * n)
-    L.check(L.lib().jtsm_dropout_split_f32(L.ptr(y), L.ptr(y), hi, lo, C.c_long(n), L.f32(p), C.c_ulonglong(seed),
-                                           L.stream()), "dropout_split")
+    L.check(L.lib().jtsm_dropout_split_f32(L.ptr(y), L.ptr(y), hi, lo, n, p, seed, L.stream()), "dropout_split")
     return buf
 
 
@@ -220,7 +217,7 @@ class _SumTensors(torch.autograd.Function):
             buf = conv._planes_buf(n, out.device)
             hi, lo = conv._hl(buf)
         ptrs = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
-        L.check(L.lib().jtsm_sum_tensors_f32(ptrs, len(xs), C.c_long(n), L.ptr(out), hi, lo, L.stream()), "sum_tensors")
+        L.check(L.lib().jtsm_sum_tensors_f32(ptrs, len(xs), n, L.ptr(out), hi, lo, L.stream()), "sum_tensors")
         if buf is not None:
             conv.planes_put(out, buf)
         ctx.n = len(xs)
@@ -283,9 +280,9 @@ class _GroupNormReLU(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty((n, groups), dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
-        ws = torch.empty(lib.jtsm_group_norm_workspace_bytes(n, C.c_long(h * w), c), dtype=torch.uint8, device=x.device)
+        ws = torch.empty(lib.jtsm_group_norm_workspace_bytes(n, h * w, c), dtype=torch.uint8, device=x.device)
         L.check(lib.jtsm_group_norm_forward_f32(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y), L.ptr(mean),
-                                                L.ptr(rstd), L.ptr(ws), n, C.c_long(h * w), c, groups, L.f32(eps),
+                                                L.ptr(rstd), L.ptr(ws), n, h * w, c, groups, eps,
                                                 int(relu), L.stream()), "group_norm_forward")
         ctx.save_for_backward(x, gamma, beta, mean, rstd)
         ctx.cfg = (groups, relu)
@@ -301,14 +298,13 @@ class _GroupNormReLU(torch.autograd.Function):
         from . import conv
         dx = torch.empty_like(x)
         dg, db = torch.empty_like(gamma), torch.empty_like(beta)
-        ws = torch.empty(lib.jtsm_group_norm_workspace_bytes(n, C.c_long(h * w), c), dtype=torch.uint8, device=x.device)
+        ws = torch.empty(lib.jtsm_group_norm_workspace_bytes(n, h * w, c), dtype=torch.uint8, device=x.device)
         # dx is the output gradient of the convolution in front of this norm: hand it its bf16 planes as well
         buf = conv._planes_buf(dx.numel(), dx.device) if (conv.MATH == "bf16x3" and c % 8 == 0) else None
         hi, lo = conv._hl(buf)
         L.check(lib.jtsm_group_norm_backward_f32(L.ptr(x), L.ptr(dy), L.ptr(gamma), L.ptr(beta), L.ptr(mean),
                                                  L.ptr(rstd), L.ptr(dx), hi, lo, L.ptr(dg), L.ptr(db), L.ptr(ws), n,
-                                                 C.c_long(h * w), c, groups, int(relu), L.stream()),
-                "group_norm_backward")
+                                                 h * w, c, groups, int(relu), L.stream()), "group_norm_backward")
         if buf is not None:
             conv.planes_put(dx, buf)
         return dx, dg, db, None, None, None
@@ -376,7 +372,7 @@ class _SemSegCE(torch.autograd.Function):
         wsb = torch.empty(lib.jtsm_semseg_ce_workspace_bytes(n, hs, ws, scale), dtype=torch.uint8, device=logits.device)
         L.note_bytes(4.0 * n * hs * ws * c + 8.0 * target.numel())     # stride-4 logits + full-resolution labels
         L.check(lib.jtsm_semseg_ce_forward_f32(L.ptr(logits), ld, c, L.ptr(target), L.ptr(out), L.ptr(wsb), n, hs, ws,
-                                               scale, C.c_long(ignore_index), L.stream()), "semseg_ce_forward")
+                                               scale, ignore_index, L.stream()), "semseg_ce_forward")
         ctx.save_for_backward(logits, target, out, wsb)
         ctx.cfg = (ld, scale, ignore_index)
         return out[0]
@@ -391,7 +387,7 @@ class _SemSegCE(torch.autograd.Function):
         L.note_bytes(4.0 * n * hs * ws * c + 8.0 * target.numel() + 4.0 * dfull.numel())
         L.check(L.lib().jtsm_semseg_ce_backward_f32(L.ptr(logits), ld, c, L.ptr(target), L.ptr(out), L.ptr(g),
                                                     L.ptr(dfull), L.ptr(wsb), n, hs, ws, scale,
-                                                    C.c_long(ignore_index), L.stream()), "semseg_ce_backward")
+                                                    ignore_index, L.stream()), "semseg_ce_backward")
         if ld != c:
             from .conv import ZERO_PADDED
             setattr(dfull, ZERO_PADDED, True)   # (the kernel wrote zeros into channels c .. ld - 1)

@@ -1,5 +1,7 @@
 """Fused pseudo-GT mining / labelling (jtsm_amd/csrc/mining.hip): device-side replacements for the
 get_pgt_top_k + label_and_sample_proposals glue of JTSMROIHeads (no autograd: label generation)."""
+import ctypes as C
+
 import torch
 
 from .. import _lib as L
@@ -58,7 +60,7 @@ def match_label(proposals, bag_offsets, pgt, classes, counts, bg_label, iou_thre
                scores=torch.empty(R, dtype=torch.float32, device=dev))
     L.check(L.lib().jtsm_match_label_f32(
         L.ptr(proposals), L.ptr(bag_offsets), B, R, L.ptr(pgt["boxes"]), L.ptr(classes), L.ptr(counts),
-        L.ptr(pgt["weights"]), L.ptr(pgt["scores"]), G, L.f32(iou_thresh), int(bg_label), L.ptr(out["labels"]),
+        L.ptr(pgt["weights"]), L.ptr(pgt["scores"]), G, iou_thresh, int(bg_label), L.ptr(out["labels"]),
         L.ptr(out["matched"]), L.ptr(out["boxes"]), L.ptr(out["weights"]), L.ptr(out["scores"]), L.stream()),
         "match_label")
     return out
@@ -77,7 +79,7 @@ def paint_sem_seg(boxes, classes, scores, counts, class_base, height, width, ero
     out = torch.empty((B, height, width), dtype=torch.int64, device=boxes.device)
     ws = torch.empty(lib.jtsm_paint_sem_seg_workspace_bytes(B), dtype=torch.uint8, device=boxes.device)
     L.check(lib.jtsm_paint_sem_seg(L.ptr(boxes), L.ptr(classes), L.ptr(scores), L.ptr(counts), B, G, int(class_base),
-                                   height, width, L.f32(erode), L.ptr(out), L.ptr(ws), L.stream()), "paint_sem_seg")
+                                   height, width, erode, L.ptr(out), L.ptr(ws), L.stream()), "paint_sem_seg")
     return out
 
 
@@ -115,7 +117,7 @@ def rect_mask_targets(rois, rects, side, height, width, erode=2.0):
     n = rois.shape[0]
     out = torch.empty((n, side, side), dtype=torch.uint8, device=rois.device)
     L.check(L.lib().jtsm_rect_mask_targets_f32(L.ptr(rois), L.ptr(rects), L.ptr(out), n, side, height, width,
-                                               L.f32(erode), L.stream()), "rect_mask_targets")
+                                               erode, L.stream()), "rect_mask_targets")
     return out.view(torch.bool)      # (0 / 1 bytes: the same memory read as bool, no pass)
 
 
@@ -161,7 +163,7 @@ def paste_crop_targets(probs, rois, side, height, width, threshold=0.5):
     n, m = probs.shape[0], probs.shape[-1]
     out = torch.empty((n, side, side), dtype=torch.uint8, device=rois.device)
     L.check(L.lib().jtsm_paste_crop_targets_f32(L.ptr(probs), L.ptr(rois), L.ptr(out), n, m, side, height, width,
-                                                L.f32(threshold), L.stream()), "paste_crop_targets")
+                                                threshold, L.stream()), "paste_crop_targets")
     return out.view(torch.bool)      # (0 / 1 bytes: the same memory read as bool, no pass)
 
 
@@ -172,7 +174,6 @@ MAX_IMAGES = 16
 def _image_rows(tensors, dtype):
     """(pointer array, count array) of per-image device tensors for the `B pointers + counts` entry points; the
     tensors are made contiguous / cast here and returned so that they outlive the launch."""
-    import ctypes as C
     keep = [t.to(dtype).contiguous() for t in tensors]
     ptrs = (C.c_void_p * len(keep))(*[t.data_ptr() if t.numel() else None for t in keep])
     counts = (C.c_int * len(keep))(*[int(t.shape[0]) for t in keep])
@@ -183,15 +184,14 @@ def _image_rows(tensors, dtype):
 def pooler_rois_levels(box_tensors, min_level, max_level, canonical_box_size, canonical_level):
     """list of per-image (n_i, 4) float32 boxes -> (rois (M,5) float32, level (M,) int32): detectron2's
     convert_boxes_to_pooler_format + assign_boxes_to_levels in one launch, the same levels bit for bit."""
-    import ctypes as C
     L.require_gpu(*box_tensors)
     ptrs, counts, keep = _image_rows([b.reshape(-1, 4) for b in box_tensors], torch.float32)
     M, dev = sum(int(t.shape[0]) for t in keep), keep[0].device
     rois = torch.empty((M, 5), dtype=torch.float32, device=dev)
     level = torch.empty(M, dtype=torch.int32, device=dev)
     L.check(L.lib().jtsm_pooler_rois_levels_f32(ptrs, counts, len(keep), int(min_level), int(max_level),
-                                                C.c_float(canonical_box_size), C.c_float(canonical_level), L.ptr(rois),
-                                                L.ptr(level), L.stream()), "pooler_rois_levels")
+                                                canonical_box_size, canonical_level, L.ptr(rois), L.ptr(level),
+                                                L.stream()), "pooler_rois_levels")
     return rois, level
 
 
@@ -216,7 +216,6 @@ def image_labels(gt_classes_list, num_classes, gt_sem_seg=None, num_stuff=0, stu
     L.require_gpu(*gt_classes_list)
     B, dev = len(gt_classes_list), gt_classes_list[0].device
     ptrs, counts, keep = _image_rows(gt_classes_list, torch.int64)
-    import ctypes as C
 
     def triple(width):      # one allocation carved into (presence (B,width) float32, list (B,width) int32, count (B,) int32)
         words = torch.empty(B * (2 * width + 1), dtype=torch.int32, device=dev)
@@ -233,7 +232,7 @@ def image_labels(gt_classes_list, num_classes, gt_sem_seg=None, num_stuff=0, stu
         esz, pixels = sem.element_size(), sem[0].numel()
         oh_s, cls_s, cnt_s = triple(num_stuff - 1)
         ws = torch.empty(L.lib().jtsm_image_labels_workspace_bytes(B), dtype=torch.uint8, device=dev)
-    L.check(L.lib().jtsm_image_labels(ptrs, counts, B, num_classes, L.ptr(sem), esz, C.c_long(pixels), num_stuff,
+    L.check(L.lib().jtsm_image_labels(ptrs, counts, B, num_classes, L.ptr(sem), esz, pixels, num_stuff,
                                       stuff_offset, L.ptr(oh_t), L.ptr(cls_t), L.ptr(cnt_t), L.ptr(oh_s), L.ptr(cls_s),
                                       L.ptr(cnt_s), L.ptr(ws), L.stream()), "image_labels")
     return oh_t, cls_t, cnt_t, oh_s, cls_s, cnt_s

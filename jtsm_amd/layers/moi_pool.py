@@ -29,22 +29,19 @@ def moi_pool_forward(input, rois, spatial_scale, pooled_h, pooled_w, oh_labels, 
     if out.numel() == 0:
         return out, arg
     if input.dtype == torch.float16:   # fp16 at the boundary (MOIPool_cuda.cu:400 dispatches on half too)
-        import ctypes as C
         lib = L.lib()
-        lib.jtsm_moi_pool_f16_workspace_bytes.restype = C.c_size_t
         nb = lib.jtsm_moi_pool_f16_workspace_bytes(B, Cc, H, W, M, Lw, pooled_h, pooled_w)
         ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
         L.check(lib.jtsm_moi_pool_forward_f16(
-            L.ptr(x), L.ptr(rois), L.ptr(oh), L.ptr(sp), L.ptr(out), L.ptr(arg), L.ptr(ws), C.c_size_t(nb), B, Cc, H, W,
-            M, Lw, sp.shape[1], sp.shape[2], L.f32(spatial_scale), pooled_h, pooled_w, layout, L.stream()),
+            L.ptr(x), L.ptr(rois), L.ptr(oh), L.ptr(sp), L.ptr(out), L.ptr(arg), L.ptr(ws), nb, B, Cc, H, W,
+            M, Lw, sp.shape[1], sp.shape[2], spatial_scale, pooled_h, pooled_w, layout, L.stream()),
             "moi_pool_forward_f16")
         return out, arg
     nbytes = L.lib().jtsm_moi_pool_workspace_bytes(B, H, W, M, Lw)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     L.check(L.lib().jtsm_moi_pool_forward_f32(
         L.ptr(x), L.ptr(rois), L.ptr(oh), L.ptr(sp), L.ptr(out), L.ptr(arg), L.ptr(ws), B, Cc, H,
-        W, M, Lw, sp.shape[1], sp.shape[2], L.f32(spatial_scale), pooled_h, pooled_w, layout,
-        L.stream()), "moi_pool_forward")
+        W, M, Lw, sp.shape[1], sp.shape[2], spatial_scale, pooled_h, pooled_w, layout, L.stream()), "moi_pool_forward")
     return out, arg
 
 
@@ -59,14 +56,11 @@ def moi_pool_backward(grad, rois, argmax, spatial_scale, pooled_h, pooled_w, B, 
     if gin.numel() == 0:
         return gin
     if g.dtype == torch.float16:
-        import ctypes as C
         lib = L.lib()
-        lib.jtsm_pool_f16_workspace_bytes.restype = C.c_size_t
-        nb = lib.jtsm_pool_f16_workspace_bytes(C.c_long(g.numel()), C.c_long(rois.numel()), C.c_long(gin.numel()),
-                                               C.c_size_t(0))
+        nb = lib.jtsm_pool_f16_workspace_bytes(g.numel(), rois.numel(), gin.numel(), 0)
         ws = torch.empty(nb, dtype=torch.uint8, device=g.device)
         L.check(lib.jtsm_moi_pool_backward_f16(
-            L.ptr(g), L.ptr(rois.contiguous()), L.ptr(a), L.ptr(gin), L.ptr(ws), C.c_size_t(nb), B, Cc, H, W,
+            L.ptr(g), L.ptr(rois.contiguous()), L.ptr(a), L.ptr(gin), L.ptr(ws), nb, B, Cc, H, W,
             rois.shape[0], pooled_h, pooled_w, layout, L.stream()), "moi_pool_backward_f16")
         return gin
     L.check(L.lib().jtsm_moi_pool_backward_f32(

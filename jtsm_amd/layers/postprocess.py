@@ -18,11 +18,6 @@ def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-def _sizet(fn, *args):
-    fn.restype = C.c_size_t
-    return int(fn(*args))
-
-
 @torch.no_grad()
 def oicr_predict(logits_heads, deltas_heads, proposal_boxes, weights, scale_clamp):
     """Mean over heads of the row soft-max and Box2BoxTransform.apply_deltas of the mean deltas
@@ -43,7 +38,7 @@ def oicr_predict(logits_heads, deltas_heads, proposal_boxes, weights, scale_clam
         proposal_boxes = proposal_boxes.contiguous()
     w = (C.c_float * 4)(*[float(v) for v in weights]) if deltas_heads is not None else None
     L.check(L.lib().jtsm_oicr_predict_f32(_ptr_array(logits_heads), dptr, len(logits_heads), R, C1, kb,
-                                          L.ptr(proposal_boxes) if boxes is not None else None, w, L.f32(scale_clamp),
+                                          L.ptr(proposal_boxes) if boxes is not None else None, w, scale_clamp,
                                           L.ptr(probs), L.ptr(boxes), L.stream()), "oicr_predict")
     return probs, boxes
 
@@ -63,11 +58,10 @@ def batched_nms_device(boxes, scores, idxs, iou_threshold, num_classes, max_per_
     scores = scores.to(torch.float32).contiguous()
     idxs = idxs.to(torch.int64).contiguous()
     lib = L.lib()
-    nbytes = _sizet(lib.jtsm_batched_nms_workspace_bytes, n, int(num_classes), int(max_per_class))
-    ws = _ws(nbytes, dev)
+    ws = _ws(lib.jtsm_batched_nms_workspace_bytes(n, int(num_classes), int(max_per_class)), dev)
     L.check(lib.jtsm_batched_nms_f32(L.ptr(boxes), L.ptr(scores), L.ptr(idxs), n, int(num_classes), int(max_per_class),
-                                     L.f32(iou_threshold), int(coordinate_trick), L.ptr(keep), L.ptr(num), L.ptr(ovf),
-                                     L.ptr(ws), C.c_size_t(ws.numel()), L.stream()), "batched_nms")
+                                     iou_threshold, int(coordinate_trick), L.ptr(keep), L.ptr(num), L.ptr(ovf),
+                                     L.ptr(ws), ws.numel(), L.stream()), "batched_nms")
     return keep, num, ovf
 
 
@@ -87,11 +81,11 @@ def fast_rcnn_inference_device(boxes, scores, image_shape, score_thresh, nms_thr
                rows=torch.empty(cap, dtype=torch.int64, device=dev),
                count=torch.zeros(1, dtype=torch.int32, device=dev))
     lib = L.lib()
-    ws = _ws(_sizet(lib.jtsm_fast_rcnn_inference_workspace_bytes, R, K), dev)
+    ws = _ws(lib.jtsm_fast_rcnn_inference_workspace_bytes(R, K), dev)
     L.check(lib.jtsm_fast_rcnn_inference_f32(
-        L.ptr(boxes), L.ptr(scores), R, K, kb, L.f32(image_shape[0]), L.f32(image_shape[1]), L.f32(score_thresh),
-        L.f32(nms_thresh), int(topk), cap, L.ptr(out["boxes"]), L.ptr(out["scores"]), L.ptr(out["classes"]),
-        L.ptr(out["rows"]), L.ptr(out["count"]), L.ptr(ws), C.c_size_t(ws.numel()), L.stream()), "fast_rcnn_inference")
+        L.ptr(boxes), L.ptr(scores), R, K, kb, image_shape[0], image_shape[1], score_thresh, nms_thresh, int(topk),
+        cap, L.ptr(out["boxes"]), L.ptr(out["scores"]), L.ptr(out["classes"]), L.ptr(out["rows"]), L.ptr(out["count"]),
+        L.ptr(ws), ws.numel(), L.stream()), "fast_rcnn_inference")
     return out
 
 
@@ -119,7 +113,7 @@ def paste_masks(masks, boxes, img_h, img_w, threshold=0.5):
     for s in range(0, N, 65535):
         e = min(N, s + 65535)
         L.check(L.lib().jtsm_paste_masks_f32(L.ptr(masks[s:e]), L.ptr(boxes[s:e]), e - s, M, int(img_h), int(img_w),
-                                             L.f32(threshold), L.ptr(out[s:e]), L.stream()), "paste_masks")
+                                             threshold, L.ptr(out[s:e]), L.stream()), "paste_masks")
     return out.view(torch.bool) if threshold >= 0 else out
 
 
@@ -141,7 +135,7 @@ def resize_bilinear(x, out_hw, crop_hw=None, scale_factor=None):
         sw = float(torch.tensor(cw, dtype=torch.float32) / torch.tensor(ow, dtype=torch.float32)) if ow > 0 else 0.0
     y = torch.empty((N, Cc, oh, ow), dtype=torch.float32, device=x.device)
     L.check(L.lib().jtsm_resize_bilinear_f32(L.ptr(x), L.NHWC if nhwc else L.NCHW, N, Cc, H, W, ch, cw, oh, ow,
-                                             L.f32(sh), L.f32(sw), L.ptr(y), L.stream()), "resize_bilinear")
+                                             sh, sw, L.ptr(y), L.stream()), "resize_bilinear")
     return y
 
 
@@ -152,7 +146,7 @@ def argmax_channels(x):
     x = x.contiguous()
     Cc, H, W = x.shape
     out = torch.empty((H, W), dtype=torch.int64, device=x.device)
-    L.check(L.lib().jtsm_argmax_channels_f32(L.ptr(x), Cc, C.c_long(H * W), L.ptr(out), L.stream()), "argmax_channels")
+    L.check(L.lib().jtsm_argmax_channels_f32(L.ptr(x), Cc, H * W, L.ptr(out), L.stream()), "argmax_channels")
     return out
 
 
@@ -182,13 +176,12 @@ def panoptic_combine(masks, scores, classes, sem, num_sem_classes, overlap_thres
         # count up front (one small read; this function ends with a read anyway) saves the rest
         visits = int((scores >= float(instances_confidence_threshold)).sum().item())
     lib = L.lib()
-    ws = _ws(_sizet(lib.jtsm_panoptic_combine_workspace_bytes, N, S), dev)
+    ws = _ws(lib.jtsm_panoptic_combine_workspace_bytes(N, S), dev)
     L.check(lib.jtsm_panoptic_combine(L.ptr(masks) if N else None, L.ptr(order), L.ptr(scores) if N else None,
-                                      L.ptr(classes) if N else None, N, H, W, L.ptr(sem), S,
-                                      C.c_double(float(overlap_threshold)), int(stuff_area_limit),
-                                      L.f32(instances_confidence_threshold), L.ptr(pan), L.ptr(table), L.ptr(tscore),
-                                      L.ptr(nseg), visits if N else -1, L.ptr(ws), C.c_size_t(ws.numel()), L.stream()),
-            "panoptic_combine")
+                                      L.ptr(classes) if N else None, N, H, W, L.ptr(sem), S, overlap_threshold,
+                                      int(stuff_area_limit), instances_confidence_threshold, L.ptr(pan), L.ptr(table),
+                                      L.ptr(tscore), L.ptr(nseg), visits if N else -1, L.ptr(ws), ws.numel(),
+                                      L.stream()), "panoptic_combine")
     n = int(nseg.item())
     return pan, table[:n], tscore[:n]
 
@@ -214,7 +207,7 @@ def preprocess_images_u8(images, mean, std, size_divisibility=0, pad_value=0.0):
     ws = (C.c_int32 * B)(*[s[1] for s in sizes])
     m = (C.c_float * Cc)(*[float(v) for v in mean])
     sd = (C.c_float * Cc)(*[float(v) for v in std])
-    L.check(entry(_ptr_array(images), hs, ws, B, Cc, m, sd, L.f32(pad_value), hp, wp, L.ptr(out), L.stream()),
+    L.check(entry(_ptr_array(images), hs, ws, B, Cc, m, sd, pad_value, hp, wp, L.ptr(out), L.stream()),
             "preprocess_images")
     return out, sizes
 

@@ -13,7 +13,7 @@ from torch.nn.modules.utils import _pair
 
 from .. import _lib as L
 
-_SFX = {torch.float32: ("_f32", L.f32), torch.float64: ("_f64", L.f64), torch.float16: ("_f16", L.f32)}
+_SFX = {torch.float32: "_f32", torch.float64: "_f64", torch.float16: "_f16"}
 
 
 def _dtype_entry(t, opname):
@@ -42,7 +42,7 @@ def pooled_forward(kind, input, rois, out_hw, spatial_scale, sampling_ratio, ali
     if input.dtype != rois.dtype:
         raise RuntimeError("expected input and rois to have the same dtype, got %s and %s"
                            % (input.dtype, rois.dtype))
-    sfx, real = _dtype_entry(input, kind + "_forward")
+    sfx = _dtype_entry(input, kind + "_forward")
     x, layout = _as_layout(input)
     rois = rois.contiguous()
     B, Cc, H, W = x.shape
@@ -51,17 +51,14 @@ def pooled_forward(kind, input, rois, out_hw, spatial_scale, sampling_ratio, ali
     if out.numel() == 0:
         return out
     fn = getattr(L.lib(), "jtsm_%s_forward%s" % (kind, sfx))
-    args = [L.ptr(x), L.ptr(rois), L.ptr(out), B, Cc, H, W, M, real(spatial_scale), out_hw[0],
-            out_hw[1], int(sampling_ratio)]
+    args = [L.ptr(x), L.ptr(rois), L.ptr(out), B, Cc, H, W, M, spatial_scale, out_hw[0], out_hw[1],
+            int(sampling_ratio)]
     if kind == "roi_align":
         args.append(int(bool(aligned)))
     if sfx == "_f16":
-        import ctypes as C
-        L.lib().jtsm_pool_f16_workspace_bytes.restype = C.c_size_t
-        nb = L.lib().jtsm_pool_f16_workspace_bytes(C.c_long(x.numel()), C.c_long(rois.numel()), C.c_long(out.numel()),
-                                                   C.c_size_t(0))
+        nb = L.lib().jtsm_pool_f16_workspace_bytes(x.numel(), rois.numel(), out.numel(), 0)
         ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
-        L.check(fn(*args, layout, L.ptr(ws), C.c_size_t(nb), L.stream()), kind + "_forward")
+        L.check(fn(*args, layout, L.ptr(ws), nb, L.stream()), kind + "_forward")
         return out
     L.check(fn(*args, layout, L.stream()), kind + "_forward")
     return out
@@ -69,7 +66,7 @@ def pooled_forward(kind, input, rois, out_hw, spatial_scale, sampling_ratio, ali
 
 def pooled_backward(kind, grad, rois, out_hw, spatial_scale, sampling_ratio, aligned, in_shape):
     L.require_gpu(grad, rois)
-    sfx, real = _dtype_entry(grad, kind + "_backward")
+    sfx = _dtype_entry(grad, kind + "_backward")
     B, Cc, H, W = in_shape
     g, layout = _as_layout(grad)
     gin = _empty_like_layout((B, Cc, H, W), g, layout)
@@ -77,17 +74,14 @@ def pooled_backward(kind, grad, rois, out_hw, spatial_scale, sampling_ratio, ali
         return gin
     rois = rois.contiguous()
     fn = getattr(L.lib(), "jtsm_%s_backward%s" % (kind, sfx))
-    args = [L.ptr(g), L.ptr(rois), L.ptr(gin), B, Cc, H, W, rois.shape[0], real(spatial_scale),
-            out_hw[0], out_hw[1], int(sampling_ratio)]
+    args = [L.ptr(g), L.ptr(rois), L.ptr(gin), B, Cc, H, W, rois.shape[0], spatial_scale, out_hw[0], out_hw[1],
+            int(sampling_ratio)]
     if kind == "roi_align":
         args.append(int(bool(aligned)))
     if sfx == "_f16":
-        import ctypes as C
-        L.lib().jtsm_pool_f16_workspace_bytes.restype = C.c_size_t
-        nb = L.lib().jtsm_pool_f16_workspace_bytes(C.c_long(g.numel()), C.c_long(rois.numel()), C.c_long(gin.numel()),
-                                                   C.c_size_t(0))
+        nb = L.lib().jtsm_pool_f16_workspace_bytes(g.numel(), rois.numel(), gin.numel(), 0)
         ws = torch.empty(nb, dtype=torch.uint8, device=g.device)
-        L.check(fn(*args, layout, L.ptr(ws), C.c_size_t(nb), L.stream()), kind + "_backward")
+        L.check(fn(*args, layout, L.ptr(ws), nb, L.stream()), kind + "_backward")
         return gin
     L.check(fn(*args, layout, L.stream()), kind + "_backward")
     return gin

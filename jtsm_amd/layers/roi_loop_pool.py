@@ -40,7 +40,7 @@ def roi_loop_pool_forward(input, rois, spatial_scale, pooled_h, pooled_w):
     if out.numel():
         L.note_bytes(4.0 * (2 * out.numel() + r.numel()))
         L.check(L.lib().jtsm_roi_loop_pool_forward_f32(
-            L.ptr(x), L.ptr(r), L.ptr(out), L.ptr(arg), B, Cc, H, W, R, L.f32(spatial_scale), pooled_h, pooled_w,
+            L.ptr(x), L.ptr(r), L.ptr(out), L.ptr(arg), B, Cc, H, W, R, spatial_scale, pooled_h, pooled_w,
             layout, L.stream()), "roi_loop_pool_forward")
     if half:
         out = out.half()
@@ -63,7 +63,7 @@ def roi_loop_pool_backward(grad, rois, argmax, spatial_scale, pooled_h, pooled_w
                          device=g.device)
         L.note_bytes(4.0 * (2 * g.numel() + gin.numel()))
         L.check(lib.jtsm_roi_loop_pool_backward_f32(
-            L.ptr(g), L.ptr(r), L.ptr(a), L.ptr(gin), L.ptr(ws), B, Cc, H, W, r.shape[0], L.f32(spatial_scale),
+            L.ptr(g), L.ptr(r), L.ptr(a), L.ptr(gin), L.ptr(ws), B, Cc, H, W, r.shape[0], spatial_scale,
             pooled_h, pooled_w, L.stream()), "roi_loop_pool_backward")
     if nchw:
         gin = gin.contiguous()

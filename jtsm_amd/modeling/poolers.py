@@ -81,11 +81,11 @@ class _AlignLevels(Function):
             L.note_bytes(4.0 * (out.numel() / len(feats) + f.numel() + rois.numel()))
             if rotated:
                 L.check(L.lib().jtsm_roi_align_rotated_forward_level_f32(
-                    L.ptr(f), L.ptr(rois), L.ptr(roi_level), lvl, L.ptr(out), B, C, H, W, M, L.f32(sc), res, res,
+                    L.ptr(f), L.ptr(rois), L.ptr(roi_level), lvl, L.ptr(out), B, C, H, W, M, sc, res, res,
                     sampling_ratio, L.stream()), "roi_align_rotated_forward_level")
                 continue
             L.check(L.lib().jtsm_roi_align_forward_level_f32(
-                L.ptr(f), L.ptr(rois), L.ptr(roi_level), lvl, L.ptr(out), B, C, H, W, M, L.f32(sc), res, res,
+                L.ptr(f), L.ptr(rois), L.ptr(roi_level), lvl, L.ptr(out), B, C, H, W, M, sc, res, res,
                 sampling_ratio, int(aligned), L.stream()), "roi_align_forward_level")
         ctx.save_for_backward(rois, roi_level)
         ctx.cfg = (res, sampling_ratio, aligned, scales, [tuple(f.shape) for f in feats])
@@ -115,7 +115,7 @@ class _AlignLevels(Function):
                 L.note_bytes(4.0 * (g.numel() / nl + grads[lvl].numel() + rois.numel()))
                 L.check(L.lib().jtsm_roi_align_rotated_backward_level_f32(
                     L.ptr(g), L.ptr(rois), L.ptr(roi_level), lvl, L.ptr(grads[lvl]), B, Cc, shapes[lvl][2],
-                    shapes[lvl][3], rois.shape[0], L.f32(scales[lvl]), res, res, sampling_ratio, int(accumulate),
+                    shapes[lvl][3], rois.shape[0], scales[lvl], res, res, sampling_ratio, int(accumulate),
                     L.stream()), "roi_align_rotated_backward_level")
             if accumulate:
                 return (None,) * (7 + nl)
@@ -132,7 +132,7 @@ class _AlignLevels(Function):
                          dtype=torch.uint8, device=g.device)
         L.check(lib.jtsm_roi_align_backward_levels_f32(
             L.ptr(g), L.ptr(rois), L.ptr(roi_level), ptrs, Hs, Ws, sc, nl, B, Cc, rois.shape[0], res, res,
-            sampling_ratio, int(aligned), int(accumulate), L.ptr(ws), C.c_size_t(ws.numel()), L.stream()),
+            sampling_ratio, int(aligned), int(accumulate), L.ptr(ws), ws.numel(), L.stream()),
             "roi_align_backward_levels")
         if accumulate:
             return (None,) * (7 + nl)
@@ -199,7 +199,7 @@ class _MOILevels(Function):
         L.note_bytes(4.0 * (2 * g.numel() + sum(t.numel() for t in grads)))   # gradient + argmax read, maps written
         L.check(lib.jtsm_moi_pool_backward_levels_f32(
             L.ptr(g), L.ptr(rois), L.ptr(roi_level), L.ptr(arg), ptrs, Hs, Ws, sc, nl, B, Cc, rois.shape[0], res, res,
-            int(accumulate), L.ptr(ws), C.c_size_t(ws.numel()), L.stream()), "moi_pool_backward_levels")
+            int(accumulate), L.ptr(ws), ws.numel(), L.stream()), "moi_pool_backward_levels")
         if accumulate:
             return (None,) * (7 + nl)
         grads = [gi if wanted[lvl] else None for lvl, gi in enumerate(grads)]

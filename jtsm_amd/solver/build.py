@@ -2,7 +2,6 @@
 JTSM configs (torch.optim.SGD, per-parameter lr / weight decay: BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS,
 WEIGHT_DECAY_NORM), applied to every parameter in ONE launch of libjtsm_hip.so (csrc/elementwise.hip:
 sgd_multi_kernel) instead of torch's three multi-tensor passes."""
-import ctypes as C
 import struct
 
 import torch
@@ -147,7 +146,7 @@ class SGD(torch.optim.Optimizer):
             ev.record()
             st["copied"][st["turn"]] = ev
             L.note_bytes(20.0 * sum(r[3] for r in rows))   # param, grad, momentum read; param, momentum written
-            L.check(L.lib().jtsm_sgd_momentum_multi_f32(L.ptr(table), len(rows), C.c_long(blocks), 0, L.stream()),
+            L.check(L.lib().jtsm_sgd_momentum_multi_f32(L.ptr(table), len(rows), blocks, 0, L.stream()),
                     "sgd_momentum_multi")
             torch.autograd.graph.increment_version(touched)   # updated behind autograd's back: say so
 

@@ -1,5 +1,7 @@
-"""CPU suite: the C-ABI library loads here (no GPU) and exports every symbol the header declares;
+"""CPU suite: the C-ABI library loads here (no GPU), exports every symbol the header declares and is typed from it;
 the product never reaches into oracle/."""
+import ast
+import ctypes as C
 import os
 import re
 
@@ -9,14 +11,9 @@ from conftest import ROOT
 
 
 def _declared():
-    names = set()
-    inc = os.path.join(ROOT, "include")
-    for f in os.listdir(inc):
-        if f.endswith(".h"):
-            txt = open(os.path.join(inc, f)).read()
-            txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-            names |= set(re.findall(r"\b(jtsm_[a-z0-9_]+)\s*\(", txt))
-    return sorted(names)
+    from jtsm_amd import _lib
+
+    return sorted(_lib.declarations())
 
 
 def test_library_loads_and_exports_all_declared_symbols():
@@ -71,12 +68,10 @@ def test_product_never_imports_the_oracle():
 def test_conv_planning_host_logic_handles_empty_and_odd_shapes():
     """jtsm_conv_workspace_bytes / jtsm_conv_plan are pure host code: an empty batch (a rank with no
     foreground roi) must plan to 'nothing', not divide by zero; a real layer plans a sane tile / split."""
-    import ctypes as C
     from jtsm_amd import _lib
     from jtsm_amd.layers.conv import ConvShape
 
     lib = _lib.lib()
-    lib.jtsm_conv_workspace_bytes.restype = C.c_size_t
     for kh, stride, pad in ((1, 1, 0), (3, 1, 1), (1, 2, 0), (2, 2, 0)):
         s = ConvShape(0, 14, 14, 256, 256, kh, kh, stride, pad, 1)
         for bwd in (0, 1):
@@ -100,7 +95,6 @@ def test_bf16x3_plan_reports_the_ring_for_long_k_64_tiles():
     """jtsm_conv_bf16x3_plan (host code): the res4 / res5 1x1 layers that run on 64 x 64 tiles take the four-stage
     ring (NBUF = 4) from four stages per K slice; the GPU conv cases `ring_*` in tests/test_hip_conv.py are such
     shapes; large layers stay double-buffered on 256 x 256 tiles."""
-    import ctypes as C
     from jtsm_amd import _lib
     from jtsm_amd.layers.conv import ConvShape
 
@@ -148,3 +142,105 @@ def test_integration_doc_maps_every_declared_symbol():
     missing = [n for n in _declared()
                if n not in have and not any("*" in w and re.fullmatch(w.replace("*", ".*"), n) for w in have)]
     assert not missing, missing
+
+
+def test_every_declared_function_is_typed_from_the_header():
+    """lib() gives every entry point one argtype per declared parameter and the mapped return type: size_t for the
+    workspace sizes, int return codes for the rest but a handful of declared exceptions."""
+    from jtsm_amd import _lib
+
+    lib = _lib.lib()
+    txt = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER).read(), flags=re.S)
+    params = dict(re.findall(r"\b(jtsm_[a-z0-9_]+)\s*\(([^()]*)\)", txt))
+    assert sorted(params) == _declared()
+    special = {"jtsm_last_error": C.c_char_p, "jtsm_version": C.c_char_p, "jtsm_event_create": C.c_void_p,
+               "jtsm_event_destroy": None, "jtsm_conv_set_mid_event": None, "jtsm_conv_set_splitk_fused": None}
+    for name, plist in params.items():
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == (0 if plist.strip() == "void" else plist.count(",") + 1), name
+        want = special.get(name, C.c_size_t if name.endswith("_workspace_bytes") else C.c_int)
+        assert fn.restype is want, (name, fn.restype)
+    assert lib.jtsm_dropout_split_f32.argtypes[4:7] == [C.c_long, C.c_float, C.c_ulonglong]
+
+
+def test_size_arguments_and_results_keep_64_bits():
+    """jtsm_pool_f16_workspace_bytes is host arithmetic on long element counts: an untyped call would pass and
+    return them as 32-bit ints."""
+    from jtsm_amd import _lib
+
+    assert _lib.lib().jtsm_pool_f16_workspace_bytes(3 << 31, 0, 0, 0) >= 12 << 31
+
+
+def test_declarations_reject_unmapped_types(tmp_path):
+    from jtsm_amd import _lib
+
+    h = tmp_path / "h.h"
+    h.write_text("int jtsm_ok(const float* x, unsigned long long n, void* stream);\nint jtsm_bad(bool flag);\n")
+    with pytest.raises(ValueError, match="jtsm_bad"):
+        _lib.declarations(str(h))
+    h.write_text("/* jtsm_comment(int a); */\n#define JTSM_X(a) jtsm_macro(a)\nint jtsm_ok(const float* x, "
+                 "unsigned long long n, void* stream);\nvoid jtsm_none(void);\n")
+    assert _lib.declarations(str(h)) == {"jtsm_ok": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_void_p]),
+                                         "jtsm_none": (None, [])}
+
+
+def test_a_declared_symbol_missing_from_the_library_fails_at_load(monkeypatch):
+    from jtsm_amd import _lib
+
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "declarations", lambda: {"jtsm_not_exported": (C.c_int, [])})
+    with pytest.raises(RuntimeError, match="jtsm_not_exported"):
+        _lib.lib()
+
+
+# Calls whose entry point is picked at run time, out of the scan's sight: roi_align.py builds the name from the op and
+# dtype for getattr; postprocess.py picks the u8 or f32 image preprocessing.
+_PICKED_AT_RUN_TIME = {"jtsm_amd/layers/roi_align.py", "jtsm_amd/layers/postprocess.py"}
+# Called by tools/sweeps/sem_side_*.py; exported only by a JTSM_DIAG_UP2 build of the library, not declared.
+_UNDECLARED = {"jtsm_diag_up2_read"}
+
+
+def _python_sources():
+    paths = [os.path.join(ROOT, "__graft_entry__.py")]
+    for top in ("jtsm_amd", "tests", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, top)):
+            paths += [os.path.join(dirpath, f) for f in files if f.endswith(".py")]
+    return sorted(paths)
+
+
+def test_library_calls_pass_the_declared_number_of_arguments():
+    """Every `<expr>.jtsm_name(...)` call without *args in the tree passes exactly the header's parameter count: a
+    typed ctypes function refuses too few arguments but silently accepts too many."""
+    from jtsm_amd import _lib
+
+    decl = _lib.declarations()
+    bad, undeclared, picked = [], set(), set()
+    for path in _python_sources():
+        rel = os.path.relpath(path, ROOT)
+        tree = ast.parse(open(path).read(), path)
+        seen = set()    # attributes that are called or read further (`fn.argtypes`)
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute):
+                seen.add(id(node.func))
+            if isinstance(node, ast.Attribute):
+                seen.add(id(node.value))
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Attribute) and node.attr.startswith("jtsm_") and id(node) not in seen:
+                picked.add(rel)
+            if not isinstance(node, ast.Call):
+                continue
+            f = node.func
+            if isinstance(f, ast.Name) and f.id == "getattr" and len(node.args) > 1 and any(
+                    isinstance(c, ast.Constant) and str(c.value).startswith("jtsm_") for c in ast.walk(node.args[1])):
+                picked.add(rel)
+            if not (isinstance(f, ast.Attribute) and f.attr.startswith("jtsm_")) or \
+                    any(isinstance(a, ast.Starred) for a in node.args):
+                continue
+            n = len(node.args) + len(node.keywords)
+            if f.attr not in decl:
+                undeclared.add(f.attr)
+            elif n != len(decl[f.attr][1]):
+                bad.append("%s:%d %s: %d arguments, declared %d" % (rel, node.lineno, f.attr, n, len(decl[f.attr][1])))
+    assert not bad, bad
+    assert undeclared <= _UNDECLARED, undeclared
+    assert picked == _PICKED_AT_RUN_TIME, picked

@@ -125,7 +125,7 @@ def test_sample_tables_bit_exact(cuda, rotated):
     pos = torch.empty(M, cap, 4, dtype=torch.int32, device=cuda)
     w = torch.empty(M, cap, 4, dtype=torch.float32, device=cuda)
     rd = dev(r, cuda)  # keep alive: a temporary would hand its block back to the allocator
-    L.check(L.lib().jtsm_roi_sample_table_f32(L.ptr(rd), int(rotated), M, H, W, L.f32(scale), PH,
+    L.check(L.lib().jtsm_roi_sample_table_f32(L.ptr(rd), int(rotated), M, H, W, scale, PH,
                                               PW, 0, 1, L.ptr(grid), L.ptr(pos), L.ptr(w), cap, L.stream()))
     grid, pos, w = grid.cpu().numpy(), pos.cpu().numpy(), w.cpu().numpy()
     checked = 0
@@ -218,7 +218,7 @@ def test_moi_mask_bit_exact(cuda):
     ws = torch.empty(L.lib().jtsm_moi_pool_workspace_bytes(B, H, W, M, Lw), dtype=torch.uint8, device=cuda)
     rd, ohd, spd = dev(c["rois"], cuda), dev(c["oh"], cuda), dev(c["sp"], cuda)  # keep alive
     L.check(L.lib().jtsm_moi_mask_f32(L.ptr(rd), L.ptr(ohd), L.ptr(spd), L.ptr(mois), L.ptr(ws), B, H, W, M,
-                                      Lw, Hs, Ws, L.f32(0.25), L.stream()))
+                                      Lw, Hs, Ws, 0.25, L.stream()))
     assert np.array_equal(mois.cpu().numpy(), P.moi_mask(c["rois"], c["oh"], c["sp"], H, W, 0.25))
 
 
@@ -448,7 +448,7 @@ def test_multilevel_moi_pool_backward_gather_matches_oracle_and_scatter(cuda):
     ptrs = (C.c_void_p * nl)(*[t.data_ptr() for t in grads])
     gcl, acl = gd.contiguous(memory_format=torch.channels_last), arg.contiguous(memory_format=torch.channels_last)
     L.check(L.lib().jtsm_moi_pool_backward_levels_f32(L.ptr(gcl), L.ptr(rois), L.ptr(lv), L.ptr(acl), ptrs, Hs, Ws, None,
-                                                      nl, B, Cc, rois.shape[0], 7, 7, 0, None, C.c_size_t(0), L.stream()),
+                                                      nl, B, Cc, rois.shape[0], 7, 7, 0, None, 0, L.stream()),
             "scatter form")
     for a, s in zip(xs, grads):
         assert torch.allclose(a.grad, s, rtol=1e-5, atol=1e-5)
