@@ -528,6 +528,111 @@ def _check(*ts):
             raise RuntimeError("jtsm_amd conv kernels are float32, got %s" % t.dtype)
 
 
+# ---- one launcher per contraction role: operand PLANE BUFFERS in (`_planes_buf`), optional fp32 tensors beside them.
+# Both front ends below (tensors whose planes come from the cache; PlaneTensors) launch through these and nowhere else.
+def _launch_forward(pl, x, w, y, yp, scale=None, bias=None, residual=None, relu=False, residual_plane=None):
+    """relu?(conv(x, w) * scale + bias + residual) -> fp32 `y` and / or planes `yp` (either may be None).
+    residual_plane (fp16 arithmetic only): the residual as an fp16 plane instead of an fp32 tensor."""
+    xh, xl = _hl(x)
+    wh, wl = _hl(w)
+    yh, yl = _hl(yp)
+    relu = int(bool(relu))
+    nbytes = pl.ws[0]
+    ws = _scratch(nbytes, x.device)
+    lib = L.lib()
+    if residual_plane is not None:
+        assert MATH == "f16" and residual is None
+        rh = _hl(residual_plane)[0]
+        name, call = "conv2d_forward_res16_f16", lambda: lib.jtsm_conv2d_forward_res16_f16(
+            xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), rh, relu, L.ptr(ws), nbytes, L.stream())
+    elif MATH == "f16":
+        name, call = "conv2d_forward_f16", lambda: lib.jtsm_conv2d_forward_f16(
+            xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), relu, L.ptr(ws), nbytes,
+            L.stream())
+    else:
+        name, call = "conv2d_forward_bf16x3", lambda: lib.jtsm_conv2d_forward_bf16x3(
+            xh, xl, wh, wl, L.ptr(y), yh, yl, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), relu, L.ptr(ws),
+            nbytes, L.stream())
+    n_out = pl.s.batch * pl.s.out_c * pl.oh * pl.ow
+    extra = _numel(residual) + (0.5 * n_out if residual_plane is not None else 0)    # (an fp16 plane: 2 B per element)
+    L.check(_timed(_x3_variant(pl.s, 0), pl.flops, call, pl.desc, extra, n_out, yp is not None, y is not None), name)
+
+
+def _launch_backward_data(pl, g, wt, dx, dp, accumulate=None, relu_mask=None, row_scale=None, gate=None,
+                          accumulate_plane=None, colsum=None):
+    """Data gradient of the planes `g` against the transposed weight planes `wt` -> fp32 `dx` and / or planes `dp`.
+    accumulate / relu_mask: fp32 tensors of dx's shape added to / gating the result; gate: the same gate read from an
+    activation's planes; accumulate_plane (fp16 arithmetic only): a gradient term as an fp16 plane; colsum: (rows, in_c)
+    buffer that also receives the per-row-tile column sums of the finished result."""
+    gh, gl = _hl(g)
+    wh, wl = _hl(wt)
+    dh, dl = _hl(dp)
+    gate_h = _hl(gate)[0]
+    nbytes = pl.ws[1]
+    ws = _scratch(nbytes, g.device)
+    lib = L.lib()
+    if accumulate_plane is not None:
+        assert MATH == "f16" and accumulate is None and relu_mask is None and colsum is None
+        ah = _hl(accumulate_plane)[0]
+        name, call = "conv2d_backward_data_acc16_f16", lambda: lib.jtsm_conv2d_backward_data_acc16_f16(
+            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), ah, gate_h, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream())
+    elif colsum is not None and MATH == "f16":
+        name, call = "conv2d_backward_data_colsum_f16", lambda: lib.jtsm_conv2d_backward_data_colsum_f16(
+            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), L.ptr(accumulate), L.ptr(relu_mask), gate_h, GRAD_SHIFT,
+            L.ptr(colsum), L.ptr(ws), nbytes, L.stream())
+    elif colsum is not None:
+        name, call = "conv2d_backward_data_colsum_bf16x3", lambda: lib.jtsm_conv2d_backward_data_colsum_bf16x3(
+            gh, gl, wh, wl, L.ptr(dx), dh, dl, pl.ref, L.ptr(row_scale), L.ptr(accumulate), L.ptr(relu_mask), gate_h,
+            L.ptr(colsum), L.ptr(ws), nbytes, L.stream())
+    elif MATH == "f16":     # (jtsm_conv2d_backward_data_* is the _ex_ entry point with row_scale and gate_plane null)
+        name, call = "conv2d_backward_data_ex_f16", lambda: lib.jtsm_conv2d_backward_data_ex_f16(
+            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), L.ptr(accumulate), L.ptr(relu_mask), gate_h, GRAD_SHIFT,
+            L.ptr(ws), nbytes, L.stream())
+    else:
+        name, call = "conv2d_backward_data_ex_bf16x3", lambda: lib.jtsm_conv2d_backward_data_ex_bf16x3(
+            gh, gl, wh, wl, L.ptr(dx), dh, dl, pl.ref, L.ptr(row_scale), L.ptr(accumulate), L.ptr(relu_mask), gate_h,
+            L.ptr(ws), nbytes, L.stream())
+    n_in = pl.s.batch * pl.s.in_c * pl.s.in_h * pl.s.in_w
+    half = (gate is not None) + (accumulate_plane is not None)     # (a gate / fp16 plane: 2 bytes per element)
+    extra = _numel(accumulate) + _numel(relu_mask) + 0.5 * n_in * half
+    L.check(_timed(_x3_variant(pl.s, 1), pl.flops, call, pl.desc, extra, n_in, dp is not None, dx is not None), name)
+
+
+def _launch_backward_weight(pl, g, x, out, row_scale, fresh, bias_out=None):
+    """dW (+)= from the planes of the output gradient `g` and of the input `x` (fresh: written, not accumulated).
+    bias_out (out_c,): also the bias gradient, from the same gradient planes inside the same contraction."""
+    gh, gl = _hl(g)
+    xh, xl = _hl(x)
+    fresh = int(fresh)
+    nbytes = pl.ws[2] if bias_out is None else max(pl.ws[3], pl.ws[2])
+    ws = _scratch(nbytes, x.device)
+    lib = L.lib()
+    if bias_out is not None and MATH == "f16":
+        name, call = "conv2d_backward_weight_bias_f16", lambda: lib.jtsm_conv2d_backward_weight_bias_f16(
+            gh, xh, L.ptr(out), L.ptr(bias_out), pl.ref, L.ptr(row_scale), fresh, GRAD_SHIFT, L.ptr(ws), nbytes,
+            L.stream())
+    elif bias_out is not None:
+        name, call = "conv2d_backward_weight_bias_bf16x3", lambda: lib.jtsm_conv2d_backward_weight_bias_bf16x3(
+            gh, gl, xh, xl, L.ptr(out), L.ptr(bias_out), pl.ref, L.ptr(row_scale), fresh, L.ptr(ws), nbytes, L.stream())
+    elif MATH == "f16":
+        name, call = "conv2d_backward_weight_f16", lambda: lib.jtsm_conv2d_backward_weight_f16(
+            gh, xh, L.ptr(out), pl.ref, L.ptr(row_scale), fresh, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream())
+    else:
+        name, call = "conv2d_backward_weight_bf16x3", lambda: lib.jtsm_conv2d_backward_weight_bf16x3(
+            gh, gl, xh, xl, L.ptr(out), pl.ref, L.ptr(row_scale), fresh, L.ptr(ws), nbytes, L.stream())
+    L.check(_timed(_x3_variant(pl.s, 2), pl.flops, call, pl.desc, 0, out.numel()), name)
+
+
+def _slot_view(w, w_shape):
+    """The parameter's gradient slot (grad_slot) as the OHWI result the kernels write — the parameter is dense and
+    channels_last, so these are the same bytes — or None."""
+    slot = grad_slot(w)
+    if slot is None:
+        return None
+    o, i, kh, kw = w_shape
+    return slot.as_strided(tuple(w_shape), (kh * kw * i, 1, kw * i, i))
+
+
 def conv2d_forward(x, w, stride=1, pad=0, dil=1, scale=None, bias=None, residual=None, relu=False,
                    emit_planes=False):
     _check(x, w, scale, bias, residual)
@@ -538,29 +643,17 @@ def conv2d_forward(x, w, stride=1, pad=0, dil=1, scale=None, bias=None, residual
     if residual is not None:
         residual = _cl(residual)
         assert residual.shape == y.shape
-    nbytes = pl.ws[0]
-    ws = _scratch(nbytes, x.device)
-    lib = L.lib()
     if MATH != "f32" and pl.x3[0]:
-        xh, xl = _hl(planes_of(x))
+        xbuf = planes_of(x)
         wbuf = _weight_planes(w)
-        wh, wl = _hl(wbuf)
         ybuf = _planes_buf(y.numel(), y.device) if (emit_planes and s.out_c % 8 == 0) else None
-        yh, yl = _hl(ybuf)
-        if MATH == "f16":
-            L.check(_timed(_x3_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_f16(
-                xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), int(bool(relu)),
-                L.ptr(ws), nbytes, L.stream()), pl.desc, _numel(residual), y.numel(), ybuf is not None),
-                    "conv2d_forward_f16")
-        else:
-            L.check(_timed(_x3_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_bf16x3(
-                xh, xl, wh, wl, L.ptr(y), yh, yl, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), int(bool(relu)),
-                L.ptr(ws), nbytes, L.stream()), pl.desc, _numel(residual), y.numel(), ybuf is not None),
-                    "conv2d_forward_bf16x3")
+        _launch_forward(pl, xbuf, wbuf, y, ybuf, scale, bias, residual, relu)
         if ybuf is not None:
             planes_put(y, ybuf)
         return y
-    L.check(_timed(_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_f32(
+    nbytes = pl.ws[0]
+    ws = _scratch(nbytes, x.device)
+    L.check(_timed(_variant(s, 0), pl.flops, lambda: L.lib().jtsm_conv2d_forward_f32(
         L.ptr(x), L.ptr(w), L.ptr(y), pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), int(bool(relu)),
         L.ptr(ws), nbytes, L.stream()), pl.desc, _numel(residual), y.numel()), "conv2d_forward")
     return y
@@ -584,31 +677,19 @@ def conv2d_backward_data(dy, w, x_shape, stride=1, pad=0, dil=1, kscale=None, ac
         accumulate = _cl(accumulate)
     if relu_mask is not None:
         relu_mask = _cl(relu_mask)
-    nbytes = pl.ws[1]
-    ws = _scratch(nbytes, dy.device)
-    lib = L.lib()
     if MATH != "f32" and pl.x3[1]:
-        gh, gl = _hl(planes_of(dy, grad=True))
+        gbuf = planes_of(dy, grad=True)
         wbuf = _weight_planes(w, True, kscale)   # the per-row scale rides along in the transposing split
-        wh, wl = _hl(wbuf)
         scatter = s.kernel_h == 1 and s.kernel_w == 1 and s.pad == 0 and s.stride > 1 and \
             (accumulate is None or into is not None) and relu_mask is None
         dbuf = _planes_buf(dx.numel(), dx.device) if (emit_planes and s.in_c % 8 == 0 and not scatter) else None
-        dh, dl = _hl(dbuf)
-        if MATH == "f16":
-            L.check(_timed(_x3_variant(s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_f16(
-                gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(accumulate), L.ptr(relu_mask), GRAD_SHIFT, L.ptr(ws),
-                nbytes, L.stream()), pl.desc, _numel(accumulate) + _numel(relu_mask), dx.numel(),
-                    dbuf is not None), "conv2d_backward_data_f16")
-        else:
-            L.check(_timed(_x3_variant(s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_bf16x3(
-                gh, gl, wh, wl, L.ptr(dx), dh, dl, pl.ref, L.ptr(accumulate), L.ptr(relu_mask), L.ptr(ws),
-                nbytes, L.stream()), pl.desc, _numel(accumulate) + _numel(relu_mask), dx.numel(),
-                    dbuf is not None), "conv2d_backward_data_bf16x3")
+        _launch_backward_data(pl, gbuf, wbuf, dx, dbuf, accumulate, relu_mask)
         if dbuf is not None:
             planes_put(dx, dbuf)
         return dx
-    L.check(_timed(_variant(s, 1, kscale is not None), pl.flops, lambda: lib.jtsm_conv2d_backward_data_f32(
+    nbytes = pl.ws[1]
+    ws = _scratch(nbytes, dy.device)
+    L.check(_timed(_variant(s, 1, kscale is not None), pl.flops, lambda: L.lib().jtsm_conv2d_backward_data_f32(
         L.ptr(dy), L.ptr(w), L.ptr(dx), pl.ref, L.ptr(kscale), L.ptr(accumulate), L.ptr(relu_mask),
         L.ptr(ws), nbytes, L.stream()), pl.desc, _numel(accumulate) + _numel(relu_mask), dx.numel()),
             "conv2d_backward_data")
@@ -620,48 +701,30 @@ def conv2d_backward_weight(dy, x, w_shape, stride=1, pad=0, dil=1, row_scale=Non
     has registered a gradient slot for it, the result is written there (a fresh result, not an accumulation).
     `bias_out` (out_c,): also the bias gradient sum_pixels dy — inside the same contraction in the plane arithmetics
     (no second pass over dy), by a channel_sum pass otherwise."""
+    from .elementwise import channel_sum
     _check(dy, x, row_scale)
     dy, x = _cl(dy), _cl(x)
     pl = _plan(x.shape, w_shape, stride, pad, dil)
-    s = pl.s
-    lib = L.lib()
-    slot = grad_slot(w) if out is None else None
-    if slot is not None:   # same bytes as the OHWI result the kernels write (the parameter is dense, channels_last)
-        n, taps = w_shape[0], w_shape[2] * w_shape[3]
-        slot = slot.as_strided(tuple(w_shape), (taps * w_shape[1], 1, w_shape[3] * w_shape[1], w_shape[1]))
+    slot = _slot_view(w, w_shape) if out is None else None
     if MATH != "f32" and pl.x3[2]:
-        gh, gl = _hl(planes_of(dy, grad=True))
-        xh, xl = _hl(planes_of(x))
+        gbuf = planes_of(dy, grad=True)
+        xbuf = planes_of(x)
         fresh = out is None
         if fresh:   # deterministic slab kernel: writes every element, nothing to clear
             out = slot if slot is not None else torch.empty(tuple(w_shape), dtype=x.dtype, device=x.device,
                                                             memory_format=CL)
-        if bias_out is not None and BIAS_IN_WGRAD and _wgrad_bias_fits(pl):
-            _wgrad_bias_call(pl, gh, gl, xh, xl, out, bias_out, row_scale, fresh, x.device)
-            return out
-        if bias_out is not None:
-            from .elementwise import channel_sum
+        if bias_out is not None and not (BIAS_IN_WGRAD and _wgrad_bias_fits(pl)):
             bias_out.copy_(channel_sum(dy))
-        nbytes = pl.ws[2]
-        ws = _scratch(nbytes, x.device)
-        if MATH == "f16":
-            L.check(_timed(_x3_variant(s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_f16(
-                gh, xh, L.ptr(out), pl.ref, L.ptr(row_scale), int(fresh), GRAD_SHIFT, L.ptr(ws), nbytes,
-                L.stream()), pl.desc, 0, out.numel()), "conv2d_backward_weight_f16")
-        else:
-            L.check(_timed(_x3_variant(s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_bf16x3(
-                gh, gl, xh, xl, L.ptr(out), pl.ref, L.ptr(row_scale), int(fresh), L.ptr(ws), nbytes,
-                L.stream()), pl.desc, 0, out.numel()), "conv2d_backward_weight_bf16x3")
+            bias_out = None
+        _launch_backward_weight(pl, gbuf, xbuf, out, row_scale, fresh, bias_out)
         return out
     if bias_out is not None:
-        from .elementwise import channel_sum
         bias_out.copy_(channel_sum(dy))
-    zero = False   # cleared here (not inside the timed launch) so per-launch timings are kernel-only
-    if out is None:
+    if out is None:   # cleared here (not inside the timed launch) so per-launch timings are kernel-only
         out = slot.zero_() if slot is not None else \
             torch.empty(tuple(w_shape), dtype=x.dtype, device=x.device, memory_format=CL).zero_()
-    L.check(_timed(_variant(s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_f32(
-        L.ptr(dy), L.ptr(x), L.ptr(out), pl.ref, L.ptr(row_scale), int(zero), L.stream()), pl.desc),
+    L.check(_timed(_variant(pl.s, 2), pl.flops, lambda: L.lib().jtsm_conv2d_backward_weight_f32(
+        L.ptr(dy), L.ptr(x), L.ptr(out), pl.ref, L.ptr(row_scale), 0, L.stream()), pl.desc),
             "conv2d_backward_weight")
     return out
 
@@ -678,65 +741,92 @@ def _ct_desc(n, h, w, i, o):
     return (n, h, w, i, 4 * o, 1, 1, 4.0 * elems)
 
 
-def conv_transpose2x2_forward(x, w, bias=None, relu=False, emit_planes=False):
-    """y (N, out, 2H, 2W) channels_last = relu?(conv_transpose2d(x, w, stride 2) + bias): one GEMM of (N*H*W) x
-    (4*out) whose epilogue writes each row's four column groups to the four output pixels."""
-    _check(x, w, bias)
-    x = _cl(x)
-    n, i, h, wd = x.shape
+def _launch_ct_forward(x, x_shape, w, y, yp, bias, relu):
+    """Transposed 2x2 forward from the planes `x` of a (N, in, H, W) input -> fp32 `y` and / or planes `yp`: one GEMM
+    of (N*H*W) x (4*out) whose epilogue writes each row's four column groups to the four output pixels."""
+    n, i, h, wd = x_shape
     o = w.shape[1]
-    y = torch.empty((n, o, 2 * h, 2 * wd), dtype=x.dtype, device=x.device, memory_format=CL)
-    xh, xl = _hl(planes_of(x))
+    xh, xl = _hl(x)
     w1 = w.as_strided((i, 4 * o, 1, 1), (4 * o, 1, 1, 1))       # the same memory as a 1x1 weight: [in][(dy,dx,out)]
     wth, wtl = _hl(_weight_planes(w1, True))
-    ybuf = _planes_buf(y.numel(), y.device) if emit_planes else None
-    yh, yl = _hl(ybuf)
+    yh, yl = _hl(yp)
+    relu = int(bool(relu))
     lib = L.lib()
-    flops = 2.0 * n * h * wd * i * 4 * o
     var = _x3_variant(_plan((n, i, h, wd), (4 * o, i, 1, 1), 1, 0, 1).s, 0)
     var = _Variant(str(var), 1) if var is not None else None      # (the pixel-shuffle epilogue never splits K)
     if MATH == "f16":
-        L.check(_timed(var, flops, lambda: lib.jtsm_conv_transpose2x2_forward_f16(
-            xh, wth, L.ptr(y), yh, n, h, wd, i, o, L.ptr(bias), int(bool(relu)), L.stream()),
-            _ct_desc(n, h, wd, i, o), 0, y.numel(), ybuf is not None), "conv_transpose2x2_forward_f16")
+        name, call = "conv_transpose2x2_forward_f16", lambda: lib.jtsm_conv_transpose2x2_forward_f16(
+            xh, wth, L.ptr(y), yh, n, h, wd, i, o, L.ptr(bias), relu, L.stream())
     else:
-        L.check(_timed(var, flops, lambda: lib.jtsm_conv_transpose2x2_forward_bf16x3(
-            xh, xl, wth, wtl, L.ptr(y), yh, yl, n, h, wd, i, o, L.ptr(bias), int(bool(relu)), L.stream()),
-            _ct_desc(n, h, wd, i, o), 0, y.numel(), ybuf is not None), "conv_transpose2x2_forward_bf16x3")
+        name, call = "conv_transpose2x2_forward_bf16x3", lambda: lib.jtsm_conv_transpose2x2_forward_bf16x3(
+            xh, xl, wth, wtl, L.ptr(y), yh, yl, n, h, wd, i, o, L.ptr(bias), relu, L.stream())
+    L.check(_timed(var, 2.0 * n * h * wd * i * 4 * o, call, _ct_desc(n, h, wd, i, o), 0, 4 * n * o * h * wd,
+                   yp is not None, y is not None), name)
+
+
+def _launch_ct_backward_data(pl, g, w, dx, dp, relu_mask=None, gate=None, colsum=None):
+    """Transposed 2x2 data gradient -> fp32 `dx` and / or planes `dp`: the forward role of the 2x2 / stride-2
+    convolution `pl` whose OHWI weight (planes `w`) is the parameter's memory.  relu_mask / gate / colsum: see
+    _launch_backward_data."""
+    s = pl.s
+    n, o, i, h, wd = s.batch, s.in_c, s.out_c, pl.oh, pl.ow
+    gh, gl = _hl(g)
+    wh, wl = _hl(w)
+    dh, dl = _hl(dp)
+    gate_h = _hl(gate)[0]
+    nbytes = pl.ws[0]
+    ws = _scratch(nbytes, g.device)
+    lib = L.lib()
+    if colsum is not None and MATH == "f16":
+        name = "conv_transpose2x2_backward_data_colsum_f16"
+        call = lambda: lib.jtsm_conv_transpose2x2_backward_data_colsum_f16(      # noqa: E731
+            gh, wh, L.ptr(dx), dh, n, h, wd, i, o, L.ptr(relu_mask), gate_h, GRAD_SHIFT, L.ptr(colsum), L.ptr(ws),
+            nbytes, L.stream())
+    elif colsum is not None:
+        name = "conv_transpose2x2_backward_data_colsum_bf16x3"
+        call = lambda: lib.jtsm_conv_transpose2x2_backward_data_colsum_bf16x3(   # noqa: E731
+            gh, gl, wh, wl, L.ptr(dx), dh, dl, n, h, wd, i, o, L.ptr(relu_mask), gate_h, L.ptr(colsum), L.ptr(ws),
+            nbytes, L.stream())
+    elif MATH == "f16":
+        name, call = "conv_transpose2x2_backward_data_f16", lambda: lib.jtsm_conv_transpose2x2_backward_data_f16(
+            gh, wh, L.ptr(dx), dh, n, h, wd, i, o, L.ptr(relu_mask), gate_h, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream())
+    else:
+        name, call = "conv_transpose2x2_backward_data_bf16x3", lambda: lib.jtsm_conv_transpose2x2_backward_data_bf16x3(
+            gh, gl, wh, wl, L.ptr(dx), dh, dl, n, h, wd, i, o, L.ptr(relu_mask), gate_h, L.ptr(ws), nbytes, L.stream())
+    n_dx = n * i * h * wd
+    extra = _numel(relu_mask) + 0.5 * n_dx * (gate is not None)     # (the gate plane: 2 bytes per element)
+    L.check(_timed(_x3_variant(s, 0), pl.flops, call, pl.desc, extra, n_dx, dp is not None, dx is not None), name)
+
+
+def conv_transpose2x2_forward(x, w, bias=None, relu=False, emit_planes=False):
+    """y (N, out, 2H, 2W) channels_last = relu?(conv_transpose2d(x, w, stride 2) + bias)."""
+    _check(x, w, bias)
+    x = _cl(x)
+    n, i, h, wd = x.shape
+    y = torch.empty((n, w.shape[1], 2 * h, 2 * wd), dtype=x.dtype, device=x.device, memory_format=CL)
+    xbuf = planes_of(x)
+    ybuf = _planes_buf(y.numel(), y.device) if emit_planes else None
+    _launch_ct_forward(xbuf, x.shape, w, y, ybuf, bias, relu)
     if ybuf is not None:
         planes_put(y, ybuf)
     return y
 
 
 def conv_transpose2x2_backward_data(g, w, relu_mask=None, emit_planes=False):
-    """dx (N, in, H, W) of conv_transpose2x2_forward, kept where relu_mask > 0: the forward role of the 2x2 / stride-2
-    convolution whose OHWI weight is the parameter's memory."""
+    """dx (N, in, H, W) of conv_transpose2x2_forward, kept where relu_mask > 0."""
     _check(g, w, relu_mask)
     g = _cl(g)
     n, o, h2, w2 = g.shape
     i = w.shape[0]
-    h, wd = h2 // 2, w2 // 2
     pl = _plan(g.shape, (i, o, 2, 2), 2, 0, 1)
-    dx = torch.empty((n, i, h, wd), dtype=g.dtype, device=g.device, memory_format=CL)
+    dx = torch.empty((n, i, h2 // 2, w2 // 2), dtype=g.dtype, device=g.device, memory_format=CL)
     if relu_mask is not None:
         relu_mask = _cl(relu_mask)
         assert relu_mask.shape == dx.shape
-    gh, gl = _hl(planes_of(g, grad=True))
-    wh, wl = _hl(_weight_planes(w))
+    gbuf = planes_of(g, grad=True)
+    wbuf = _weight_planes(w)
     dbuf = _planes_buf(dx.numel(), dx.device) if emit_planes else None
-    dh, dl = _hl(dbuf)
-    nbytes = pl.ws[0]
-    ws = _scratch(nbytes, g.device)
-    lib = L.lib()
-    if MATH == "f16":
-        L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_f16(
-            gh, wh, L.ptr(dx), dh, n, h, wd, i, o, L.ptr(relu_mask), None, GRAD_SHIFT, L.ptr(ws), nbytes,
-            L.stream()), pl.desc, _numel(relu_mask), dx.numel(), dbuf is not None), "conv_transpose2x2_backward_data_f16")
-    else:
-        L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_bf16x3(
-            gh, gl, wh, wl, L.ptr(dx), dh, dl, n, h, wd, i, o, L.ptr(relu_mask), None, L.ptr(ws), nbytes,
-            L.stream()), pl.desc, _numel(relu_mask), dx.numel(), dbuf is not None),
-                "conv_transpose2x2_backward_data_bf16x3")
+    _launch_ct_backward_data(pl, gbuf, wbuf, dx, dbuf, relu_mask)
     if dbuf is not None:
         planes_put(dx, dbuf)
     return dx
@@ -784,6 +874,10 @@ class PlaneTensor(object):
         return PlaneTensor(_planes_buf(n, device), shape)
 
 
+def _buf(p):
+    return None if p is None else p.buf
+
+
 def planes_forward(x, w, stride=1, pad=0, dil=1, bias=None, relu=False, fp32=False, scale=None, residual=None,
                    residual_plane=None):
     """x: PlaneTensor -> PlaneTensor of relu?(conv(x, w) + bias) (fp32=False: planes only, no fp32 copy is written), or
@@ -797,32 +891,12 @@ def planes_forward(x, w, stride=1, pad=0, dil=1, bias=None, relu=False, fp32=Fal
     both = fp32 == "both"            # -> (y fp32, PlaneTensor)
     y = torch.empty(oshape, dtype=torch.float32, device=x.device, memory_format=CL) if fp32 else None
     yp = PlaneTensor.empty(oshape, x.device) if (both or not fp32) else None
-    xh, xl = _hl(x.buf)
-    wh, wl = _hl(_weight_planes(_cl(w)))
-    yh, yl = _hl(yp.buf if yp is not None else None)
-    nbytes = pl.ws[0]
-    ws = _scratch(nbytes, x.device)
-    lib = L.lib()
-    n_out = s.batch * s.out_c * pl.oh * pl.ow
+    wbuf = _weight_planes(_cl(w))
     if residual is not None:
         residual = _cl(residual)
     if residual_plane is not None:
-        assert MATH == "f16" and residual is None and tuple(residual_plane.shape) == oshape
-        rh = _hl(residual_plane.buf)[0]
-        L.check(_timed(_x3_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_res16_f16(
-            xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), rh, int(bool(relu)), L.ptr(ws), nbytes,
-            L.stream()), pl.desc, 0.5 * n_out, n_out, yp is not None, bool(fp32)),
-                "conv2d_forward_res16_f16")
-    elif MATH == "f16":
-        L.check(_timed(_x3_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_f16(
-            xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), int(bool(relu)), L.ptr(ws),
-            nbytes, L.stream()), pl.desc, _numel(residual), n_out, yp is not None, bool(fp32)),
-                "conv2d_forward_f16")
-    else:
-        L.check(_timed(_x3_variant(s, 0), pl.flops, lambda: lib.jtsm_conv2d_forward_bf16x3(
-            xh, xl, wh, wl, L.ptr(y), yh, yl, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), int(bool(relu)),
-            L.ptr(ws), nbytes, L.stream()), pl.desc, _numel(residual), n_out, yp is not None, bool(fp32)),
-                "conv2d_forward_bf16x3")
+        assert tuple(residual_plane.shape) == oshape
+    _launch_forward(pl, x.buf, wbuf, y, _buf(yp), scale, bias, residual, relu, _buf(residual_plane))
     if both:
         return y, yp
     return y if fp32 else yp
@@ -875,52 +949,18 @@ class _ColsumSlot(object):
 
 def planes_backward_data(g, w, x_shape, stride=1, pad=0, dil=1, gate=None, fp32=False, accumulate=None,
                          row_scale=None, kscale=None, both=False, into=None, bias_out=None, accumulate_plane=None):
-    """bias_out (a ColsumBatch slot): ALSO the column sums of the finished (gated) result — the bias gradient of the
+    """g: PlaneTensor of the output gradient (gradient planes: times 2^GRAD_SHIFT in fp16 mode); gate: PlaneTensor of
+    the ReLU output the result is gated by (or None) -> the input gradient as fp32 tensor (fp32=True) or PlaneTensor.
+    kscale: per-output-channel factor folded into the weight rows (FrozenBN).  both: fp32 AND planes.
+    bias_out (a ColsumBatch slot): ALSO the column sums of the finished (gated) result — the bias gradient of the
     layer whose output gradient this call produces — taken in the epilogue that writes it.  Returns (result, True)
     then, or (result, False) when this shape cannot (the caller sums the planes afterwards)."""
     if bias_out is not None:
-        assert not fp32 and not both and accumulate is None and into is None
-        return _planes_backward_data_colsum(g, w, x_shape, stride, pad, dil, gate, kscale, bias_out, row_scale)
-    return _planes_backward_data(g, w, x_shape, stride, pad, dil, gate, fp32, accumulate, row_scale, kscale, both, into,
-                                 accumulate_plane)
-
-
-def _planes_backward_data_colsum(g, w, x_shape, stride, pad, dil, gate, kscale, bias_out, row_scale=None):
+        assert not fp32 and not both and accumulate is None and into is None and accumulate_plane is None
     pl = _plan(x_shape, w.shape, stride, pad, dil)
-    part = _colsum_partials(pl, 1, x_shape[1], g.device) if pl.x3[1] else None
-    if part is None:
-        return _planes_backward_data(g, w, x_shape, stride, pad, dil, gate, False, None, row_scale, kscale, False,
-                                     None), False
-    dp = PlaneTensor.empty(x_shape, g.device)
-    gh, gl = _hl(g.buf)
-    wh, wl = _hl(_weight_planes(_cl(w), True, kscale))
-    dh, dl = _hl(dp.buf)
-    gate_h = _hl(gate.buf)[0] if gate is not None else None
-    nbytes = pl.ws[1]
-    ws = _scratch(nbytes, g.device)
-    lib = L.lib()
-    extra = 0.5 * dp.numel if gate is not None else 0
-    if MATH == "f16":
-        L.check(_timed(_x3_variant(pl.s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_colsum_f16(
-            gh, wh, None, dh, pl.ref, L.ptr(row_scale), None, None, gate_h, GRAD_SHIFT, L.ptr(part), L.ptr(ws),
-            nbytes, L.stream()), pl.desc, extra, dp.numel, True, False), "conv2d_backward_data_colsum_f16")
-    else:
-        L.check(_timed(_x3_variant(pl.s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_colsum_bf16x3(
-            gh, gl, wh, wl, None, dh, dl, pl.ref, L.ptr(row_scale), None, None, gate_h, L.ptr(part), L.ptr(ws),
-            nbytes, L.stream()), pl.desc, extra, dp.numel, True, False), "conv2d_backward_data_colsum_bf16x3")
-    bias_out.take(part)
-    return dp, True
-
-
-def _planes_backward_data(g, w, x_shape, stride=1, pad=0, dil=1, gate=None, fp32=False, accumulate=None,
-                          row_scale=None, kscale=None, both=False, into=None, accumulate_plane=None):
-    """... kscale: per-output-channel factor folded into the weight rows (FrozenBN).  both: fp32 AND planes."""
-    """g: PlaneTensor of the output gradient (gradient planes: times 2^GRAD_SHIFT in fp16 mode); gate: PlaneTensor of
-    the ReLU output the result is gated by (or None) -> the input gradient as fp32 tensor (fp32=True) or PlaneTensor."""
-    pl = _plan(x_shape, w.shape, stride, pad, dil)
-    s = pl.s
     if not pl.x3[1]:
         raise RuntimeError("planes_backward_data: shape is not eligible for the plane arithmetic")
+    part = _colsum_partials(pl, 1, x_shape[1], g.device) if bias_out is not None else None
     fp32 = fp32 or both
     if into is not None:   # add into an existing gradient map in place (see conv2d_backward_data)
         assert fp32 and not both and accumulate is None and gate is None and tuple(into.shape) == tuple(x_shape) and \
@@ -930,38 +970,19 @@ def _planes_backward_data(g, w, x_shape, stride=1, pad=0, dil=1, gate=None, fp32
     else:
         dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=g.device, memory_format=CL) if fp32 else None
     dp = PlaneTensor.empty(x_shape, g.device) if (both or not fp32) else None
-    gh, gl = _hl(g.buf)
-    wh, wl = _hl(_weight_planes(_cl(w), True, kscale))
-    dh, dl = _hl(dp.buf if dp is not None else None)
-    gate_h = _hl(gate.buf)[0] if gate is not None else None
-    nbytes = pl.ws[1]
-    ws = _scratch(nbytes, g.device)
-    lib = L.lib()
-    n_in = 1
-    for d in x_shape:
-        n_in *= d
-    extra = (0.5 * n_in if gate is not None else 0) + _numel(accumulate)     # (the gate plane: 2 bytes per element)
+    wbuf = _weight_planes(_cl(w), True, kscale)
     if accumulate is not None:
         accumulate = _cl(accumulate)
     if accumulate_plane is not None:
         # another gradient term as an fp16 plane (times 2^GRAD_SHIFT): the shortcut path of a chain whose gradient
         # stream has no fp32 copy
-        assert MATH == "f16" and accumulate is None and into is None and tuple(accumulate_plane.shape) == tuple(x_shape)
-        ah = _hl(accumulate_plane.buf)[0]
-        L.check(_timed(_x3_variant(s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_acc16_f16(
-            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), ah, gate_h, GRAD_SHIFT, L.ptr(ws), nbytes,
-            L.stream()), pl.desc, extra + 0.5 * n_in, n_in, dp is not None, fp32), "conv2d_backward_data_acc16_f16")
-    elif MATH == "f16":
-        L.check(_timed(_x3_variant(s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_ex_f16(
-            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), L.ptr(accumulate), None, gate_h, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream()),
-            pl.desc, extra, n_in, dp is not None, fp32), "conv2d_backward_data_ex_f16")
-    else:
-        L.check(_timed(_x3_variant(s, 1), pl.flops, lambda: lib.jtsm_conv2d_backward_data_ex_bf16x3(
-            gh, gl, wh, wl, L.ptr(dx), dh, dl, pl.ref, L.ptr(row_scale), L.ptr(accumulate), None, gate_h, L.ptr(ws), nbytes,
-            L.stream()), pl.desc, extra, n_in, dp is not None, fp32), "conv2d_backward_data_ex_bf16x3")
-    if both:
-        return dx, dp
-    return dx if fp32 else dp
+        assert into is None and tuple(accumulate_plane.shape) == tuple(x_shape)
+    _launch_backward_data(pl, g.buf, wbuf, dx, _buf(dp), accumulate, None, row_scale, _buf(gate),
+                          _buf(accumulate_plane), part)
+    if part is not None:
+        bias_out.take(part)
+    result = (dx, dp) if both else (dx if fp32 else dp)
+    return (result, part is not None) if bias_out is not None else result
 
 
 def planes_backward_weight(g, x, w, stride=1, pad=0, dil=1, w_shape=None, row_scale=None, bias_out=None):
@@ -969,32 +990,14 @@ def planes_backward_weight(g, x, w, stride=1, pad=0, dil=1, w_shape=None, row_sc
     the data-parallel exchange registered one."""
     w_shape = tuple(w.shape) if w_shape is None else tuple(w_shape)
     pl = _plan(x.shape, w_shape, stride, pad, dil)
-    s = pl.s
     if not pl.x3[2]:
         raise RuntimeError("planes_backward_weight: shape is not eligible for the plane arithmetic")
-    slot = grad_slot(w)
-    if slot is not None:
-        taps = w_shape[2] * w_shape[3]
-        slot = slot.as_strided(w_shape, (taps * w_shape[1], 1, w_shape[3] * w_shape[1], w_shape[1]))
+    slot = _slot_view(w, w_shape)
     out = slot if slot is not None else torch.empty(w_shape, dtype=torch.float32, device=x.device, memory_format=CL)
-    gh, gl = _hl(g.buf)
-    xh, xl = _hl(x.buf)
-    if bias_out is not None and BIAS_IN_WGRAD and _wgrad_bias_fits(pl):   # db beside dW, from the same gradient planes
-        _wgrad_bias_call(pl, gh, gl, xh, xl, out, bias_out, row_scale, True, x.device)
-        return out
-    if bias_out is not None:
+    if bias_out is not None and not (BIAS_IN_WGRAD and _wgrad_bias_fits(pl)):
         bias_out.copy_(planes_channel_sum(g))
-    nbytes = pl.ws[2]
-    ws = _scratch(nbytes, x.device)
-    lib = L.lib()
-    if MATH == "f16":
-        L.check(_timed(_x3_variant(s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_f16(
-            gh, xh, L.ptr(out), pl.ref, L.ptr(row_scale), 1, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream()),
-            pl.desc, 0, out.numel()), "conv2d_backward_weight_f16")
-    else:
-        L.check(_timed(_x3_variant(s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_bf16x3(
-            gh, gl, xh, xl, L.ptr(out), pl.ref, L.ptr(row_scale), 1, L.ptr(ws), nbytes, L.stream()),
-            pl.desc, 0, out.numel()), "conv2d_backward_weight_bf16x3")
+        bias_out = None     # (else: db beside dW, from the same gradient planes)
+    _launch_backward_weight(pl, g.buf, x.buf, out, row_scale, True, bias_out)
     return out
 
 
@@ -1250,10 +1253,7 @@ def flush_deferred_weight_gradients():
             n = len(part)
             outs = []
             for g, x, w, _, _, _, rs in part:
-                slot = grad_slot(w)
-                taps = w_shape[2] * w_shape[3]
-                if slot is not None:
-                    slot = slot.as_strided(w_shape, (taps * w_shape[1], 1, w_shape[3] * w_shape[1], w_shape[1]))
+                slot = _slot_view(w, w_shape)
                 outs.append(slot if slot is not None else
                             torch.empty(w_shape, dtype=torch.float32, device=x.device, memory_format=CL))
             ptr_t = C.c_void_p * n
@@ -1324,26 +1324,10 @@ def planes_channel_sum_multi(gs, grad=True):
 def planes_conv_transpose2x2_forward(x, w, bias=None, relu=False, fp32=False):
     """conv_transpose2x2_forward on a PlaneTensor -> PlaneTensor of y (or the fp32 y with fp32=True)."""
     n, i, h, wd = x.shape
-    o = w.shape[1]
-    oshape = (n, o, 2 * h, 2 * wd)
+    oshape = (n, w.shape[1], 2 * h, 2 * wd)
     y = torch.empty(oshape, dtype=torch.float32, device=x.device, memory_format=CL) if fp32 else None
     yp = PlaneTensor.empty(oshape, x.device)
-    xh, xl = _hl(x.buf)
-    w1 = w.as_strided((i, 4 * o, 1, 1), (4 * o, 1, 1, 1))
-    wth, wtl = _hl(_weight_planes(w1, True))
-    yh, yl = _hl(yp.buf)
-    lib = L.lib()
-    flops = 2.0 * n * h * wd * i * 4 * o
-    var = _x3_variant(_plan((n, i, h, wd), (4 * o, i, 1, 1), 1, 0, 1).s, 0)
-    var = _Variant(str(var), 1) if var is not None else None
-    if MATH == "f16":
-        L.check(_timed(var, flops, lambda: lib.jtsm_conv_transpose2x2_forward_f16(
-            xh, wth, L.ptr(y), yh, n, h, wd, i, o, L.ptr(bias), int(bool(relu)), L.stream()),
-            _ct_desc(n, h, wd, i, o), 0, yp.numel, True, fp32), "conv_transpose2x2_forward_f16")
-    else:
-        L.check(_timed(var, flops, lambda: lib.jtsm_conv_transpose2x2_forward_bf16x3(
-            xh, xl, wth, wtl, L.ptr(y), yh, yl, n, h, wd, i, o, L.ptr(bias), int(bool(relu)), L.stream()),
-            _ct_desc(n, h, wd, i, o), 0, yp.numel, True, fp32), "conv_transpose2x2_forward_bf16x3")
+    _launch_ct_forward(x.buf, x.shape, w, y, yp.buf, bias, relu)
     if y is not None:
         planes_put(y, yp.buf)
     return (y, yp) if fp32 else yp
@@ -1354,46 +1338,13 @@ def planes_conv_transpose2x2_backward_data(g, w, gate=None, bias_out=None):
     bias_out (in,): see planes_backward_data — then returns (dx, whether bias_out was written)."""
     n, o, h2, w2 = g.shape
     i = w.shape[0]
-    h, wd = h2 // 2, w2 // 2
     pl = _plan(g.shape, (i, o, 2, 2), 2, 0, 1)
-    dp = PlaneTensor.empty((n, i, h, wd), g.device)
+    dp = PlaneTensor.empty((n, i, h2 // 2, w2 // 2), g.device)
     part = _colsum_partials(pl, 0, i, g.device) if bias_out is not None else None
+    _launch_ct_backward_data(pl, g.buf, _weight_planes(w), None, dp.buf, gate=_buf(gate), colsum=part)
     if part is not None:
-        gh, gl = _hl(g.buf)
-        wh, wl = _hl(_weight_planes(w))
-        dh, dl = _hl(dp.buf)
-        gate_h = _hl(gate.buf)[0] if gate is not None else None
-        nbytes = pl.ws[0]
-        ws = _scratch(nbytes, g.device)
-        lib = L.lib()
-        extra = 0.5 * dp.numel if gate is not None else 0
-        if MATH == "f16":
-            L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_colsum_f16(
-                gh, wh, None, dh, n, h, wd, i, o, None, gate_h, GRAD_SHIFT, L.ptr(part), L.ptr(ws), nbytes,
-                L.stream()), pl.desc, extra, dp.numel, True, False), "conv_transpose2x2_backward_data_colsum_f16")
-        else:
-            L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_colsum_bf16x3(
-                gh, gl, wh, wl, None, dh, dl, n, h, wd, i, o, None, gate_h, L.ptr(part), L.ptr(ws), nbytes,
-                L.stream()), pl.desc, extra, dp.numel, True, False), "conv_transpose2x2_backward_data_colsum_bf16x3")
         bias_out.take(part)
-        return dp, True
-    gh, gl = _hl(g.buf)
-    wh, wl = _hl(_weight_planes(w))
-    dh, dl = _hl(dp.buf)
-    gate_h = _hl(gate.buf)[0] if gate is not None else None
-    nbytes = pl.ws[0]
-    ws = _scratch(nbytes, g.device)
-    lib = L.lib()
-    extra = 0.5 * dp.numel if gate is not None else 0
-    if MATH == "f16":
-        L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_f16(
-            gh, wh, None, dh, n, h, wd, i, o, None, gate_h, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream()),
-            pl.desc, extra, dp.numel, True, False), "conv_transpose2x2_backward_data_f16")
-    else:
-        L.check(_timed(_x3_variant(pl.s, 0), pl.flops, lambda: lib.jtsm_conv_transpose2x2_backward_data_bf16x3(
-            gh, gl, wh, wl, None, dh, dl, n, h, wd, i, o, None, gate_h, L.ptr(ws), nbytes, L.stream()),
-            pl.desc, extra, dp.numel, True, False), "conv_transpose2x2_backward_data_bf16x3")
-    return (dp, False) if bias_out is not None else dp
+    return (dp, part is not None) if bias_out is not None else dp
 
 
 def planes_conv_transpose2x2_backward_weight(g, x, w):
@@ -1450,21 +1401,6 @@ def wgrad_bias_fits(x_shape, w_shape, stride=1, pad=0, dil=1):
         return False
     pl = _plan(x_shape, w_shape, stride, pad, dil)
     return bool(pl.x3[2]) and _wgrad_bias_fits(pl)
-
-
-def _wgrad_bias_call(pl, gh, gl, xh, xl, out, bias_out, row_scale, fresh, device):
-    """Weight gradient + bias gradient in one contraction (jtsm_conv2d_backward_weight_bias_*)."""
-    nbytes = max(pl.ws[3], pl.ws[2])
-    ws = _scratch(nbytes, device)
-    lib = L.lib()
-    if MATH == "f16":
-        L.check(_timed(_x3_variant(pl.s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_bias_f16(
-            gh, xh, L.ptr(out), L.ptr(bias_out), pl.ref, L.ptr(row_scale), int(fresh), GRAD_SHIFT, L.ptr(ws),
-            nbytes, L.stream()), pl.desc, 0, out.numel()), "conv2d_backward_weight_bias_f16")
-    else:
-        L.check(_timed(_x3_variant(pl.s, 2), pl.flops, lambda: lib.jtsm_conv2d_backward_weight_bias_bf16x3(
-            gh, gl, xh, xl, L.ptr(out), L.ptr(bias_out), pl.ref, L.ptr(row_scale), int(fresh), L.ptr(ws),
-            nbytes, L.stream()), pl.desc, 0, out.numel()), "conv2d_backward_weight_bias_bf16x3")
 
 
 class _ConvFused(Function):
