@@ -1479,33 +1479,6 @@ inline int finish_split(const Params& p, int splits, hipStream_t st, int scale_b
   return JTSM_OK;
 }
 
-template <int ROLE, int BM, int BN>
-int launch_split(Params& p, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  const int ntiles = ceil_div(p.N, BN) * ceil_div(p.M, BM);
-  const int ktiles = ceil_div(p.K, BK);
-  int splits = plan_splits(ntiles, ktiles);
-  if (splits > 1 && (size_t)splits * p.M * p.ldc * sizeof(float) > workspace_bytes) splits = 1;
-  const bool dma = dma_eligible(ROLE, p) && ceil_div(ktiles, splits) >= kDmaMinKTiles;
-  const bool dma1 = !dma && dma_eligible(ROLE, p) && kShortSweepDma;
-  if (splits <= 1) {
-    if (dma) hipLaunchKernelGGL((igemm_dma_kernel<ROLE, BM, BN, 2>), dim3(ntiles, 1), dim3(256), 0, st, p);
-    else if (dma1) hipLaunchKernelGGL((igemm_dma_kernel<ROLE, BM, BN, 1>), dim3(ntiles, 1), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((igemm_kernel<ROLE, BM, BN>), dim3(ntiles, 1), dim3(256), 0, st, p);
-    JTSM_CHECK_LAUNCH("igemm");
-    record_mid(st);
-    return JTSM_OK;
-  }
-  p.ktiles_per_split = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, p.ktiles_per_split);
-  p.slab = reinterpret_cast<float*>(workspace);
-  if (dma) hipLaunchKernelGGL((igemm_dma_kernel<ROLE, BM, BN, 2>), dim3(ntiles, splits), dim3(256), 0, st, p);
-  else if (dma1) hipLaunchKernelGGL((igemm_dma_kernel<ROLE, BM, BN, 1>), dim3(ntiles, splits), dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((igemm_kernel<ROLE, BM, BN>), dim3(ntiles, splits), dim3(256), 0, st, p);
-  JTSM_CHECK_LAUNCH("igemm split-K");
-  record_mid(st);
-  return finish_split(p, splits, st);
-}
-
 #include "conv_x3.h"
 
 // The finishing pass of a GROUP of same-shape weight gradients (conv_x3.h: X3Group): blockIdx.y = member.
@@ -1517,21 +1490,6 @@ __global__ __launch_bounds__(256) void splitk_finish_group(const Params p_in, in
   p.e.scale = G.scale[z];
   p.slab += (size_t)z * G.slab_stride;
   splitk_finish_body<VEC, 1>(p, splits, 1);
-}
-
-
-template <int ROLE, int BM, int BN>
-int launch(const Params& p, int splits, hipStream_t st) {
-  const int ntiles = ceil_div(p.N, BN) * ceil_div(p.M, BM);
-  if (dma_eligible(ROLE, p) && p.ktiles_per_split >= kDmaMinKTiles)
-    hipLaunchKernelGGL((igemm_dma_kernel<ROLE, BM, BN, 2>), dim3(ntiles, splits), dim3(256), 0, st, p);
-  else if (dma_eligible(ROLE, p) && kShortSweepDma && ROLE != WGRAD)  // WGRAD short sweeps: register-staged is on par
-    hipLaunchKernelGGL((igemm_dma_kernel<ROLE, BM, BN, 1>), dim3(ntiles, splits), dim3(256), 0, st, p);
-  else
-    hipLaunchKernelGGL((igemm_kernel<ROLE, BM, BN>), dim3(ntiles, splits), dim3(256), 0, st, p);
-  JTSM_CHECK_LAUNCH("igemm");
-  record_mid(st);
-  return JTSM_OK;
 }
 
 int check_shape(const jtsm_conv_shape* s) {
@@ -1553,6 +1511,94 @@ ConvShape to_shape(const jtsm_conv_shape* s) {
   return c;
 }
 
+inline bool strided_1x1(const ConvShape& s) { return s.KH == 1 && s.KW == 1 && s.pad == 0 && s.stride > 1; }
+
+// The role -> GEMM mapping of every entry point and query: checks the shape, fills p.s and p.M, p.N, p.K.
+// out_grid: count the data gradient of a strided 1x1 convolution on the OUTPUT grid, where it runs (scatter_from_output_grid).
+// The queries pass true; a launcher maps with false and switches once it has seen that its epilogue operands allow it.
+int map_gemm(const jtsm_conv_shape* s, int role, bool out_grid, Params& p) {
+  int rc = check_shape(s);
+  if (rc) return rc;
+  p.s = to_shape(s);
+  JTSM_REQUIRE(p.s.Ho > 0 && p.s.Wo > 0, "conv: kernel larger than padded input");
+  const int taps = p.s.KH * p.s.KW, out_pixels = p.s.Bn * p.s.Ho * p.s.Wo;
+  if (role == FWD) { p.M = out_pixels; p.N = p.s.Cout; p.K = taps * p.s.Cin; }
+  else if (role == DGRAD) {
+    p.M = out_grid && strided_1x1(p.s) ? out_pixels : p.s.Bn * p.s.H * p.s.W; p.N = p.s.Cin; p.K = taps * p.s.Cout;
+  } else { p.M = p.s.Cout; p.N = taps * p.s.Cin; p.K = out_pixels; }
+  return JTSM_OK;
+}
+
+// Strided 1x1 data gradient: only every stride-th input pixel receives gradient.  Zero dX (unless it holds a gradient
+// that the scattered rows are added to in place — the epilogue reads its residual at the scattered position — while
+// the pixels in between keep what they hold), then run the dense GEMM over the OUTPUT pixels (a 1x1 / stride-1 problem
+// on the (Ho, Wo) grid) and scatter its rows.
+int scatter_from_output_grid(Params& p, float* dx, bool zero_dx, hipStream_t st) {
+  if (zero_dx) JTSM_CHECK_HIP(hipMemsetAsync(dx, 0, (size_t)p.M * p.N * sizeof(float), st));
+  p.scatter = 1; p.sc_Ho = p.s.Ho; p.sc_Wo = p.s.Wo; p.sc_H = p.s.H; p.sc_W = p.s.W; p.sc_stride = p.s.stride;
+  p.s.H = p.s.Ho; p.s.W = p.s.Wo; p.s.stride = 1;
+  p.M = p.s.Bn * p.s.Ho * p.s.Wo;
+  return JTSM_OK;
+}
+
+// What an fp32 launch does: the ONLY place the fp32 path's tile, slice and kernel rules live (launch_f32 launches
+// from it, jtsm_conv_plan and jtsm_conv_workspace_bytes report from it).
+struct F32Plan {
+  int bm, bn, ntiles;
+  int wanted;             // FWD / DGRAD: K slices wanted — what the scratch has to hold, splits * M * N floats
+  int splits;             // K slices launched (grid.y)
+  int ktiles_per_split;
+  int kernel;             // 0: igemm_kernel (register-staged), 1: igemm_dma_kernel, 2: its single-buffered form
+};
+
+// workspace_bytes: the scratch at hand (a FWD / DGRAD launch whose slabs do not fit runs unsplit; WGRAD adds its
+// slices with atomics and needs none).
+F32Plan plan_f32(int role, const Params& p, size_t workspace_bytes) {
+  F32Plan pl = {};
+  const bool narrow = role != WGRAD && p.N <= 64;
+  pl.bm = narrow ? 256 : 128; pl.bn = narrow ? 64 : 128;
+  pl.ntiles = ceil_div(p.N, pl.bn) * ceil_div(p.M, pl.bm);
+  const int ktiles = ceil_div(p.K, BK);
+  if (role == WGRAD) {
+    // Split the pixel axis so that ~4 workgroups per CU are in flight (1024 groups), but keep at
+    // least 8 K tiles (256 pixels) per split so the atomic tail stays small.
+    pl.splits = ceil_div(kWgradTargetBlocks, pl.ntiles);
+    if (pl.splits > ceil_div(ktiles, 8)) pl.splits = ceil_div(ktiles, 8);
+    if (pl.splits < 1) pl.splits = 1;
+    pl.wanted = 1;
+  } else {
+    pl.wanted = pl.splits = plan_splits(pl.ntiles, ktiles);
+    if (pl.splits > 1 && (size_t)pl.splits * p.M * p.N * sizeof(float) > workspace_bytes) pl.splits = 1;
+  }
+  pl.ktiles_per_split = even_slices(ktiles, pl.splits);
+  // (WGRAD short sweeps: the register-staged kernel is on par with the single-buffered DMA one)
+  pl.kernel = !dma_eligible(role, p) ? 0
+              : (pl.ktiles_per_split >= kDmaMinKTiles ? 1 : ((kShortSweepDma && role != WGRAD) ? 2 : 0));
+  return pl;
+}
+
+template <int ROLE, int BM, int BN>
+int launch_f32(Params& p, const F32Plan& pl, void* workspace, hipStream_t st) {
+  const bool slabs = ROLE != WGRAD && pl.splits > 1;
+  if (ROLE == WGRAD || slabs) p.ktiles_per_split = pl.ktiles_per_split;
+  if (slabs) p.slab = reinterpret_cast<float*>(workspace);
+  const dim3 grid(pl.ntiles, pl.splits);
+  if (pl.kernel == 1) hipLaunchKernelGGL((igemm_dma_kernel<ROLE, BM, BN, 2>), grid, dim3(256), 0, st, p);
+  else if (pl.kernel == 2) hipLaunchKernelGGL((igemm_dma_kernel<ROLE, BM, BN, 1>), grid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((igemm_kernel<ROLE, BM, BN>), grid, dim3(256), 0, st, p);
+  JTSM_CHECK_LAUNCH(slabs ? "igemm split-K" : "igemm");
+  record_mid(st);
+  return slabs ? finish_split(p, pl.splits, st) : JTSM_OK;
+}
+
+// FWD / DGRAD: plan against the scratch handed in and launch on the plan's tile.
+template <int ROLE>
+int launch_split(Params& p, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  const F32Plan pl = plan_f32(ROLE, p, workspace ? workspace_bytes : 0);
+  if (pl.bm == 256) return launch_f32<ROLE, 256, 64>(p, pl, workspace, st);
+  return launch_f32<ROLE, 128, 128>(p, pl, workspace, st);
+}
+
 }  // namespace
 }  // namespace jtsm
 
@@ -1571,129 +1617,74 @@ int jtsm_conv_out_size(const jtsm_conv_shape* s, int* out_h, int* out_w) {
 }
 
 size_t jtsm_conv_workspace_bytes(const jtsm_conv_shape* s, int backward_data) {
-  if (!s || check_shape(s)) return 0;
-  const ConvShape c = to_shape(s);
-  if (c.Ho <= 0 || c.Wo <= 0) return 0;
-  long M, N, K;
-  if (!backward_data) { M = (long)c.Bn * c.Ho * c.Wo; N = c.Cout; K = (long)c.KH * c.KW * c.Cin; }
-  else if (c.KH == 1 && c.KW == 1 && c.pad == 0 && c.stride > 1) { M = (long)c.Bn * c.Ho * c.Wo; N = c.Cin; K = c.Cout; }
-  else { M = (long)c.Bn * c.H * c.W; N = c.Cin; K = (long)c.KH * c.KW * c.Cout; }
-  const int bm = N <= 64 ? 256 : 128, bn = N <= 64 ? 64 : 128;
-  int splits = plan_splits(ceil_div(N, bn) * ceil_div(M, bm), ceil_div(K, BK));
-  Params p = {};   // the bf16x3 launcher may want more slices (other tiles, other round size): cover both
-  p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  const int sx = x3_wanted_splits(p);
-  if (sx > splits) splits = sx;
-  return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
+  Params p = {};
+  const int role = backward_data ? DGRAD : FWD;
+  if (!s || map_gemm(s, role, true, p)) return 0;
+  // the bf16x3 launcher may want more slices (other tiles, other round size): cover both.  (Its generic kernel is asked.)
+  const int splits = std::max(plan_f32(role, p, SIZE_MAX).wanted, plan_x3(role, p, SIZE_MAX, true).wanted);
+  return splits > 1 ? (size_t)splits * p.M * p.N * sizeof(float) : 0;
 }
 
-// What a call of this shape will launch: *kernel = 0 register-staged igemm_kernel, 1 = igemm_dma_kernel;
-// tile and K-split as chosen by the launchers (assuming the caller passes the advertised workspace).
+// What a call of this shape will launch: *kernel = 0 register-staged igemm_kernel, 1 = igemm_dma_kernel, 2 = its
+// single-buffered form; tile and K-split as chosen by the launchers (assuming the caller passes the advertised workspace).
 // role: 0 forward, 1 backward-data, 2 backward-weight.
 int jtsm_conv_plan(const jtsm_conv_shape* s, int role, int has_kscale, int* kernel, int* tile_m, int* tile_n,
                    int* splits) {
-  int rc = check_shape(s);
-  if (rc) return rc;
   Params p = {};
-  p.s = to_shape(s);
-  JTSM_REQUIRE(p.s.Ho > 0 && p.s.Wo > 0, "conv: kernel larger than padded input");
+  int rc = map_gemm(s, role >= 0 && role <= 2 ? role : FWD, true, p);
+  if (rc) return rc;
   JTSM_REQUIRE(role >= 0 && role <= 2, "conv_plan: role must be 0, 1 or 2");
-  if (role == FWD) { p.M = p.s.Bn * p.s.Ho * p.s.Wo; p.N = p.s.Cout; p.K = p.s.KH * p.s.KW * p.s.Cin; }
-  else if (role == DGRAD) {
-    p.M = p.s.Bn * p.s.H * p.s.W; p.N = p.s.Cin; p.K = p.s.KH * p.s.KW * p.s.Cout;
-    if (p.s.KH == 1 && p.s.KW == 1 && p.s.pad == 0 && p.s.stride > 1) p.M = p.s.Bn * p.s.Ho * p.s.Wo;
-    if (has_kscale) p.kscale = reinterpret_cast<const float*>(1);
-  } else { p.M = p.s.Cout; p.N = p.s.KH * p.s.KW * p.s.Cin; p.K = p.s.Bn * p.s.Ho * p.s.Wo; }
-  int bm = 128, bn = 128, sp = 1, kps;
-  const int ktiles = ceil_div(p.K, BK);
-  if (role == WGRAD) {
-    const int ntiles = ceil_div(p.N, 128) * ceil_div(p.M, 128);
-    sp = ceil_div(kWgradTargetBlocks, ntiles);
-    if (sp > ceil_div(ktiles, 8)) sp = ceil_div(ktiles, 8);
-    if (sp < 1) sp = 1;
-    kps = ceil_div(ktiles, sp);
-    sp = kps > 0 ? ceil_div(ktiles, kps) : 1;
-  } else {
-    if (p.N <= 64) { bm = 256; bn = 64; }
-    sp = plan_splits(ceil_div(p.N, bn) * ceil_div(p.M, bm), ktiles);
-    kps = ceil_div(ktiles, sp);
-    sp = kps > 0 ? ceil_div(ktiles, kps) : 1;
-  }
-  if (kernel) *kernel = !dma_eligible(role, p) ? 0 : (kps >= kDmaMinKTiles ? 1 : ((kShortSweepDma && role != WGRAD) ? 2 : 0));
-  if (tile_m) *tile_m = bm;
-  if (tile_n) *tile_n = bn;
-  if (splits) *splits = sp;
+  if (role == DGRAD && has_kscale) p.kscale = reinterpret_cast<const float*>(1);
+  const F32Plan pl = plan_f32(role, p, SIZE_MAX);
+  if (kernel) *kernel = pl.kernel;
+  if (tile_m) *tile_m = pl.bm;
+  if (tile_n) *tile_n = pl.bn;
+  if (splits) *splits = pl.splits;
   return JTSM_OK;
 }
 
 int jtsm_conv2d_forward_f32(const float* x, const float* w, float* y, const jtsm_conv_shape* s,
                             const float* scale, const float* bias, const float* residual, int relu,
                             void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = check_shape(s);
-  if (rc) return rc;
   Params p = {};
-  p.s = to_shape(s);
-  JTSM_REQUIRE(p.s.Ho > 0 && p.s.Wo > 0, "conv: kernel larger than padded input");
-  p.M = p.s.Bn * p.s.Ho * p.s.Wo;
-  p.N = p.s.Cout;
-  p.K = p.s.KH * p.s.KW * p.s.Cin;
+  int rc = map_gemm(s, FWD, false, p);
+  if (rc) return rc;
   if (p.M == 0) return JTSM_OK;
   JTSM_REQUIRE(x && w && y, "conv forward: null pointer");
   JTSM_REQUIRE(aligned16(x) && aligned16(w), "conv forward: x and w must be 16-byte aligned");
   p.A = x; p.B = w; p.C = y; p.ldc = p.N;
   p.e.scale = scale; p.e.bias = bias; p.e.residual = residual; p.e.relu = relu;
-  hipStream_t st = as_stream(stream);
-  if (!workspace) workspace_bytes = 0;
-  if (p.N <= 64) return launch_split<FWD, 256, 64>(p, workspace, workspace_bytes, st);
-  return launch_split<FWD, 128, 128>(p, workspace, workspace_bytes, st);
+  return launch_split<FWD>(p, workspace, workspace_bytes, as_stream(stream));
 }
 
 int jtsm_conv2d_backward_data_f32(const float* dy, const float* w, float* dx,
                                   const jtsm_conv_shape* s, const float* kscale,
                                   const float* accumulate, const float* relu_mask, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  int rc = check_shape(s);
-  if (rc) return rc;
   Params p = {};
-  p.s = to_shape(s);
-  JTSM_REQUIRE(p.s.Ho > 0 && p.s.Wo > 0, "conv: kernel larger than padded input");
+  int rc = map_gemm(s, DGRAD, false, p);
+  if (rc) return rc;
   JTSM_REQUIRE(p.s.Cout % 4 == 0, "conv backward-data: out_c must be a multiple of 4, got %d", p.s.Cout);
-  p.M = p.s.Bn * p.s.H * p.s.W;
-  p.N = p.s.Cin;
-  p.K = p.s.KH * p.s.KW * p.s.Cout;
   if (p.M == 0) return JTSM_OK;
   JTSM_REQUIRE(dy && w && dx, "conv backward-data: null pointer");
   JTSM_REQUIRE(aligned16(dy) && aligned16(w), "conv backward-data: dy and w must be 16-byte aligned");
   p.A = dy; p.B = w; p.C = dx; p.ldc = p.N; p.kscale = kscale;
   p.e.residual = accumulate; p.e.mask = relu_mask;
   hipStream_t st = as_stream(stream);
-  if (!workspace) workspace_bytes = 0;
-  if (p.s.KH == 1 && p.s.KW == 1 && p.s.pad == 0 && p.s.stride > 1 && (!accumulate || accumulate == dx) && !relu_mask) {
-    // strided 1x1: only every stride-th input pixel receives gradient.  Zero dX, then run the dense
-    // GEMM over the OUTPUT pixels (a 1x1/stride-1 problem on the (Ho,Wo) grid) and scatter its rows.
-    // (accumulate == dx: dX holds a gradient already and the scattered rows are added to it in place — the epilogue
-    // reads its residual at the scattered position — while the pixels in between keep what they hold.)
-    if (!accumulate) JTSM_CHECK_HIP(hipMemsetAsync(dx, 0, (size_t)p.M * p.N * sizeof(float), st));
-    p.scatter = 1; p.sc_Ho = p.s.Ho; p.sc_Wo = p.s.Wo; p.sc_H = p.s.H; p.sc_W = p.s.W; p.sc_stride = p.s.stride;
-    p.s.H = p.s.Ho; p.s.W = p.s.Wo; p.s.stride = 1;
-    p.M = p.s.Bn * p.s.Ho * p.s.Wo;
+  if (strided_1x1(p.s) && (!accumulate || accumulate == dx) && !relu_mask) {
+    rc = scatter_from_output_grid(p, dx, !accumulate, st);
+    if (rc) return rc;
   }
-  if (p.N <= 64) return launch_split<DGRAD, 256, 64>(p, workspace, workspace_bytes, st);
-  return launch_split<DGRAD, 128, 128>(p, workspace, workspace_bytes, st);
+  return launch_split<DGRAD>(p, workspace, workspace_bytes, st);
 }
 
 int jtsm_conv2d_backward_weight_f32(const float* dy, const float* x, float* dw,
                                     const jtsm_conv_shape* s, const float* row_scale, int zero_dw,
                                     void* stream) {
-  int rc = check_shape(s);
-  if (rc) return rc;
   Params p = {};
-  p.s = to_shape(s);
-  JTSM_REQUIRE(p.s.Ho > 0 && p.s.Wo > 0, "conv: kernel larger than padded input");
+  int rc = map_gemm(s, WGRAD, false, p);
+  if (rc) return rc;
   JTSM_REQUIRE(p.s.Cout % 4 == 0, "conv backward-weight: out_c must be a multiple of 4, got %d", p.s.Cout);
-  p.M = p.s.Cout;
-  p.N = p.s.KH * p.s.KW * p.s.Cin;
-  p.K = p.s.Bn * p.s.Ho * p.s.Wo;
   JTSM_REQUIRE(dw, "conv backward-weight: null dw");
   hipStream_t st = as_stream(stream);
   if (zero_dw) JTSM_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)p.M * p.N * sizeof(float), st));
@@ -1702,16 +1693,7 @@ int jtsm_conv2d_backward_weight_f32(const float* dy, const float* x, float* dw,
   JTSM_REQUIRE(aligned16(dy) && aligned16(x), "conv backward-weight: dy and x must be 16-byte aligned");
   p.A = dy; p.B = x; p.C = dw; p.ldc = p.N;
   p.e.scale = row_scale;
-  // Split the pixel axis so that ~4 workgroups per CU are in flight (1024 groups), but keep at
-  // least 8 K tiles (256 pixels) per split so the atomic tail stays small.
-  const int ntiles = ceil_div(p.N, 128) * ceil_div(p.M, 128);
-  const int ktiles = ceil_div(p.K, BK);
-  int splits = ceil_div(kWgradTargetBlocks, ntiles);
-  if (splits > ceil_div(ktiles, 8)) splits = ceil_div(ktiles, 8);
-  if (splits < 1) splits = 1;
-  p.ktiles_per_split = ceil_div(ktiles, splits);
-  splits = ceil_div(ktiles, p.ktiles_per_split);
-  return launch<WGRAD, 128, 128>(p, splits, st);
+  return launch_f32<WGRAD, 128, 128>(p, plan_f32(WGRAD, p, 0), nullptr, st);
 }
 
 /* ---- split-bf16 ("bf16x3") path ---- */
@@ -1757,10 +1739,9 @@ int jtsm_split_bf16_transposed_f32(const float* w, const float* row_scale, uint1
 }
 
 int jtsm_conv_bf16x3_eligible(const jtsm_conv_shape* s, int role) {
-  if (!s || check_shape(s)) return 0;
-  const ConvShape c = to_shape(s);
-  if (c.Ho <= 0 || c.Wo <= 0) return 0;
-  return x3_eligible(role, c) ? 1 : 0;
+  Params p = {};
+  if (!s || map_gemm(s, FWD, false, p)) return 0;
+  return x3_eligible(role, p.s) ? 1 : 0;
 }
 
 }  // extern "C"
@@ -1783,16 +1764,11 @@ static int x3_forward(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t
                       const jtsm_conv_shape* s, const float* scale, const float* bias,
                       const float* residual, int relu, void* workspace, size_t workspace_bytes,
                       void* stream, const FwdExtras& ex = FwdExtras()) {
-  int rc = check_shape(s);
-  if (rc) return rc;
   Params p = {};
-  p.s = to_shape(s);
-  JTSM_REQUIRE(p.s.Ho > 0 && p.s.Wo > 0, "conv: kernel larger than padded input");
+  int rc = map_gemm(s, FWD, false, p);
+  if (rc) return rc;
   JTSM_REQUIRE(x3_eligible(FWD, p.s), "conv forward bf16x3: in_c=%d with a %dx%d kernel is not eligible "
                "(see jtsm_conv_bf16x3_eligible)", p.s.Cin, p.s.KH, p.s.KW);
-  p.M = p.s.Bn * p.s.Ho * p.s.Wo;
-  p.N = p.s.Cout;
-  p.K = p.s.KH * p.s.KW * p.s.Cin;
   if (p.M == 0) return JTSM_OK;
   JTSM_REQUIRE(x_hi && w_hi && (y || y_hi) && (NP == 1 || (x_lo && w_lo)), "conv forward bf16x3 / f16: null pointer");
   JTSM_REQUIRE(aligned16(x_hi) && aligned16(x_lo) && aligned16(w_hi) && aligned16(w_lo),
@@ -1834,16 +1810,11 @@ static int x3_backward_data(const uint16_t* dy_hi, const uint16_t* dy_lo, const 
                             void* workspace, size_t workspace_bytes, void* stream,
                             const uint16_t* gate_plane = nullptr, const float* row_scale = nullptr,
                             float* colsum = nullptr, const uint16_t* accumulate_h = nullptr) {
-  int rc = check_shape(s);
-  if (rc) return rc;
   Params p = {};
-  p.s = to_shape(s);
-  JTSM_REQUIRE(p.s.Ho > 0 && p.s.Wo > 0, "conv: kernel larger than padded input");
+  int rc = map_gemm(s, DGRAD, false, p);
+  if (rc) return rc;
   JTSM_REQUIRE(x3_eligible(DGRAD, p.s), "conv backward-data bf16x3: out_c=%d with a %dx%d kernel is not eligible",
                p.s.Cout, p.s.KH, p.s.KW);
-  p.M = p.s.Bn * p.s.H * p.s.W;
-  p.N = p.s.Cin;
-  p.K = p.s.KH * p.s.KW * p.s.Cout;
   if (p.M == 0) return JTSM_OK;
   JTSM_REQUIRE(dy_hi && wt_hi && (dx || dx_hi) && (NP == 1 || (dy_lo && wt_lo)),
                "conv backward-data bf16x3 / f16: null pointer");
@@ -1866,8 +1837,7 @@ static int x3_backward_data(const uint16_t* dy_hi, const uint16_t* dy_lo, const 
   JTSM_REQUIRE(NP == 1 || (dx_hi == nullptr) == (dx_lo == nullptr), "conv backward-data bf16x3: give both output planes or neither");
   hipStream_t st = as_stream(stream);
   if (!workspace) workspace_bytes = 0;
-  const bool scatter = p.s.KH == 1 && p.s.KW == 1 && p.s.pad == 0 && p.s.stride > 1 && (!accumulate || accumulate == dx) &&
-                       !relu_mask && !gate_plane && !row_scale && dx;   // (accumulate == dx: see jtsm_conv2d_backward_data_f32)
+  const bool scatter = strided_1x1(p.s) && (!accumulate || accumulate == dx) && !relu_mask && !gate_plane && !row_scale && dx;
   JTSM_REQUIRE(!colsum || (aligned16(colsum) && !scatter), "conv backward-data: column sums need a 16-byte aligned buffer (not the strided 1x1 scatter)");
   p.colsum = colsum;
   JTSM_REQUIRE(!row_scale || (p.N % 4 == 0 && aligned16(dx)), "conv backward-data: a row scale needs in_c %% 4 == 0");
@@ -1878,10 +1848,8 @@ static int x3_backward_data(const uint16_t* dy_hi, const uint16_t* dy_lo, const 
     p.out_hi = dx_hi; p.out_lo = dx_lo;
   }
   if (scatter) {
-    if (!accumulate) JTSM_CHECK_HIP(hipMemsetAsync(dx, 0, (size_t)p.M * p.N * sizeof(float), st));
-    p.scatter = 1; p.sc_Ho = p.s.Ho; p.sc_Wo = p.s.Wo; p.sc_H = p.s.H; p.sc_W = p.s.W; p.sc_stride = p.s.stride;
-    p.s.H = p.s.Ho; p.s.W = p.s.Wo; p.s.stride = 1;
-    p.M = p.s.Bn * p.s.Ho * p.s.Wo;
+    rc = scatter_from_output_grid(p, dx, !accumulate, st);
+    if (rc) return rc;
   }
   return launch_split_x3<DGRAD, NP>(p, q, workspace, workspace_bytes, st);
 }
@@ -1897,6 +1865,20 @@ static bool x3_wgrad_big(const Params& p) {
   return t256 * ceil_div(p.K, XBK) >= min_work;   // (tiles x stages: measured crossover, tools/sweeps/wgrad_sweep.py)
 }
 
+// 256 x 256 tiles for a GROUP: the single launch's rule with the group's tile count (a res4 1x1 layer alone has 4 such
+// tiles — too few to fill the chip at any slice count; six of them have 24).
+static bool x3_wgrad_group_big(const Params& p, int n) {
+  static const int mode = [] { const char* e = getenv("JTSM_WGRAD_GROUP_BIG"); return e ? atoi(e) : 1; }();   // sweeps
+  if (mode == 0) return x3_wgrad_big(p);
+  if (p.M < 256 || p.N < 256) return false;
+  const long t256 = (long)ceil_div(p.N, 256) * ceil_div(p.M, 256) * n;
+  if (t256 < 8 || t256 * ceil_div(p.K, XBK) < 2000) return false;
+  // ... and only where slices of >= 16 stages still give most CUs a workgroup (res5's 2048 pixels do not: measured
+  // 53 us on 128 such workgroups against 44 us on 512 of the 128 x 128 tiles)
+  const long slices = std::min<long>(std::max<long>(1, 256 / t256), std::max<long>(1, ceil_div(p.K, XBK) / 16));
+  return t256 * slices >= 192;
+}
+
 // The LDS-halo weight gradient: 3x3, stride 1, undilated, 32-channel input blocks, output rows of whole 32-pixel
 // segments, and enough pixels to feed the split.
 static bool x3_wgrad_halo(const Params& p) {
@@ -1905,63 +1887,85 @@ static bool x3_wgrad_halo(const Params& p) {
          s.Cout % 8 == 0 && p.K >= 2048;
 }
 
-static int x3_wgrad_splits(const Params& p) {
-  if (x3_wgrad_halo(p)) {
-    const int ntiles = ceil_div(p.M, 128) * (p.s.Cin / 32), segs = p.K / 32;
-    int splits = ntiles >= 512 ? 1 : 512 / ntiles;
-    if (splits > segs / 8) splits = segs / 8;   // at least 8 segments per workgroup
-    if (splits > 64) splits = 64;
-    if (splits < 1) splits = 1;
-    return ceil_div(segs, ceil_div(segs, splits));
-  }
-  const bool big = x3_wgrad_big(p);
-  const int t = big ? 256 : 128;
-  const int ntiles = ceil_div(p.N, t) * ceil_div(p.M, t);
+// What a weight-gradient launch (bf16x3 and f16) does, alone or as a GROUP of n same-shape layers in one launch: the
+// ONLY place its tile and slice rules live.  x3_backward_weight / x3_backward_weight_group launch from it; the
+// workspace-size functions, jtsm_conv_bf16x3_plan and jtsm_conv_bf16x3_wgrad_group_plan report from it.
+struct WgradPlan {
+  bool halo;               // igemm_x3_wgrad_halo_kernel
+  bool big;                // 256 x 256 tiles of igemm_x3_wgrad_kernel (else 128 x 128)
+  int ntiles;              // output tiles of ONE layer (grid.x)
+  int splits;              // pixel slices (grid.y); deterministic: every slice writes its partial tile to a slab, a
+  int ktiles_per_split;    //   fixed-order pass adds them
+  size_t slab_bytes;       // the slabs of all members: n * splits * M * N floats (0: one slice, no scratch)
+  size_t bias_offset;      // single launch with a bias gradient: its per-slice partials follow the slabs here ...
+  size_t bias_bytes;       // ... splits * M floats
+};
+
+static WgradPlan plan_wgrad(const Params& p, bool group, int n, bool with_bias) {
+  WgradPlan pl = {};
   const int ktiles = ceil_div(p.K, XBK);
-  // Pixel-axis split (measured on MI355X, tools/sweeps/wsplit.py): the kernels are bound by memory latency x bytes in
-  // flight, so two workgroups per CU (512) beat one as long as each keeps >= 8 stages; 256 x 256 tiles hold one
-  // workgroup per CU.
-  // one resident round: 256 workgroups of 256 x 256 (one per CU), 512 of 128 x 128 (two per CU) — rounded DOWN, so the
-  // launch never spills a handful of workgroups into a second round (9 tiles x 29 slices = 261 did: half the time idle)
-  int splits = max(1, (big ? 256 : 512) / ntiles);
-  if (!big && ceil_div(ktiles, splits) > 64) splits = max(1, 768 / ntiles);
-  const int min_stages = big ? 16 : 8;
-  if (splits > ceil_div(ktiles, min_stages)) splits = ceil_div(ktiles, min_stages);
-  // slab traffic: the finishing pass reads splits x dW — 64 slices at most, more (up to 256) only while all the slabs
-  // together stay below 48 MB: the narrow predictors (80 x 256, 56 x 128 outputs over 10^5 pixels) were running on
-  // 64-128 workgroups
-  int cap = 64;
-  const size_t out_bytes = (size_t)p.M * p.N * sizeof(float);
-  while (cap < 256 && (size_t)cap * 2 * out_bytes <= (48u << 20)) cap *= 2;
-  if (splits > cap) splits = cap;
-  if (splits < 1) splits = 1;
-  const int kps = ceil_div(ktiles, splits);
-  return kps > 0 ? ceil_div(ktiles, kps) : 1;
+  pl.halo = x3_wgrad_halo(p);
+  if (pl.halo) {   // (output rows are whole 32-pixel segments: ktiles counts them)
+    pl.ntiles = ceil_div(p.M, 128) * (p.s.Cin / 32);
+    pl.splits = halo_slices(512, pl.ntiles * n, ktiles / 8, 64);   // at least 8 segments per workgroup
+  } else {
+    pl.big = group ? x3_wgrad_group_big(p, n) : x3_wgrad_big(p);
+    const int t = pl.big ? 256 : 128;
+    pl.ntiles = ceil_div(p.N, t) * ceil_div(p.M, t);
+    const int all_tiles = pl.ntiles * n;
+    // Pixel-axis split (measured on MI355X, tools/sweeps/wsplit.py): the kernels are bound by memory latency x bytes in
+    // flight, so two workgroups per CU (512) beat one as long as each keeps >= 8 stages; 256 x 256 tiles hold one
+    // workgroup per CU.
+    // one resident round: 256 workgroups of 256 x 256 (one per CU), 512 of 128 x 128 (two per CU) — rounded DOWN, so the
+    // launch never spills a handful of workgroups into a second round (9 tiles x 29 slices = 261 did: half the time idle)
+    pl.splits = max(1, (pl.big ? 256 : 512) / all_tiles);
+    if (!group && !pl.big && ceil_div(ktiles, pl.splits) > 64) pl.splits = max(1, 768 / all_tiles);
+    const int min_stages = pl.big ? 16 : 8;
+    if (pl.splits > ceil_div(ktiles, min_stages)) pl.splits = ceil_div(ktiles, min_stages);
+    // slab traffic: the finishing pass reads splits x dW — 64 slices at most; a single launch more (up to 256) only
+    // while all the slabs together stay below 48 MB: the narrow predictors (80 x 256, 56 x 128 outputs over 10^5
+    // pixels) were running on 64-128 workgroups
+    int cap = 64;
+    const size_t out_bytes = (size_t)p.M * p.N * sizeof(float);
+    while (!group && cap < 256 && (size_t)cap * 2 * out_bytes <= (48u << 20)) cap *= 2;
+    if (pl.splits > cap) pl.splits = cap;
+    if (pl.splits < 1) pl.splits = 1;
+  }
+  pl.ktiles_per_split = even_slices(ktiles, pl.splits);
+  if (pl.splits > 1) {
+    pl.slab_bytes = (size_t)n * pl.splits * p.M * p.N * sizeof(float);
+    pl.bias_offset = (pl.slab_bytes + 15) & ~(size_t)15;
+    pl.bias_bytes = with_bias ? (size_t)pl.splits * p.M * sizeof(float) : 0;
+  }
+  return pl;
 }
 
-extern "C" size_t jtsm_conv_bf16x3_wgrad_workspace_bytes(const jtsm_conv_shape* s);
+// The weight-gradient mapping for a query: false for a shape that launches nothing.
+static bool wgrad_query(const jtsm_conv_shape* s, Params& p) { return s && !map_gemm(s, WGRAD, false, p) && p.K > 0; }
+
 extern "C" size_t jtsm_conv_bf16x3_wgrad_bias_workspace_bytes(const jtsm_conv_shape* s) {
-  if (!s || check_shape(s)) return 0;
   Params p = {};
-  p.s = to_shape(s);
-  if (p.s.Ho <= 0 || p.s.Wo <= 0) return 0;
-  p.M = p.s.Cout; p.N = p.s.KH * p.s.KW * p.s.Cin; p.K = p.s.Bn * p.s.Ho * p.s.Wo;
-  if (p.K == 0) return 0;
-  const int splits = x3_wgrad_splits(p);
-  if (splits <= 1) return 0;
-  const size_t main_bytes = ((size_t)splits * p.M * p.N * sizeof(float) + 15) & ~(size_t)15;
-  return main_bytes + (size_t)splits * p.M * sizeof(float);
+  if (!wgrad_query(s, p)) return 0;
+  const WgradPlan pl = plan_wgrad(p, false, 1, true);
+  return pl.splits > 1 ? pl.bias_offset + pl.bias_bytes : 0;
 }
 
 extern "C" size_t jtsm_conv_bf16x3_wgrad_workspace_bytes(const jtsm_conv_shape* s) {
-  if (!s || check_shape(s)) return 0;
   Params p = {};
-  p.s = to_shape(s);
-  if (p.s.Ho <= 0 || p.s.Wo <= 0) return 0;
-  p.M = p.s.Cout; p.N = p.s.KH * p.s.KW * p.s.Cin; p.K = p.s.Bn * p.s.Ho * p.s.Wo;
-  if (p.K == 0) return 0;
-  const int splits = x3_wgrad_splits(p);
-  return splits > 1 ? (size_t)splits * p.M * p.N * sizeof(float) : 0;
+  return wgrad_query(s, p) ? plan_wgrad(p, false, 1, false).slab_bytes : 0;
+}
+
+template <int NP, bool BIAS>
+static void launch_wgrad(const WgradPlan& pl, const Params& p, const X3Planes& q, hipStream_t st) {
+  const dim3 grid(pl.ntiles, pl.splits);
+  if (pl.halo)
+    hipLaunchKernelGGL((igemm_x3_wgrad_halo_kernel<NP, BIAS>), grid, dim3(256), 0, st, p, q);
+  else if (pl.big)
+    hipLaunchKernelGGL((igemm_x3_wgrad_kernel<X3Tile256::wm, X3Tile256::wn, X3Tile256::tm, X3Tile256::tn, 2, NP, BIAS>),
+                       grid, dim3(512), 0, st, p, q);
+  else
+    hipLaunchKernelGGL((igemm_x3_wgrad_kernel<X3Tile128::wm, X3Tile128::wn, X3Tile128::tm, X3Tile128::tn, 2, NP, BIAS>),
+                       grid, dim3(256), 0, st, p, q);
 }
 
 template <int NP>
@@ -1969,16 +1973,11 @@ static int x3_backward_weight(const uint16_t* dy_hi, const uint16_t* dy_lo, cons
                               const uint16_t* x_lo, float* dw, const jtsm_conv_shape* s,
                               const float* row_scale, int zero_dw, int grad_shift, void* workspace,
                               size_t workspace_bytes, void* stream, float* bias_grad = nullptr) {
-  int rc = check_shape(s);
-  if (rc) return rc;
   Params p = {};
-  p.s = to_shape(s);
-  JTSM_REQUIRE(p.s.Ho > 0 && p.s.Wo > 0, "conv: kernel larger than padded input");
+  int rc = map_gemm(s, WGRAD, false, p);
+  if (rc) return rc;
   JTSM_REQUIRE(x3_eligible(WGRAD, p.s), "conv backward-weight bf16x3: in_c=%d and out_c=%d must be multiples of 8",
                p.s.Cin, p.s.Cout);
-  p.M = p.s.Cout;
-  p.N = p.s.KH * p.s.KW * p.s.Cin;
-  p.K = p.s.Bn * p.s.Ho * p.s.Wo;
   JTSM_REQUIRE(dw && aligned16(dw), "conv backward-weight bf16x3: dw must be non-null and 16-byte aligned");
   hipStream_t st = as_stream(stream);
   if (p.K == 0) {
@@ -1996,99 +1995,43 @@ static int x3_backward_weight(const uint16_t* dy_hi, const uint16_t* dy_lo, cons
   p.C = dw; p.ldc = p.N;
   p.e.scale = row_scale;
   if (!zero_dw) p.e.residual = dw;   // accumulate: dw = dw + result (the epilogue reads dw[o] before writing it)
-  // Deterministic: every pixel slice writes its partial tile to a slab, a fixed-order pass adds them.
-  int splits = x3_wgrad_splits(p);
-  const size_t need = (size_t)splits * p.M * p.N * sizeof(float);
-  JTSM_REQUIRE(splits <= 1 || (workspace && workspace_bytes >= need && aligned16(workspace)),
-               "conv backward-weight bf16x3: workspace of %zu bytes needed (jtsm_conv_bf16x3_wgrad_workspace_bytes)", need);
-  const bool big = x3_wgrad_big(p);
-  const int tl = big ? 256 : 128;
-  const int ntiles = ceil_div(p.N, tl) * ceil_div(p.M, tl);
-  p.ktiles_per_split = ceil_div(ceil_div(p.K, XBK), splits);
+  const WgradPlan pl = plan_wgrad(p, false, 1, bias_grad != nullptr);
+  const int splits = pl.splits;
+  JTSM_REQUIRE(splits <= 1 || (workspace && workspace_bytes >= pl.slab_bytes && aligned16(workspace)),
+               "conv backward-weight bf16x3: workspace of %zu bytes needed (jtsm_conv_bf16x3_wgrad_workspace_bytes)", pl.slab_bytes);
+  p.ktiles_per_split = pl.ktiles_per_split;
   p.slab = splits > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
   p.wide = 1;   // N = taps * in_c is a multiple of 8, dw / slab 16-byte aligned
-  const bool halo = x3_wgrad_halo(p);
   if (bias_grad) {   // db beside dW: per-slice partials behind the slabs, folded by the finishing pass
     if (splits > 1) {
-      const size_t off = (need + 15) & ~(size_t)15;
-      JTSM_REQUIRE(workspace_bytes >= off + (size_t)splits * p.M * sizeof(float),
+      JTSM_REQUIRE(workspace_bytes >= pl.bias_offset + pl.bias_bytes,
                    "conv backward-weight bf16x3: workspace too small for the bias partials "
                    "(jtsm_conv_bf16x3_wgrad_bias_workspace_bytes)");
-      p.bias_slab = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + off);
+      p.bias_slab = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + pl.bias_offset);
       p.bias_out = bias_grad;
     } else {
       p.bias_slab = bias_grad;
     }
   }
-  const bool fused = !bias_grad && use_fused_finish(p, halo ? ceil_div(p.M, 128) * (p.s.Cin / 32) : ntiles, splits, st);
-  if (halo) {
-    const int halo_tiles = ceil_div(p.M, 128) * (p.s.Cin / 32);
-    if (bias_grad) hipLaunchKernelGGL((igemm_x3_wgrad_halo_kernel<NP, true>), dim3(halo_tiles, splits), dim3(256), 0, st, p, q);
-    else hipLaunchKernelGGL((igemm_x3_wgrad_halo_kernel<NP, false>), dim3(halo_tiles, splits), dim3(256), 0, st, p, q);
-  } else if (big) {
-    if (bias_grad) hipLaunchKernelGGL((igemm_x3_wgrad_kernel<4, 2, 2, 4, 2, NP, true>), dim3(ntiles, splits), dim3(512), 0, st, p, q);
-    else hipLaunchKernelGGL((igemm_x3_wgrad_kernel<4, 2, 2, 4, 2, NP, false>), dim3(ntiles, splits), dim3(512), 0, st, p, q);
-  } else {
-    if (bias_grad) hipLaunchKernelGGL((igemm_x3_wgrad_kernel<2, 2, 2, 2, 2, NP, true>), dim3(ntiles, splits), dim3(256), 0, st, p, q);
-    else hipLaunchKernelGGL((igemm_x3_wgrad_kernel<2, 2, 2, 2, 2, NP, false>), dim3(ntiles, splits), dim3(256), 0, st, p, q);
-  }
+  const bool fused = !bias_grad && use_fused_finish(p, pl.ntiles, splits, st);
+  if (bias_grad) launch_wgrad<NP, true>(pl, p, q, st);
+  else launch_wgrad<NP, false>(pl, p, q, st);
   JTSM_CHECK_LAUNCH("igemm bf16x3 wgrad");
   record_mid(st);
   if (splits > 1 && !fused) return finish_split(p, splits, st, 1);
   return JTSM_OK;
 }
 
-// K slices of a GROUP of n same-shape weight gradients: the single launch's rule with n times the tiles — one resident
-// round of workgroups over the whole group.
-// 256 x 256 tiles for a GROUP: the single launch's rule with the group's tile count (a res4 1x1 layer alone has 4 such
-// tiles — too few to fill the chip at any slice count; six of them have 24).
-static bool x3_wgrad_group_big(const Params& p, int n) {
-  static const int mode = [] { const char* e = getenv("JTSM_WGRAD_GROUP_BIG"); return e ? atoi(e) : 1; }();   // sweeps
-  if (mode == 0) return x3_wgrad_big(p);
-  if (p.M < 256 || p.N < 256) return false;
-  const long t256 = (long)ceil_div(p.N, 256) * ceil_div(p.M, 256) * n;
-  if (t256 < 8 || t256 * ceil_div(p.K, XBK) < 2000) return false;
-  // ... and only where slices of >= 16 stages still give most CUs a workgroup (res5's 2048 pixels do not: measured
-  // 53 us on 128 such workgroups against 44 us on 512 of the 128 x 128 tiles)
-  const long slices = std::min<long>(std::max<long>(1, 256 / t256), std::max<long>(1, ceil_div(p.K, XBK) / 16));
-  return t256 * slices >= 192;
-}
-
-static int x3_wgrad_group_splits(const Params& p, int n) {
-  if (x3_wgrad_halo(p)) {
-    const int ntiles = ceil_div(p.M, 128) * (p.s.Cin / 32) * n, segs = p.K / 32;
-    int splits = ntiles >= 512 ? 1 : 512 / ntiles;
-    if (splits > segs / 8) splits = segs / 8;   // at least 8 segments per workgroup
-    if (splits > 64) splits = 64;
-    if (splits < 1) splits = 1;
-    return ceil_div(segs, ceil_div(segs, splits));
-  }
-  const bool big = x3_wgrad_group_big(p, n);
-  const int t = big ? 256 : 128;
-  const int ntiles = ceil_div(p.N, t) * ceil_div(p.M, t) * n;
-  const int ktiles = ceil_div(p.K, XBK);
-  int splits = max(1, (big ? 256 : 512) / ntiles);
-  const int min_stages = big ? 16 : 8;
-  if (splits > ceil_div(ktiles, min_stages)) splits = ceil_div(ktiles, min_stages);
-  if (splits > 64) splits = 64;
-  if (splits < 1) splits = 1;
-  const int kps = ceil_div(ktiles, splits);
-  return kps > 0 ? ceil_div(ktiles, kps) : 1;
-}
-
 static int group_shape(const jtsm_conv_shape* s, Params& p) {
-  int rc = check_shape(s);
+  int rc = map_gemm(s, WGRAD, false, p);
   if (rc) return rc;
-  p.s = to_shape(s);
-  JTSM_REQUIRE(p.s.Ho > 0 && p.s.Wo > 0, "conv: kernel larger than padded input");
   JTSM_REQUIRE(x3_eligible(WGRAD, p.s), "conv backward-weight group: in_c=%d and out_c=%d must be multiples of 8",
                p.s.Cin, p.s.Cout);
-  p.M = p.s.Cout;
-  p.N = p.s.KH * p.s.KW * p.s.Cin;
-  p.K = p.s.Bn * p.s.Ho * p.s.Wo;
   return JTSM_OK;
 }
 
+// A GROUP of n same-shape weight gradients in one launch (blockIdx.z = member): one resident round of workgroups over
+// the whole group (plan_wgrad).
 template <int NP>
 static int x3_backward_weight_group(int n, const uint16_t* const* dy_hi, const uint16_t* const* dy_lo,
                                     const uint16_t* const* x_hi, const uint16_t* const* x_lo, float* const* dw,
@@ -2118,25 +2061,23 @@ static int x3_backward_weight_group(int n, const uint16_t* const* dy_hi, const u
     G.C[i] = dw[i];
     G.scale[i] = row_scale ? row_scale[i] : nullptr;
   }
-  const int splits = x3_wgrad_group_splits(p, n);
+  const WgradPlan pl = plan_wgrad(p, true, n, false);
+  const int splits = pl.splits;
   G.slab_stride = (size_t)splits * p.M * p.N;
-  const size_t need = splits > 1 ? (size_t)n * G.slab_stride * sizeof(float) : 0;
-  JTSM_REQUIRE(splits <= 1 || (workspace && workspace_bytes >= need && aligned16(workspace)),
-               "conv backward-weight group: workspace of %zu bytes needed (jtsm_conv_bf16x3_wgrad_group_workspace_bytes)", need);
-  p.ktiles_per_split = ceil_div(ceil_div(p.K, XBK), splits);
+  JTSM_REQUIRE(splits <= 1 || (workspace && workspace_bytes >= pl.slab_bytes && aligned16(workspace)),
+               "conv backward-weight group: workspace of %zu bytes needed (jtsm_conv_bf16x3_wgrad_group_workspace_bytes)", pl.slab_bytes);
+  p.ktiles_per_split = pl.ktiles_per_split;
   p.slab = splits > 1 ? reinterpret_cast<float*>(workspace) : nullptr;
   p.tickets = nullptr;
-  const bool big = x3_wgrad_group_big(p, n);
-  const int tl = big ? 256 : 128;
-  const int ntiles = ceil_div(p.N, tl) * ceil_div(p.M, tl);
-  if (x3_wgrad_halo(p)) {
-    const int halo_tiles = ceil_div(p.M, 128) * (p.s.Cin / 32);
-    hipLaunchKernelGGL((igemm_x3_wgrad_halo_group_kernel<NP>), dim3(halo_tiles, splits, n), dim3(256), 0, st, p, G);
-  } else if (big) {
-    hipLaunchKernelGGL((igemm_x3_wgrad_group_kernel<4, 2, 2, 4, 2, NP>), dim3(ntiles, splits, n), dim3(512), 0, st, p, G);
-  } else {
-    hipLaunchKernelGGL((igemm_x3_wgrad_group_kernel<2, 2, 2, 2, 2, NP>), dim3(ntiles, splits, n), dim3(256), 0, st, p, G);
-  }
+  const dim3 grid(pl.ntiles, splits, n);
+  if (pl.halo)
+    hipLaunchKernelGGL((igemm_x3_wgrad_halo_group_kernel<NP>), grid, dim3(256), 0, st, p, G);
+  else if (pl.big)
+    hipLaunchKernelGGL((igemm_x3_wgrad_group_kernel<X3Tile256::wm, X3Tile256::wn, X3Tile256::tm, X3Tile256::tn, 2, NP>), grid,
+                       dim3(512), 0, st, p, G);
+  else
+    hipLaunchKernelGGL((igemm_x3_wgrad_group_kernel<X3Tile128::wm, X3Tile128::wn, X3Tile128::tm, X3Tile128::tn, 2, NP>), grid,
+                       dim3(256), 0, st, p, G);
   JTSM_CHECK_LAUNCH("igemm bf16x3 wgrad group");
   record_mid(st);
   if (splits > 1) {
@@ -2153,9 +2094,7 @@ extern "C" {
 size_t jtsm_conv_bf16x3_wgrad_group_workspace_bytes(const jtsm_conv_shape* s, int n) {
   if (!s || n < 1 || n > kMaxGroup) return 0;
   Params p = {};
-  if (group_shape(s, p) || p.K == 0) return 0;
-  const int splits = x3_wgrad_group_splits(p, n);
-  return splits > 1 ? (size_t)n * splits * p.M * p.N * sizeof(float) : 0;
+  return group_shape(s, p) ? 0 : plan_wgrad(p, true, n, false).slab_bytes;
 }
 
 int jtsm_conv_bf16x3_wgrad_group_plan(const jtsm_conv_shape* s, int n, int* tile, int* splits) {
@@ -2163,8 +2102,9 @@ int jtsm_conv_bf16x3_wgrad_group_plan(const jtsm_conv_shape* s, int n, int* tile
   Params p = {};
   int rc = group_shape(s, p);
   if (rc) return rc;
-  *tile = x3_wgrad_halo(p) ? 0 : (x3_wgrad_group_big(p, n) ? 256 : 128);
-  *splits = p.K > 0 ? x3_wgrad_group_splits(p, n) : 1;
+  const WgradPlan pl = plan_wgrad(p, true, n, false);
+  *tile = pl.halo ? 0 : (pl.big ? 256 : 128);
+  *splits = pl.splits;
   return JTSM_OK;
 }
 
@@ -2328,18 +2268,12 @@ int jtsm_conv2d_backward_data_ex_f16(const uint16_t* dy_h, const uint16_t* wt_h,
 // of the layer below, taken where its output gradient is written.  colsum: jtsm_conv_bf16x3_colsum_rows(s, role) x in_c
 // floats; the caller adds the rows up (jtsm_channel_sum_f32) in order.
 int jtsm_conv_bf16x3_colsum_rows(const jtsm_conv_shape* s, int role) {
-  if (check_shape(s) || (role != FWD && role != DGRAD)) return 0;
   Params p = {};
-  p.s = to_shape(s);
-  if (p.s.Ho <= 0 || p.s.Wo <= 0 || !x3_eligible(role, p.s)) return 0;
-  if (role == FWD) { p.M = p.s.Bn * p.s.Ho * p.s.Wo; p.N = p.s.Cout; p.K = p.s.KH * p.s.KW * p.s.Cin; }
-  else {
-    if (p.s.KH == 1 && p.s.KW == 1 && p.s.pad == 0 && p.s.stride > 1) return 0;   // (the scatter form)
-    p.M = p.s.Bn * p.s.H * p.s.W; p.N = p.s.Cin; p.K = p.s.KH * p.s.KW * p.s.Cout;
-  }
+  if ((role != FWD && role != DGRAD) || map_gemm(s, role, false, p) || !x3_eligible(role, p.s)) return 0;
+  if (role == DGRAD && strided_1x1(p.s)) return 0;   // (the scatter form)
   if (p.M <= 0 || p.N % 4) return 0;
-  const int c = x3_tile_choice(p);
-  return ceil_div(p.M, c == 0 ? 128 : (c == 3 ? 64 : 256));
+  const X3Plan pl = plan_x3(role, p, 0, true);   // (column sums: one row per row tile of the generic kernel)
+  return ceil_div(p.M, 32 * pl.wm * pl.tm);
 }
 int jtsm_conv2d_backward_data_colsum_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* wt_hi,
                                             const uint16_t* wt_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
@@ -2455,54 +2389,25 @@ int jtsm_split_bf16_multi_f32(const void* table, int entries, long blocks, int t
  * igemm_x3_kernel<role, WM, WN, TM, TN, NBUF> / igemm_x3_wgrad_kernel<WM, WN, TM, TN, NBUF> and the K slices. */
 int jtsm_conv_bf16x3_plan(const jtsm_conv_shape* s, int role, int* wm, int* wn, int* tm, int* tn, int* nbuf,
                           int* splits) {
-  int rc = check_shape(s);
-  if (rc) return rc;
   Params p = {};
-  p.s = to_shape(s);
-  JTSM_REQUIRE(p.s.Ho > 0 && p.s.Wo > 0, "conv: kernel larger than padded input");
+  int rc = map_gemm(s, role >= 0 && role <= 2 ? role : FWD, true, p);
+  if (rc) return rc;
   JTSM_REQUIRE(role >= 0 && role <= 2 && x3_eligible(role, p.s), "conv_bf16x3_plan: shape not eligible in this role");
-  int cfg[4] = {2, 2, 2, 2}, nb = 2, sp = 1;
-  if (role == WGRAD) {
-    p.M = p.s.Cout; p.N = p.s.KH * p.s.KW * p.s.Cin; p.K = p.s.Bn * p.s.Ho * p.s.Wo;
-    if (x3_wgrad_halo(p)) nb = 0;   // igemm_x3_wgrad_halo_kernel
-    else if (x3_wgrad_big(p)) { cfg[0] = 4; cfg[1] = 2; cfg[2] = 2; cfg[3] = 4; }
-    sp = p.K > 0 ? x3_wgrad_splits(p) : 1;
-  } else {
-    if (role == FWD) { p.M = p.s.Bn * p.s.Ho * p.s.Wo; p.N = p.s.Cout; p.K = p.s.KH * p.s.KW * p.s.Cin; }
-    else {
-      p.M = p.s.Bn * p.s.H * p.s.W; p.N = p.s.Cin; p.K = p.s.KH * p.s.KW * p.s.Cout;
-      if (p.s.KH == 1 && p.s.KW == 1 && p.s.pad == 0 && p.s.stride > 1) p.M = p.s.Bn * p.s.Ho * p.s.Wo;
-    }
-    const int c = x3_tile_choice(p);
-    if (c == 1) { cfg[0] = 4; cfg[1] = 1; }
-    if (c == 2) { cfg[0] = 4; cfg[1] = 2; cfg[2] = 2; cfg[3] = 4; }
-    if (c == 3 && !x3_halo_ok(role, p)) { cfg[2] = 1; cfg[3] = 1; }   // 64 x 64 (the halo kernels have their own shapes)
-    if (x3_halo_ok(role, p)) {   // reported as NBUF = 0: igemm_x3_halo_kernel<role, TH, WM, WN, TN, HP16>
-      const bool big = c == 2;
-      const int OH = role == FWD ? p.s.Ho : p.s.H, OW = role == FWD ? p.s.Wo : p.s.W;
-      const int ntiles = ceil_div(p.N, big ? 256 : 128) * p.s.Bn * ceil_div(OH, big ? 16 : 8) * ceil_div(OW, 16);
-      const int Cb = (role == FWD ? p.s.Cin : p.s.Cout) / XBK, round_blocks = big ? 256 : 512;
-      sp = ntiles >= round_blocks ? 1 : round_blocks / ntiles;
-      if (sp > Cb) sp = Cb;
-      if (sp > 16) sp = 16;
-      if (sp < 1) sp = 1;
-      sp = ceil_div(Cb, ceil_div(Cb, sp));
-      nb = 0;
-    } else {
-      sp = x3_wanted_splits(p);
-      const int ktiles = ceil_div(p.K, XBK);
-      const int kps = ceil_div(ktiles, sp);
-      sp = kps > 0 ? ceil_div(ktiles, kps) : 1;
-      if (c != 2 && ceil_div(ktiles, sp) <= x3_nbuf1_stages(role)) nb = 1;
-      else if (c == 3 && x3_ring_enabled() && ceil_div(ktiles, sp) >= 4) nb = 4;   // the four-stage ring
-    }
+  X3Plan pl = {};
+  if (role == WGRAD) {   // reported as NBUF = 0: igemm_x3_wgrad_halo_kernel
+    const WgradPlan w = plan_wgrad(p, false, 1, false);
+    x3_with_tile(w.big ? 2 : 0, [&](auto t) { pl.wm = t.wm; pl.wn = t.wn; pl.tm = t.tm; pl.tn = t.tn; });
+    pl.nbuf = w.halo ? 0 : 2;
+    pl.splits = w.splits;
+  } else {   // NBUF = 0: igemm_x3_halo_kernel<role, TH, WM, WN, TN, HP16>
+    pl = plan_x3(role, p, SIZE_MAX, false);
   }
-  if (wm) *wm = cfg[0];
-  if (wn) *wn = cfg[1];
-  if (tm) *tm = cfg[2];
-  if (tn) *tn = cfg[3];
-  if (nbuf) *nbuf = nb;
-  if (splits) *splits = sp;
+  if (wm) *wm = pl.wm;
+  if (wn) *wn = pl.wn;
+  if (tm) *tm = pl.tm;
+  if (tn) *tn = pl.tn;
+  if (nbuf) *nbuf = pl.nbuf;
+  if (splits) *splits = pl.splits;
   return JTSM_OK;
 }
 

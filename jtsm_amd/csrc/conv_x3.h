@@ -1278,51 +1278,6 @@ inline bool x3_ring_enabled() {
   return on;
 }
 
-// Launch one tile configuration, with its split-K plan.
-template <int ROLE, int WM, int WN, int TM, int TN, int NP>
-int launch_x3_cfg(Params& p, const X3Planes& q, void* workspace, size_t workspace_bytes, int round_blocks,
-                  hipStream_t st) {
-  constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN, NT = 64 * WM * WN;
-  const int ntiles = ceil_div(p.N, BN) * ceil_div(p.M, BM);
-  const int ktiles = ceil_div(p.K, XBK);
-  // aim at one full round of resident workgroups (measured: tools/sweeps/x3_sweep.py)
-  int splits = plan_splits(ntiles, ktiles, round_blocks);
-  if (splits > 1 && (size_t)splits * p.M * p.ldc * sizeof(float) > workspace_bytes) splits = 1;
-  if (p.colsum) splits = 1;   // (column sums are taken where the finished result is written: one K slice)
-  if (splits > 1) {
-    p.ktiles_per_split = ceil_div(ktiles, splits);
-    splits = ceil_div(ktiles, p.ktiles_per_split);
-    p.slab = reinterpret_cast<float*>(workspace);
-  }
-  p.wide = p.N % 4 == 0 && p.ldc % 4 == 0 && aligned16(p.C) && (splits <= 1 || aligned16(p.slab)) &&
-           (!p.e.residual || aligned16(p.e.residual)) && (!p.e.mask || aligned16(p.e.mask)) &&
-           (!p.e.scale || aligned16(p.e.scale)) && (!p.e.bias || aligned16(p.e.bias));
-  JTSM_REQUIRE(!p.out_hi || p.wide, "conv bf16x3: output planes requested but the tensors are not 16-byte aligned");
-  JTSM_REQUIRE((!p.mask_plane && !p.scale_rows && p.C && !p.colsum && !p.e.residual_h) || p.wide,
-               "conv bf16x3: a gate plane, a row scale, column sums, an fp16 residual plane or a planes-only result need N %% 4 == 0 and 16-byte aligned tensors");
-  const dim3 grid(ntiles, splits > 1 ? splits : 1);
-  const bool fused = use_fused_finish(p, ntiles, splits, st);
-  if (NT == 256 && ceil_div(ktiles, splits > 1 ? splits : 1) <= x3_nbuf1_stages(ROLE))
-    // A sweep of one or two stages is bound by its output / residual traffic, not by the matrix pipes: the
-    // single-buffered instantiation (32-40 KiB of LDS, three workgroups per CU) keeps more of it in flight.
-    // (Up to round 2 this was <= 4 stages at four workgroups per CU; with the pipelined epilogue the four-stage
-    // layers run faster double-buffered — 128 -> 512 channels at 128 x 128: 56 us against 65 us — sweeps:
-    // JTSM_X3_NBUF1_STAGES_FWD / _DGRAD.)
-    hipLaunchKernelGGL((igemm_x3_kernel<ROLE, WM, WN, TM, TN, 1, NP>), grid, dim3(NT), 0, st, p, q);
-  else if (BM == 64 && BN == 64 && x3_ring_enabled() && ceil_div(ktiles, splits > 1 ? splits : 1) >= 4)
-    // 64 x 64 tiles exist for the long-K 1x1 layers of res4 / res5 (16-64 stages per workgroup): a four-stage ring
-    // (64 KiB of LDS, still two workgroups per CU) keeps three stages of loads in flight.  JTSM_X3_RING=0: the
-    // double-buffered instantiation (sweeps).
-    hipLaunchKernelGGL((igemm_x3_kernel<ROLE, WM, WN, TM, TN, (BM == 64 && BN == 64) ? 4 : 2, NP>), grid, dim3(NT), 0, st,
-                       p, q);
-  else
-    hipLaunchKernelGGL((igemm_x3_kernel<ROLE, WM, WN, TM, TN, 2, NP>), grid, dim3(NT), 0, st, p, q);
-  JTSM_CHECK_LAUNCH("igemm bf16x3");
-  record_mid(st);
-  if (splits > 1 && !fused) return finish_split(p, splits, st);
-  return JTSM_OK;
-}
-
 // Tile choice.  0: 128x128 (4 waves), 1: 256x64 (4 waves, narrow outputs), 2: 256x256 (8 waves, large layers).
 inline int x3_tile_choice(const Params& p) {
   if (p.N <= 64) return 1;
@@ -1348,19 +1303,28 @@ inline int x3_tile_choice(const Params& p) {
   return 0;
 }
 
+// The <WM, WN, TM, TN> of a tile choice (BM = 32 WM TM, BN = 32 WN TN, 64 WM WN threads): `f` is called with the
+// X3Tile of `choice`.  The only place that pairs a choice with template arguments.
+template <int WM, int WN, int TM, int TN>
+struct X3Tile { static constexpr int wm = WM, wn = WN, tm = TM, tn = TN, bm = 32 * WM * TM, bn = 32 * WN * TN; };
+using X3Tile128 = X3Tile<2, 2, 2, 2>;
+using X3Tile256 = X3Tile<4, 2, 2, 4>;
+template <class F>
+inline auto x3_with_tile(int choice, F&& f) {
+  switch (choice) {
+    case 1: return f(X3Tile<4, 1, 2, 2>());
+    case 2: return f(X3Tile256());
+    case 3: return f(X3Tile<2, 2, 1, 1>());
+    default: return f(X3Tile128());
+  }
+}
+
 // Work-list length the 64 x 64 tiles' K slicing aims at (two workgroups per CU are resident: 512 per round).
 inline int x3_tile64_target() {
   // (1024 — two rounds — up to the ring: long K sweeps were latency bound then and more, shorter slices paid; with three
   // stages in flight one round of longer slices wins: half the slabs and finishing work.  Sweep: 25.14 -> 24.97 ms per step.)
   static const int v = [] { const char* e = getenv("JTSM_X3_TILE64_TARGET"); return e ? atoi(e) : 512; }();   // (sweeps)
   return v;
-}
-
-// K slices the launcher will want for this problem (before the workspace clamp).
-inline int x3_wanted_splits(const Params& p) {
-  const int c = x3_tile_choice(p);
-  const int bm = c == 0 ? 128 : (c == 3 ? 64 : 256), bn = c == 0 ? 128 : (c == 1 || c == 3 ? 64 : 256);
-  return plan_splits(ceil_div(p.N, bn) * ceil_div(p.M, bm), ceil_div(p.K, XBK), c == 2 ? 256 : (c == 3 ? x3_tile64_target() : 512));
 }
 
 // The halo kernel serves k x k (k > 1), stride-1, undilated layers whose contracted channels come in blocks of 32
@@ -1383,51 +1347,140 @@ inline bool x3_halo_ok(int role, const Params& p) {
          ((OH >= 32 && OW >= 32) || whole_image);
 }
 
-template <int ROLE, bool BIG, int NP>
-int launch_x3_halo(Params& p, const X3Planes& q, void* workspace, size_t workspace_bytes, hipStream_t st) {
+// The halo kernels' K slices (forward, data gradient and weight gradient): one round of resident workgroups, rounded
+// DOWN so that the launch never spills into a second round, at most `most` (what the contracted axis can feed) and `cap`.
+inline int halo_slices(int round_blocks, int ntiles, int most, int cap) {
+  int splits = ntiles >= round_blocks || ntiles <= 0 ? 1 : round_blocks / ntiles;   // (ntiles == 0: an empty batch)
+  if (splits > most) splits = most;
+  if (splits > cap) splits = cap;
+  return splits < 1 ? 1 : splits;
+}
+
+// Cut `units` (K stages, channel blocks, pixel segments) into at most `splits` equal slices: the slice length, and
+// `splits` lowered to the slices of that length that are not empty.
+inline int even_slices(int units, int& splits) {
+  const int per = ceil_div(units, splits);
+  splits = per > 0 ? ceil_div(units, per) : 1;
+  return per;
+}
+
+// What a forward / data-gradient launch (bf16x3 and f16) does: the ONLY place its tile, slice and buffer rules live.
+// launch_split_x3 launches from it; jtsm_conv_bf16x3_plan and jtsm_conv_workspace_bytes report from it.
+struct X3Plan {
+  bool halo;               // igemm_x3_halo_kernel (big: its 16-row x 256-column form), else igemm_x3_kernel
+  bool big;                // 256 x 256 tiles
+  int tile;                // x3_tile_choice (x3_with_tile); the halo kernels run as 0 or 2
+  int wm, wn, tm, tn;      // that tile's X3Tile
+  int nbuf;                // igemm_x3_kernel's LDS stages: 1, 2, or 4 (the ring); 0 for the halo kernels
+  int round_blocks;        // workgroups of one resident round, which the K slicing aims at
+  int ntiles;              // output tiles (grid.x)
+  int wanted;              // K slices wanted: what the scratch has to hold, splits * M * N floats
+  int splits;              // K slices launched (grid.y)
+  int ktiles_per_split;    // slice length: K stages, or 32-channel blocks (nine stages each) for the halo kernels
+};
+
+// workspace_bytes: the scratch at hand (a launch whose slabs do not fit runs unsplit).  generic_only: no halo kernel
+// (column sums are taken per row tile of the generic kernel, and only it reads an fp16 residual plane).
+inline X3Plan plan_x3(int role, const Params& p, size_t workspace_bytes, bool generic_only) {
+  X3Plan pl = {};
   const ConvShape& s = p.s;
-  constexpr int TH = BIG ? 16 : 8, BN = BIG ? 256 : 128;
-  const int OH = ROLE == FWD ? s.Ho : s.H, OW = ROLE == FWD ? s.Wo : s.W;
-  const int ntiles = ceil_div(p.N, BN) * s.Bn * ceil_div(OH, TH) * ceil_div(OW, 16);
-  const int Cb = (ROLE == FWD ? s.Cin : s.Cout) / XBK;
-  // split-K cuts whole channel blocks (nine stages each): aim at one round of resident workgroups
-  const int round_blocks = BIG ? 256 : 512;
-  int splits = ntiles >= round_blocks ? 1 : round_blocks / ntiles;
-  if (splits > Cb) splits = Cb;
-  if (splits > 16) splits = 16;
-  if (splits < 1) splits = 1;
-  if (splits > 1 && (size_t)splits * p.M * p.ldc * sizeof(float) > workspace_bytes) splits = 1;
-  if (splits > 1) {
-    p.ktiles_per_split = ceil_div(Cb, splits);
-    splits = ceil_div(Cb, p.ktiles_per_split);
+  const int choice = x3_tile_choice(p);
+  pl.halo = !generic_only && x3_halo_ok(role, p);
+  pl.big = choice == 2;
+  pl.tile = pl.halo ? (pl.big ? 2 : 0) : choice;
+  x3_with_tile(pl.tile, [&](auto t) { pl.wm = t.wm; pl.wn = t.wn; pl.tm = t.tm; pl.tn = t.tn; });
+  const int bm = 32 * pl.wm * pl.tm, bn = 32 * pl.wn * pl.tn;
+  int units;   // what the K slices are cut from
+  if (pl.halo) {
+    const int OH = role == FWD ? s.Ho : s.H, OW = role == FWD ? s.Wo : s.W;
+    pl.ntiles = ceil_div(p.N, bn) * s.Bn * ceil_div(OH, pl.big ? 16 : 8) * ceil_div(OW, 16);
+    // split-K cuts whole channel blocks (nine stages each): aim at one round of resident workgroups
+    units = (role == FWD ? s.Cin : s.Cout) / XBK;
+    pl.round_blocks = pl.big ? 256 : 512;
+    pl.wanted = halo_slices(pl.round_blocks, pl.ntiles, units, 16);
+  } else {
+    pl.ntiles = ceil_div(p.N, bn) * ceil_div(p.M, bm);
+    units = ceil_div(p.K, XBK);
+    // aim at one full round of resident workgroups (measured: tools/sweeps/x3_sweep.py)
+    pl.round_blocks = choice == 2 ? 256 : (choice == 3 ? x3_tile64_target() : 512);
+    pl.wanted = plan_splits(pl.ntiles, units, pl.round_blocks);
+  }
+  pl.splits = pl.wanted;
+  if (pl.splits > 1 && (size_t)pl.splits * p.M * p.N * sizeof(float) > workspace_bytes) pl.splits = 1;
+  if (p.colsum) pl.splits = 1;   // (column sums are taken where the finished result is written: one K slice)
+  pl.ktiles_per_split = even_slices(units, pl.splits);
+  if (pl.halo) pl.nbuf = 0;
+  // A sweep of one or two stages is bound by its output / residual traffic, not by the matrix pipes: the
+  // single-buffered instantiation (32-40 KiB of LDS, three workgroups per CU) of the four-wave kernels keeps more of it
+  // in flight.  (Up to round 2 this was <= 4 stages at four workgroups per CU; with the pipelined epilogue the
+  // four-stage layers run faster double-buffered — 128 -> 512 channels at 128 x 128: 56 us against 65 us — sweeps:
+  // JTSM_X3_NBUF1_STAGES_FWD / _DGRAD.)
+  else if (choice != 2 && pl.ktiles_per_split <= x3_nbuf1_stages(role)) pl.nbuf = 1;
+  // 64 x 64 tiles exist for the long-K 1x1 layers of res4 / res5 (16-64 stages per workgroup): a four-stage ring
+  // (64 KiB of LDS, still two workgroups per CU) keeps three stages of loads in flight.  JTSM_X3_RING=0: the
+  // double-buffered instantiation (sweeps).
+  else if (choice == 3 && x3_ring_enabled() && pl.ktiles_per_split >= 4) pl.nbuf = 4;
+  else pl.nbuf = 2;
+  return pl;
+}
+
+// What both launchers do once they hold the pointers: the slabs of a split launch, and whether every tensor allows the
+// wide (16-byte) epilogue.
+inline void x3_bind(Params& p, const X3Plan& pl, void* workspace) {
+  if (pl.splits > 1) {
+    p.ktiles_per_split = pl.ktiles_per_split;
     p.slab = reinterpret_cast<float*>(workspace);
   }
-  p.wide = p.N % 4 == 0 && p.ldc % 4 == 0 && aligned16(p.C) && (splits <= 1 || aligned16(p.slab)) &&
+  p.wide = p.N % 4 == 0 && p.ldc % 4 == 0 && aligned16(p.C) && (pl.splits <= 1 || aligned16(p.slab)) &&
            (!p.e.residual || aligned16(p.e.residual)) && (!p.e.mask || aligned16(p.e.mask)) &&
            (!p.e.scale || aligned16(p.e.scale)) && (!p.e.bias || aligned16(p.e.bias));
+}
+
+// Launch one tile configuration of the generic kernel.
+template <int ROLE, class T, int NP>
+int launch_x3_cfg(Params& p, const X3Planes& q, const X3Plan& pl, void* workspace, hipStream_t st) {
+  constexpr int WM = T::wm, WN = T::wn, TM = T::tm, TN = T::tn, NT = 64 * WM * WN;
+  x3_bind(p, pl, workspace);
+  JTSM_REQUIRE(!p.out_hi || p.wide, "conv bf16x3: output planes requested but the tensors are not 16-byte aligned");
+  JTSM_REQUIRE((!p.mask_plane && !p.scale_rows && p.C && !p.colsum && !p.e.residual_h) || p.wide,
+               "conv bf16x3: a gate plane, a row scale, column sums, an fp16 residual plane or a planes-only result need N %% 4 == 0 and 16-byte aligned tensors");
+  const dim3 grid(pl.ntiles, pl.splits);
+  const bool fused = use_fused_finish(p, pl.ntiles, pl.splits, st);
+  if (pl.nbuf == 1)
+    hipLaunchKernelGGL((igemm_x3_kernel<ROLE, WM, WN, TM, TN, 1, NP>), grid, dim3(NT), 0, st, p, q);
+  else if (pl.nbuf == 4)
+    hipLaunchKernelGGL((igemm_x3_kernel<ROLE, WM, WN, TM, TN, (T::bm == 64 && T::bn == 64) ? 4 : 2, NP>), grid, dim3(NT), 0, st,
+                       p, q);
+  else
+    hipLaunchKernelGGL((igemm_x3_kernel<ROLE, WM, WN, TM, TN, 2, NP>), grid, dim3(NT), 0, st, p, q);
+  JTSM_CHECK_LAUNCH("igemm bf16x3");
+  record_mid(st);
+  if (pl.splits > 1 && !fused) return finish_split(p, pl.splits, st);
+  return JTSM_OK;
+}
+
+template <int ROLE, bool BIG, int NP>
+int launch_x3_halo(Params& p, const X3Planes& q, const X3Plan& pl, void* workspace, hipStream_t st) {
+  x3_bind(p, pl, workspace);
   JTSM_REQUIRE(!p.out_hi || p.wide, "conv bf16x3: output planes requested but the tensors are not 16-byte aligned");
   JTSM_REQUIRE((!p.mask_plane && !p.scale_rows && p.C) || p.wide,
                "conv bf16x3: a gate plane, a row scale or a planes-only result needs N %% 4 == 0 and 16-byte aligned tensors");
-  const dim3 grid(ntiles, splits > 1 ? splits : 1);
-  const bool fused = use_fused_finish(p, ntiles, splits, st);
+  const dim3 grid(pl.ntiles, pl.splits);
+  const bool fused = use_fused_finish(p, pl.ntiles, pl.splits, st);
   if (BIG) hipLaunchKernelGGL((igemm_x3_halo_kernel<ROLE, 16, 4, 2, 4, 21, NP>), grid, dim3(512), 0, st, p, q);
   else hipLaunchKernelGGL((igemm_x3_halo_kernel<ROLE, 8, 2, 2, 2, 12, NP>), grid, dim3(256), 0, st, p, q);
   JTSM_CHECK_LAUNCH("igemm bf16x3 halo");
   record_mid(st);
-  if (splits > 1 && !fused) return finish_split(p, splits, st);
+  if (pl.splits > 1 && !fused) return finish_split(p, pl.splits, st);
   return JTSM_OK;
 }
 
 template <int ROLE, int NP = 2>
 int launch_split_x3(Params& p, const X3Planes& q, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (!p.colsum && !p.e.residual_h && x3_halo_ok(ROLE, p)) {   // (column sums: the generic kernel's row tiles; so is the fp16 residual plane)
-    if (x3_tile_choice(p) == 2) return launch_x3_halo<ROLE, true, NP>(p, q, workspace, workspace_bytes, st);
-    return launch_x3_halo<ROLE, false, NP>(p, q, workspace, workspace_bytes, st);
+  const X3Plan pl = plan_x3(ROLE, p, workspace_bytes, p.colsum || p.e.residual_h);
+  if (pl.halo) {
+    if (pl.big) return launch_x3_halo<ROLE, true, NP>(p, q, pl, workspace, st);
+    return launch_x3_halo<ROLE, false, NP>(p, q, pl, workspace, st);
   }
-  switch (x3_tile_choice(p)) {
-    case 1: return launch_x3_cfg<ROLE, 4, 1, 2, 2, NP>(p, q, workspace, workspace_bytes, 512, st);
-    case 2: return launch_x3_cfg<ROLE, 4, 2, 2, 4, NP>(p, q, workspace, workspace_bytes, 256, st);
-    case 3: return launch_x3_cfg<ROLE, 2, 2, 1, 1, NP>(p, q, workspace, workspace_bytes, x3_tile64_target(), st);
-    default: return launch_x3_cfg<ROLE, 2, 2, 2, 2, NP>(p, q, workspace, workspace_bytes, 512, st);
-  }
+  return x3_with_tile(pl.tile, [&](auto t) { return launch_x3_cfg<ROLE, decltype(t), NP>(p, q, pl, workspace, st); });
 }

@@ -18,6 +18,11 @@ Sources of truth
     the keep list depends only on the greedy visiting order and the suppress rule, which is what it pins.
   * moi_pool_oracle.npz: MOIPool has no runnable reference -> vectors come from
     our restatement (oracle/c/pool_ops.inc); "parity unpinned", they pin regressions only.
+  * conv_plan_table.npz: what the library's host-side planning queries answer (tests/test_capi.py:
+    conv_plan_answers) for baseline_conv_shapes.json (the plan cache of layers/conv.py after BASELINE configs[2] and
+    configs[4] steps on the GPU), the convolution tests' shapes and a grid around the rule boundaries.  Needs only the
+    built library: `python tests/golden/make_golden.py conv_plan_table`.  It pins the rules as they are; re-record it
+    in the pull request that changes one on purpose.
   * roi_align_fresh_ref.json: SHA-256 digests of the REFERENCE's compiled ROIAlign / ROIAlignRotated results on the
     seeded inputs of tests/test_oracle_pooling.py: fresh_calls().
 """
@@ -180,5 +185,51 @@ def fresh_reference_digests(ref):
         f.write("\n")
 
 
+def conv_plan_grid(batches=(0, 1, 2, 64), maps=(7, 14, 16, 31, 32, 33, 64, 128, 256),
+                   channels=(8, 64, 72, 192, 256, 320, 512, 1024, 2048)):
+    """Shapes around the planning rules' boundaries, as jtsm_conv_shape field tuples.  (An empty batch only on maps
+    below 32 x 32: on the maps the 3x3 halo kernels take, the library as first recorded divided by its tile count.)"""
+    return [(b, m, m, ci, co, k, k, st, dil * (k - 1) // 2, dil)
+            for b in batches for m in maps if b > 0 or m < 32 for ci in channels for co in channels
+            for k in (1, 2, 3, 7) for st in (1, 2) for dil in (1, 2)]
+
+
+def conv_plan_shapes(keep=2400):
+    import json
+
+    from test_hip_conv import CASES
+
+    with open(os.path.join(HERE, "baseline_conv_shapes.json")) as f:
+        named = [tuple(s) for rows in json.load(f).values() for s in rows]
+    named += [(b, h, w, ci, co, k, k, st, pad, dil) for _, b, ci, h, w, co, k, st, pad, dil in CASES]
+    # tests/test_hip_conv.py: test_full_size_adjointness; tests/test_capi.py
+    named += [(b, h, w, ci, co, k, k, st, pad, 1) for b, ci, h, w, co, k, st, pad in (
+        (2, 256, 256, 256, 256, 3, 1, 1), (2, 1024, 64, 64, 256, 1, 1, 0), (2, 256, 64, 64, 256, 3, 1, 1),
+        (2, 512, 128, 128, 1024, 1, 2, 0), (4000, 12544, 1, 1, 2048, 1, 1, 0), (300, 256, 14, 14, 256, 3, 1, 1),
+        (0, 256, 14, 14, 256, 1, 1, 0), (0, 256, 14, 14, 256, 3, 1, 1), (0, 256, 14, 14, 256, 1, 2, 0),
+        (0, 256, 14, 14, 256, 2, 2, 0), (2, 512, 32, 32, 512, 3, 1, 1), (1, 3, 8, 8, 8, 1, 1, 0),
+        (2, 2048, 32, 32, 512, 1, 1, 0), (2, 1024, 16, 16, 256, 1, 1, 0), (1, 352, 20, 20, 128, 1, 1, 0),
+        (1, 64, 12, 12, 128, 3, 1, 1), (2, 256, 256, 256, 256, 1, 1, 0))]
+    named += [(1, 7, 7, 64, 64, 7, 7, 1, 0, 2), (2, 16, 16, 64, 64, 3, 3, 1, 0, 1)]   # no output pixel; unpadded 3x3
+    grid = conv_plan_grid()
+    rng = np.random.default_rng(20261016)
+    grid = [grid[i] for i in sorted(rng.choice(len(grid), keep, replace=False))]
+    return sorted(set(named)) + grid
+
+
+def conv_plan_table():
+    sys.path.insert(0, os.path.dirname(HERE))
+    from jtsm_amd import _lib
+    from test_capi import CONV_PLAN_TABLE, conv_plan_answers
+
+    shapes = np.array(conv_plan_shapes(), dtype=np.int64)
+    answers = np.array([conv_plan_answers(_lib.lib(), s) for s in shapes], dtype=np.int64)
+    np.savez_compressed(CONV_PLAN_TABLE, shapes=shapes, answers=answers)
+    print(CONV_PLAN_TABLE, shapes.shape, answers.shape, os.path.getsize(CONV_PLAN_TABLE))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["conv_plan_table"]:
+        conv_plan_table()
+    else:
+        main()

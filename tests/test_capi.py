@@ -120,6 +120,69 @@ def test_bf16x3_plan_reports_the_ring_for_long_k_64_tiles():
     assert plan((2, 256, 256, 256, 256, 1, 1, 1, 0, 1), 0)[:5] == (2, 2, 2, 2, 2)
 
 
+# Group sizes the weight-gradient group queries are recorded at (8 = kMaxGroup, csrc/conv_x3.h).
+PLAN_GROUP_SIZES = (1, 2, 3, 6, 8)
+CONV_PLAN_TABLE = os.path.join(ROOT, "tests", "golden", "conv_plan_table.npz")
+
+
+def conv_plan_answers(lib, shape):
+    """Everything the host-side planning and workspace queries say about one jtsm_conv_shape, as a flat list of
+    integers (output arguments a failing call leaves alone read -1): jtsm_conv_plan for roles 0-2 x has_kscale 0/1,
+    jtsm_conv_bf16x3_plan for roles 0-2, the weight-gradient group plan and workspace for PLAN_GROUP_SIZES, the four
+    single-layer workspace sizes, jtsm_conv_bf16x3_colsum_rows and jtsm_conv_bf16x3_eligible."""
+    from jtsm_amd.layers.conv import ConvShape
+
+    ref = C.byref(ConvShape(*[int(v) for v in shape]))
+    row = []
+
+    def outs(n):
+        o = [C.c_int(-1) for _ in range(n)]
+        return o, [C.byref(x) for x in o]
+
+    for role in (0, 1, 2):
+        for has_kscale in (0, 1):
+            o, (k, tm, tn, sp) = outs(4)
+            row.append(lib.jtsm_conv_plan(ref, role, has_kscale, k, tm, tn, sp))
+            row.extend(x.value for x in o)
+    for role in (0, 1, 2):
+        o, (wm, wn, tm, tn, nbuf, sp) = outs(6)
+        row.append(lib.jtsm_conv_bf16x3_plan(ref, role, wm, wn, tm, tn, nbuf, sp))
+        row.extend(x.value for x in o)
+    for n in PLAN_GROUP_SIZES:
+        o, (tile, sp) = outs(2)
+        row.append(lib.jtsm_conv_bf16x3_wgrad_group_plan(ref, n, tile, sp))
+        row.extend(x.value for x in o)
+        row.append(lib.jtsm_conv_bf16x3_wgrad_group_workspace_bytes(ref, n))
+    row += [lib.jtsm_conv_workspace_bytes(ref, 0), lib.jtsm_conv_workspace_bytes(ref, 1),
+            lib.jtsm_conv_bf16x3_wgrad_workspace_bytes(ref), lib.jtsm_conv_bf16x3_wgrad_bias_workspace_bytes(ref)]
+    row += [lib.jtsm_conv_bf16x3_colsum_rows(ref, role) for role in (0, 1)]
+    row += [lib.jtsm_conv_bf16x3_eligible(ref, role) for role in (0, 1, 2)]
+    return row
+
+
+def test_conv_planning_answers_match_the_recorded_table():
+    """tests/golden/conv_plan_table.npz (tests/golden/make_golden.py: conv_plan_table) holds, for every convolution /
+    linear shape of the BASELINE configs[2] and configs[4] steps, the shapes of the convolution tests and a grid around
+    the rule boundaries, what the planning queries answered when the table was recorded.  The launchers read the same
+    plan functions ("One plan per contraction launch"), so any change of a tile, slice or buffer rule shows
+    here, per field.  Recorded and replayed with no JTSM_* variable set."""
+    import numpy as np
+
+    from jtsm_amd import _lib
+
+    knobs = sorted(k for k in os.environ if k.startswith(("JTSM_X3_", "JTSM_WGRAD_")))   # (what the rules read)
+    assert not knobs, "the table holds the default rules; unset %s" % knobs
+    lib = _lib.lib()
+    table = np.load(CONV_PLAN_TABLE)
+    shapes, want = table["shapes"], table["answers"]
+    assert shapes.shape[0] == want.shape[0] >= 2000 and shapes.shape[1] == 10
+    got = np.array([conv_plan_answers(lib, s) for s in shapes], dtype=np.int64)
+    assert got.shape == want.shape
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, "%d differing fields; first: shape %s column %d: got %d, recorded %d" % (
+        len(bad), shapes[bad[0][0]].tolist(), bad[0][1], got[tuple(bad[0])], want[tuple(bad[0])])
+
+
 def test_integration_doc_maps_every_declared_symbol():
     """INTEGRATION.md's symbol <-> reference-interface table names every entry point include/jtsm_hip.h declares
     (brace lists and trailing-* families expanded)."""
