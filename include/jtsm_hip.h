@@ -166,6 +166,25 @@ int jtsm_roi_loop_pool_backward_f32(const float* grad, const float* rois, const 
                                     float* grad_input, void* workspace, int B, int C, int H, int W, int R,
                                     float spatial_scale, int pooled_h, int pooled_w, void* stream);
 /* ---------------------------------------------------------------------------
+ * ROIPool — replaces torchvision.ops.RoIPool(output_size, spatial_scale)(input, rois) as
+ * projects/WSL/wsl/modeling/poolers.py:6,183-186 builds and calls it (PCL's POOLER_TYPE "ROIPool";
+ * contract spelled out in jtsm_amd/csrc/roi_pool.hip).
+ * rois (R,5); output / argmax (R,C,PH,PW) in `layout`.  Integer rectangle roundf(coord * scale);
+ * bins [floor(p*bin), ceil((p+1)*bin)) + start with bin = max(end-start+1, 1) / P, clipped to the
+ * map; an empty bin gives 0 / -1, otherwise the first cell (h outer, w inner) holding the maximum.
+ * argmax holds the flat h*W+w of the winning cell.
+ * The backward is NHWC only (grad, argmax, grad_input channels-last) and writes every element of
+ * grad_input; it is a gather in a fixed order, so repeated calls give the same bits.
+ * workspace: jtsm_roi_pool_backward_workspace_bytes(R) bytes, 16-byte aligned.
+ * ------------------------------------------------------------------------- */
+int jtsm_roi_pool_forward_f32(const float* input, const float* rois, float* output, int32_t* argmax,
+                              int B, int C, int H, int W, int R, float spatial_scale, int pooled_h,
+                              int pooled_w, int layout, void* stream);
+size_t jtsm_roi_pool_backward_workspace_bytes(int R);
+int jtsm_roi_pool_backward_f32(const float* grad, const float* rois, const int32_t* argmax,
+                               float* grad_input, void* workspace, int B, int C, int H, int W, int R,
+                               float spatial_scale, int pooled_h, int pooled_w, void* stream);
+/* ---------------------------------------------------------------------------
  * fp16 tensors at the pooling boundary.  The reference dispatches MOIPool on half too
  * (AT_DISPATCH_FLOATING_TYPES_AND_HALF, projects/WSL/wsl/layers/csrc/MOIPool/MOIPool_cuda.cu:400,415,484) and its
  * Python layers hand half tensors to the align operators (detectron2/layers/roi_align_rotated.py:79-85: up-cast,
@@ -623,6 +642,44 @@ int jtsm_oicr_backward_f32(const float* cls_logits, int ld_cls, int num_cls, con
                            const float* proposals, const float* gt_boxes, int R, const float* losses,
                            const float* up_cls, const float* up_box, float* d_cls, int ld_dcls,
                            float* d_box, int ld_dbox, void* stream);
+
+
+/* ---------------------------------------------------------------------------
+ * PCL — proposal clustering and the PCL loss of one refinement branch, for all images at once.
+ * Replaces PCL() (projects/WSL/wsl/modeling/roi_heads/third_party/pcl.py:24-200: numpy and
+ * scikit-learn on the host) and pcl_loss_forward / pcl_loss_backward
+ * (projects/WSL/wsl/layers/csrc/pcl_loss/pcl_loss.h:9-131; the CPU kernels pcl_loss_cpu.cpp:8-115
+ * are the ones wsl/layers/pcl_loss.py:9-93 reaches).  Contract spelled out in jtsm_amd/csrc/pcl.hip;
+ * k-means is a declared deterministic substitution.
+ * Rows of image i are [offsets[i], offsets[i+1]); max_rows bounds the rows of one image (<= 8192).
+ * boxes (R,4) xyxy, 16-byte aligned.  prev_probs: the previous branch's probabilities, class c in
+ * column prev_col0 + c.  labels (nimg,K) float 0/1.  probs (R,K+1): this branch's soft-max,
+ * background in column 0.  Outputs: row_label (R) in [0,K] (0 = background), row_assign (R)
+ * cluster index or -1, row_weight (R); per image 5K cluster slots: pc_int (nimg,5K,3) =
+ * (label, member count, centre row), pc_flt (nimg,5K,3) = (centre score, summed member weight,
+ * pc_prob); pc_num (nimg) clusters used.  No float atomics: the same inputs give the same tables.
+ * ------------------------------------------------------------------------- */
+size_t jtsm_pcl_cluster_workspace_bytes(int nimg, int max_rows);
+int jtsm_pcl_cluster_f32(const float* boxes, const int32_t* offsets, int nimg, int max_rows, int total_rows,
+                         const float* prev_probs, int ld_prev, int prev_col0, const float* labels,
+                         int num_classes, const float* probs, int ld_probs, int32_t* row_label,
+                         int32_t* row_assign, float* row_weight, int32_t* pc_int, float* pc_flt,
+                         int32_t* pc_num, void* workspace, void* stream);
+/* probs (R,num_cls) dense = softmax over the num_cls columns of logits (leading dimension ld). */
+int jtsm_pcl_softmax_f32(const float* logits, int ld, int num_cls, int R, float* probs, void* stream);
+size_t jtsm_pcl_loss_workspace_bytes(int nimg);
+/* loss[0] = mean over the images of (background term + cluster term) / rows of the image. */
+int jtsm_pcl_loss_forward_f32(const float* probs, int ld_probs, const int32_t* offsets, int nimg,
+                              int num_classes, const int32_t* row_label, const float* row_weight,
+                              const int32_t* pc_int, const float* pc_flt, const int32_t* pc_num,
+                              float* loss, void* workspace, void* stream);
+/* d_logits (R,K+1) with leading dimension ld_grad = upstream[0] * dloss/dlogits (upstream NULL = 1;
+ * the reference ignores the upstream gradient, pcl_loss.py:55-90), soft-max backward included. */
+int jtsm_pcl_loss_backward_f32(const float* logits, int ld, int num_classes, const int32_t* offsets,
+                               int nimg, int total_rows, const int32_t* row_label,
+                               const int32_t* row_assign, const float* row_weight, const int32_t* pc_int,
+                               const float* pc_flt, const float* upstream, float* d_logits, int ld_grad,
+                               void* stream);
 
 
 /* Mask targets of rectangle pseudo ground truth (get_pgt_mask, roi_heads_jtsm.py:1928-1994, with the rectangle

@@ -5,5 +5,6 @@ from .moi_pool import MOIPool, moi_pool
 from .roi_align import ROIAlign, roi_align
 from .roi_align_rotated import ROIAlignRotated, roi_align_rotated
 from .roi_loop_pool import ROILoopPool, roi_loop_pool
+from .roi_pool import ROIPool, roi_pool
 
 __all__ = [k for k in globals().keys() if not k.startswith("_")]

@@ -27,6 +27,7 @@ from ..layers.moi_pool import MOIPool
 from ..layers.roi_align import ROIAlign
 from ..layers.roi_align_rotated import ROIAlignRotated
 from ..layers.roi_loop_pool import ROILoopPool
+from ..layers.roi_pool import ROIPool
 from ..layers.wrappers import cat
 
 CL = torch.channels_last
@@ -242,6 +243,8 @@ class ROIPooler(nn.Module):
             self.level_poolers = nn.ModuleList(MOIPool(output_size, spatial_scale=s) for s in scales)
         elif pooler_type == "ROILoopPool":   # wsl/modeling/poolers.py:191-194: (3 x boxes) rows out
             self.level_poolers = nn.ModuleList(ROILoopPool(output_size, spatial_scale=s) for s in scales)
+        elif pooler_type == "ROIPool":       # wsl/modeling/poolers.py:183-186: torchvision's RoIPool per level
+            self.level_poolers = nn.ModuleList(ROIPool(output_size, spatial_scale=s) for s in scales)
         elif pooler_type == "ROIAlignRotated":
             self.level_poolers = nn.ModuleList(
                 ROIAlignRotated(output_size, spatial_scale=s, sampling_ratio=sampling_ratio) for s in scales)
@@ -274,6 +277,8 @@ class ROIPooler(nn.Module):
             return torch.zeros((0, x[0].shape[1]) + self.output_size, device=x[0].device, dtype=x[0].dtype)
         if self.pooler_type == "ROILoopPool":
             return self._loop_pool(x, box_lists, level_ids)
+        if self.pooler_type == "ROIPool":
+            return self._loop_pool(x, box_lists, level_ids, blocks=1)
         # rois and levels in one launch (layers/mining.py: pooler_rois_levels) when the boxes are float32 on the device;
         # the tensor-op helpers above stay as the definition it is tested against and serve every other case
         fused = (level_ids is None and len(box_lists) <= MAX_IMAGES and
@@ -306,9 +311,10 @@ class ROIPooler(nn.Module):
         mode = "rotated" if self.pooler_type == "ROIAlignRotated" else self.pooler_type == "ROIAlignV2"
         return _AlignLevels.apply(rois, roi_level, self.output_size[0], self.sampling_ratio, mode, self.scales, fans, *x)
 
-    def _loop_pool(self, x, box_lists, level_ids):
+    def _loop_pool(self, x, box_lists, level_ids, blocks=3):
         """ROILoopPool (wsl/modeling/poolers.py:306-335): (3N, C, P, P) for N boxes; with several levels every level
-        pools its own boxes and row i of a level's output goes to rows i, i + N, i + 2N of the result."""
+        pools its own boxes and row i of a level's output goes to rows i, i + N, i + 2N of the result.  ROIPool
+        (blocks=1, :286-305): the same with one block of N rows."""
         rois = convert_boxes_to_pooler_format(box_lists)
         if len(self.level_poolers) == 1:
             return self.level_poolers[0](x[0], rois)
@@ -319,9 +325,9 @@ class ROIPooler(nn.Module):
                                                        self.canonical_box_size, self.canonical_level)
         n = rois.shape[0]
         fmt = CL if L.is_nhwc(x[0]) else torch.contiguous_format
-        output = torch.zeros((3 * n, x[0].shape[1]) + self.output_size, dtype=x[0].dtype,
+        output = torch.zeros((blocks * n, x[0].shape[1]) + self.output_size, dtype=x[0].dtype,
                              device=x[0].device).contiguous(memory_format=fmt)
         for level, pooler in enumerate(self.level_poolers):
             inds = torch.nonzero(level_assignments == level, as_tuple=True)[0]
-            output[cat([inds, inds + n, inds + 2 * n], dim=0)] = pooler(x[level], rois[inds])
+            output[cat([inds + k * n for k in range(blocks)], dim=0)] = pooler(x[level], rois[inds])
         return output

@@ -1,5 +1,5 @@
 """OICROutputLayers — surface of projects/WSL/wsl/modeling/roi_heads/fast_rcnn_oicr.py:448-586 (layers,
-losses), :684-783 (predict_probs / predict_boxes and their K-head averages), :616-646 (inference) and the
+losses), :589-614 (losses_pcl: PCLOutputs.pcl_loss :917-936 on the device, layers/pcl.py), :684-783 (predict_probs / predict_boxes and their K-head averages), :616-646 (inference) and the
 module-level fast_rcnn_inference / fast_rcnn_inference_single_image (:48-163).  `cls_score: Linear(in, K+1)`,
 `bbox_pred: Linear(in, 4K)`; losses = instance-weighted CE and L1 (jtsm_amd/csrc/wsl_losses.hip); inference =
 one fused predict launch + one per-image detection call (jtsm_amd/csrc/postprocess.hip)."""
@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ...layers.pcl import pcl_loss
 from ...layers.postprocess import fast_rcnn_inference_device, oicr_predict
 from ...layers.wrappers import Linear, cat
 from ...layers.wsl_losses import oicr_loss
@@ -154,15 +155,39 @@ class OICROutputLayers(nn.Module):
             out["loss_box_reg" + k] = lb * self.loss_weight.get("loss_box_reg", 1.0)
         return out
 
+    def losses_pcl(self, predictions, proposals, last_scores, gt_classes_img_oh, offsets=None):
+        """{"loss_cls_r<k>": PCL loss} of this branch (fast_rcnn_oicr.py:589-614): the proposals are clustered from
+        `last_scores` — the previous branch's probabilities, (R, K) or (R, K+1) with the background first — and the
+        loss reads this branch's logits, background in column 0.  Everything runs on the device; the branch's own
+        soft-max and the cluster tables stay in `self.pcl_probs` / `self.pcl_tables` (the next branch clusters from
+        the former).  B images: the mean of the per-image losses (B = 1 is the reference, pcl.py:90).
+        offsets: int32 (B+1,) device tensor of the images' first rows, built here when not given."""
+        if self.has_reg:
+            raise NotImplementedError("losses_pcl: the regression variant (WSL.REFINE_REG) is not implemented — the "
+                                      "reference's PCLOutputs has no weights for it (fast_rcnn_oicr.py:938-1003)")
+        scores = predictions[0]
+        counts = [len(p) for p in proposals]
+        boxes = cat([p.proposal_boxes.tensor for p in proposals], dim=0)
+        assert not boxes.requires_grad, "Proposals should not require gradients!"
+        if offsets is None:
+            offsets = torch.tensor([0] + list(torch.tensor(counts).cumsum(0)), dtype=torch.int32).to(
+                scores.device, non_blocking=True)
+        loss, self.pcl_probs, self.pcl_tables = pcl_loss(scores, boxes, offsets, max(max(counts), 1),
+                                                         last_scores.detach(), gt_classes_img_oh)
+        key = "loss_cls_r" + str(self.refine_k)
+        return {key: loss * self.loss_weight.get(key, 1.0)}
+
     def predict_probs(self, predictions, counts):
         return F.softmax(predictions[0], dim=-1).split(counts, dim=0)
 
     def predict_boxes(self, predictions, proposal_boxes, counts):
         return self.box2box_transform.apply_deltas(predictions[1], proposal_boxes).split(counts)
 
-    def inference(self, predictions, proposals: List[Instances]):
+    def inference(self, predictions, proposals: List[Instances], pcl_bg=False):
         """`predictions`: (logits, deltas) of this head, or a list of such pairs — then probabilities and deltas
-        are averaged over the heads (predict_probs_K / predict_boxes_K).  Returns what fast_rcnn_inference does."""
+        are averaged over the heads (predict_probs_K / predict_boxes_K).  Returns what fast_rcnn_inference does.
+        pcl_bg: the heads were trained with the background in column 0 (PCL); it is moved behind the classes before
+        the detections are selected (:635-637)."""
         heads = list(predictions) if isinstance(predictions[0], (tuple, list)) else [predictions]
         if not len(proposals):
             return [], [], [], []
@@ -170,5 +195,7 @@ class OICROutputLayers(nn.Module):
         prop = torch.cat([p.proposal_boxes.tensor for p in proposals], dim=0)
         probs, boxes = oicr_predict([h[0] for h in heads], [h[1] for h in heads], prop,
                                     self.box2box_transform.weights, self.box2box_transform.scale_clamp)
+        if pcl_bg:
+            probs = torch.cat((probs[:, 1:], probs[:, :1]), dim=1)
         return fast_rcnn_inference(boxes.split(counts), probs.split(counts), [x.image_size for x in proposals],
                                    self.test_score_thresh, self.test_nms_thresh, self.test_topk_per_image)
