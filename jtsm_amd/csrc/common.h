@@ -37,6 +37,11 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
+// The fp16 operand-plane word of v * 2^shift (DESIGN.md "Operand planes").  ldexp, not a multiply: a multiply in front
+// of the conversion is folded into v_fma_mix{lo,hi}_f16 (v * s + 0) on SOME lanes of an unrolled group, and -0 + 0 is
+// +0 — the plane of a stored -0 then depended on the element's position (tests/test_hip_planes.py).
+__device__ __forceinline__ _Float16 f16_plane(float v, int shift) { return (_Float16)__builtin_ldexpf(v, shift); }
+
 // ordered compaction of a per-thread flag over the 256 threads of the workgroup: returns this thread's slot (if
 // flagged) and the total; two barriers.
 __device__ __forceinline__ int compact256(bool flag, int* __restrict__ wave_count, int& total) {

@@ -300,17 +300,17 @@ __device__ __forceinline__ void store_tile(const Params& p, f32x16 (&acc)[TM][TN
 }
 
 // hi/lo bf16 planes of four finished outputs (what jtsm_split_bf16_f32 would produce from them); with lo == null,
-// one fp16 plane of v * 2^shift (what jtsm_split_f16_f32 would produce).
+// one fp16 plane of v * 2^shift (what jtsm_split_f16_f32 would produce).  Pinned word for word against the fp32 result
+// of the same launch by tests/test_hip_planes.py (test_contraction_epilogue_planes).
 __device__ __forceinline__ void emit_planes4(unsigned short* hi, unsigned short* lo, size_t o, const float4& v,
                                              int shift = 0) {
   typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
   const float x[4] = {v.x, v.y, v.z, v.w};
   if (!lo) {
     typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-    const float sc = pow2i(shift);
     f16x4_t h;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) h[e] = (_Float16)(x[e] * sc);
+    for (int e = 0; e < 4; ++e) h[e] = f16_plane(x[e], shift);
     *reinterpret_cast<f16x4_t*>(hi + o) = h;
     return;
   }

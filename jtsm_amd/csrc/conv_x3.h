@@ -1123,18 +1123,17 @@ __global__ __launch_bounds__(256) void split_bf16_paired_kernel(const float* __r
 __global__ __launch_bounds__(256) void split_f16_kernel(const float* __restrict__ src, _Float16* __restrict__ h, long n,
                                                         int shift) {
   const long n8 = n >> 3;
-  const float sc = pow2i(shift);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
     const float4 a = reinterpret_cast<const float4*>(src)[2 * i], b = reinterpret_cast<const float4*>(src)[2 * i + 1];
     const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     f16x8 o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (_Float16)(v[e] * sc);
+    for (int e = 0; e < 8; ++e) o[e] = f16_plane(v[e], shift);
     reinterpret_cast<f16x8*>(h)[i] = o;
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
     const long i = (n8 << 3) + threadIdx.x;
-    h[i] = (_Float16)(src[i] * sc);
+    h[i] = f16_plane(src[i], shift);
   }
 }
 

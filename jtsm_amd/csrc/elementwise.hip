@@ -48,7 +48,6 @@ typedef _Float16 ew_f16x8 __attribute__((ext_vector_type(8)));
 __global__ __launch_bounds__(256) void relu_bwd_split_f16_kernel(const float4* __restrict__ dy, const float4* __restrict__ y,
                                                                  float4* __restrict__ g, ew_f16x8* __restrict__ h, long n8,
                                                                  int shift) {
-  const float sc = __int_as_float((127 + shift) << 23);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
     const float4 a0 = dy[2 * i], a1 = dy[2 * i + 1], b0 = y[2 * i], b1 = y[2 * i + 1];
     const float v[8] = {b0.x > 0.f ? a0.x : 0.f, b0.y > 0.f ? a0.y : 0.f, b0.z > 0.f ? a0.z : 0.f, b0.w > 0.f ? a0.w : 0.f,
@@ -57,7 +56,7 @@ __global__ __launch_bounds__(256) void relu_bwd_split_f16_kernel(const float4* _
     g[2 * i + 1] = make_float4(v[4], v[5], v[6], v[7]);
     ew_f16x8 o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (_Float16)(v[e] * sc);
+    for (int e = 0; e < 8; ++e) o[e] = f16_plane(v[e], shift);
     h[i] = o;
   }
 }
@@ -97,7 +96,6 @@ __global__ __launch_bounds__(256) void planes_pass_kernel(const PassArgs q) {
   const float4* __restrict__ a = reinterpret_cast<const float4*>(q.a);
   const float4* __restrict__ b = reinterpret_cast<const float4*>(q.b);
   float4* __restrict__ out = reinterpret_cast<float4*>(q.out);
-  const float sh = __int_as_float((127 + q.shift) << 23);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < q.n8; i += (long)gridDim.x * blockDim.x) {
     const float4 a0 = a[2 * i], a1 = a[2 * i + 1];
     float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -133,7 +131,7 @@ __global__ __launch_bounds__(256) void planes_pass_kernel(const PassArgs q) {
     } else {
       ew_f16x8 o;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (_Float16)(v[e] * sh);
+      for (int e = 0; e < 8; ++e) o[e] = f16_plane(v[e], q.shift);
       reinterpret_cast<ew_f16x8*>(q.hi)[i] = o;
     }
   }
@@ -386,7 +384,8 @@ __global__ __launch_bounds__(256) void maxpool3s2_bwd(const float* __restrict__ 
 
 // out = lateral + nearest_upsample_x2(top)      (FPN top-down path, fpn.py:133-136)
 typedef __bf16 ew_bf16x4 __attribute__((ext_vector_type(4)));
-// bf16 hi / lo planes of four values (what jtsm_split_bf16_f32 makes of them), for a bf16x3 consumer
+// bf16 hi / lo planes of four values (what jtsm_split_bf16_f32 makes of them: pinned word for word by
+// tests/test_hip_planes.py, upsample2_add / sum_tensors), for a bf16x3 consumer
 __device__ __forceinline__ void ew_planes4(unsigned short* hi, unsigned short* lo, long i4, const float4& v) {
   const float x[4] = {v.x, v.y, v.z, v.w};
   ew_bf16x4 h, l;

@@ -74,7 +74,8 @@ __global__ void gn_fold_kernel(const float2* __restrict__ part, float* __restric
   rstd[n * G + g] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
-// bf16 hi / lo planes of four values (what jtsm_split_bf16_f32 would make of them), for a bf16x3 consumer
+// bf16 hi / lo planes of four values (what jtsm_split_bf16_f32 would make of them: pinned word for word by
+// tests/test_hip_planes.py, upsample_bilinear2x / group_norm backward), for a bf16x3 consumer
 typedef __bf16 ss_bf16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void put_planes4(unsigned short* hi, unsigned short* lo, long i4, const float4& v) {
   const float x[4] = {v.x, v.y, v.z, v.w};
