@@ -643,6 +643,19 @@ int jtsm_oicr_backward_f32(const float* cls_logits, int ld_cls, int num_cls, con
                            const float* up_cls, const float* up_box, float* d_cls, int ld_dcls,
                            float* d_box, int ld_dbox, void* stream);
 
+/* The same two with detectron2's smooth_l1_loss(beta) (MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA) in the box term: per
+ * component n = |d - t|, 0.5 n^2 / beta where n < beta, n - 0.5 beta elsewhere; beta < 1e-5 is L1 and computes exactly
+ * what jtsm_oicr_forward_f32 / jtsm_oicr_backward_f32 compute.  Same workspace. */
+int jtsm_oicr_smooth_forward_f32(const float* cls_logits, int ld_cls, int num_cls, const float* box_deltas,
+                                 int ld_box, const int32_t* labels, const float* weights,
+                                 const float* proposals, const float* gt_boxes, int R, float beta,
+                                 float* losses, void* workspace, void* stream);
+int jtsm_oicr_smooth_backward_f32(const float* cls_logits, int ld_cls, int num_cls, const float* box_deltas,
+                                  int ld_box, const int32_t* labels, const float* weights,
+                                  const float* proposals, const float* gt_boxes, int R, float beta,
+                                  const float* losses, const float* up_cls, const float* up_box, float* d_cls,
+                                  int ld_dcls, float* d_box, int ld_dbox, void* stream);
+
 
 /* ---------------------------------------------------------------------------
  * PCL — proposal clustering and the PCL loss of one refinement branch, for all images at once.
@@ -898,6 +911,31 @@ int jtsm_match_label_f32(const float* proposals, const int32_t* bag_offsets, int
                          const float* pgt_weight, const float* pgt_score, int Gmax, float iou_thresh,
                          int bg_label, int32_t* labels, int32_t* matched, float* gt_boxes,
                          float* gt_weights, float* gt_scores, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * MIST mining (projects/WSL/wsl/modeling/roi_heads/roi_heads_oicr.py:550-591 get_pgt_mist on get_pgt_top_k :660-811
+ * with top_k = top_pro < 1): per image, the top_t[b] rows of every present class by class score, one class-agnostic
+ * greedy NMS over all of them, the survivors as a padded pseudo-ground-truth list.  Nothing is read back.
+ * Operands as jtsm_mine_top1_f32 takes them (score = scores[r,c], or exp(scores[r,c] - lse[r]) when lse != NULL;
+ * deltas != NULL: the class's box decoded as mine_top1 decodes it; deltas == NULL and decode_zero_deltas != 0: the
+ * proposal decoded with zero deltas, which is what the reference computes for a branch without regression and differs
+ * from the proposal in the last bit; otherwise the proposal row itself).  top_t (B) int32 on the device, host-computed
+ * max(int(rows_b * top_pro), 1); t_max >= every top_t[b] (larger entries are cut to t_max, and to the image's rows).
+ * Candidate (j, g) — the class slot g's j-th best row, equal scores by lower row — has list index j * counts[b] + g;
+ * the NMS visits the list by descending score, equal scores by lower list index, and drops a candidate whose IoU with
+ * an earlier survivor is > iou_thresh (the IoU expression of jtsm_batched_nms_f32).  Outputs, P = t_max * G entries
+ * per image, survivors in visiting order and zeros behind them: out_boxes (B,P,4), out_classes (B,P), out_scores
+ * (B,P), out_weights (B,P) = the scores (:584-586), out_rows (B,P) = the source row within the image, out_num (B).
+ * An image with counts[b] == 0 gets out_num[b] = 0.  The list feeds jtsm_match_label_f32 with Gmax = P, counts =
+ * out_num.  Deterministic: no atomics.  out_boxes 16-byte, workspace 256-byte aligned.
+ * ------------------------------------------------------------------------- */
+size_t jtsm_mine_top_p_workspace_bytes(int B, int G, int t_max);
+int jtsm_mine_top_p_f32(const float* scores, int ld, const float* lse, const float* proposals,
+                        const float* deltas, int ld_deltas, int decode_zero_deltas,
+                        const int32_t* bag_offsets, const int32_t* classes, const int32_t* counts,
+                        const int32_t* top_t, int B, int G, int t_max, float iou_thresh, float* out_boxes,
+                        int32_t* out_classes, float* out_scores, float* out_weights, int32_t* out_rows,
+                        int32_t* out_num, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Inference / post-processing.  None of these entry points synchronises with the host: counts

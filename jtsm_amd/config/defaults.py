@@ -60,7 +60,11 @@ _DEFAULTS = {
 _WSL_DEFAULTS = {
     "WSL": {"VIS_TEST": False, "ITER_SIZE": 1, "MEAN_LOSS": True, "SIZE_EPOCH": 5000, "CMIL": False, "USE_OBN": True,
             "REFINE_NUM": 3, "REFINE_REG": [False, False, False], "HAS_GAM": False, "REFINE_MIST": False,
-            "CLS_AGNOSTIC_BBOX_KNOWN": False, "SAMPLING": {"SAMPLING_ON": False}, "CASCADE_ON": False, "PS_ON": False,
+            "CLS_AGNOSTIC_BBOX_KNOWN": False,
+            "SAMPLING": {"SAMPLING_ON": False, "IOU_THRESHOLDS": [[0.5], [0.5], [0.5], [0.5]],
+                         "IOU_LABELS": [[0, 1], [0, 1], [0, 1], [0, 1]],
+                         "BATCH_SIZE_PER_IMAGE": [4096, 4096, 4096, 4096], "POSITIVE_FRACTION": [1.0, 1.0, 1.0, 1.0]},
+            "CASCADE_ON": False, "PS_ON": False,
             "SP_ON": False, "MASK_MINED_TOP_K": 10},
     "MODEL": {"ROI_BOX_HEAD": {"DAN_DIM": [4096, 4096]},
               "SEM_SEG_HEAD": {"MASK_SOFTMAX": False, "CONSTRAINT": False}},

@@ -13,6 +13,7 @@
 // reference's operation order.
 #include <cfloat>
 
+#include "box_math.h"
 #include "common.h"
 
 namespace jtsm {
@@ -36,22 +37,6 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ 
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o);
   if (lane == 0) lse[r] = mx + logf(sm);
-}
-
-__device__ __forceinline__ void decode_box(const float* __restrict__ p, const float* __restrict__ d, float* out) {
-#pragma clang fp contract(off)
-  // Box2BoxTransform(10,10,5,5).apply_deltas for one (box, class) pair
-  const float w = p[2] - p[0], h = p[3] - p[1];
-  const float cx = p[0] + 0.5f * w, cy = p[1] + 0.5f * h;
-  const float dx = d[0] / 10.f, dy = d[1] / 10.f;
-  const float kClamp = 4.135166556742356f;  // log(1000/16)
-  const float dw = fminf(d[2] / 5.f, kClamp), dh = fminf(d[3] / 5.f, kClamp);
-  const float pcx = dx * w + cx, pcy = dy * h + cy;
-  const float pw = expf(dw) * w, ph = expf(dh) * h;
-  out[0] = pcx - 0.5f * pw;
-  out[1] = pcy - 0.5f * ph;
-  out[2] = pcx + 0.5f * pw;
-  out[3] = pcy + 0.5f * ph;
 }
 
 // One workgroup per (image, class slot): arg-max over the image's proposals of the class score

@@ -3,6 +3,7 @@
 // semantic logits, and the panoptic merge.  HBM-bound integer / byte work: one pass over the data per stage,
 // coalesced rows, LDS only for the 64-box column tiles of the NMS bit matrix; no host synchronisation anywhere
 // (data-dependent counts stay in device memory until the caller asks for them).
+#include "box_math.h"
 #include "common.h"
 
 #include <hipcub/hipcub.hpp>
@@ -198,18 +199,6 @@ __global__ void nms_segments_kernel(const u64* __restrict__ keys, int N, int K, 
     if ((int)(keys[mid] >> 32) < c) lo = mid + 1; else hi = mid;
   }
   seg[c] = lo;
-}
-
-// torchvision's nms IoU test (ops/csrc/cuda/nms_cuda.cu devIoU @0.8.1; the CPU kernel computes the same expression)
-__device__ __forceinline__ bool iou_above(const float4& a, const float4& b, float thr) {
-#pragma clang fp contract(off)
-  const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z);
-  const float top = fmaxf(a.y, b.y), bottom = fminf(a.w, b.w);
-  const float width = fmaxf(right - left, 0.f), height = fmaxf(bottom - top, 0.f);
-  const float inter = width * height;
-  const float sa = (a.z - a.x) * (a.w - a.y);
-  const float sb = (b.z - b.x) * (b.w - b.y);
-  return (inter / (sa + sb - inter)) > thr;
 }
 
 // trick: 0 plain per-class, 1 torchvision's coordinate offsets, 2 offsets iff fewer than 40000 valid elements

@@ -316,12 +316,20 @@ __device__ __forceinline__ void box_target(const float* __restrict__ pb, const f
   t[3] = 5.f * logf(th / sh);
 }
 
+// detectron2's smooth_l1_loss of one component (fvcore/nn/smooth_l1_loss.py): 0.5 n^2 / beta below beta, n - 0.5 beta
+// from there on.  SMOOTH = false is the beta < 1e-5 form, plain L1.
+__device__ __forceinline__ float smooth_l1(float diff, float beta) {
+  const float n = fabsf(diff);
+  return n < beta ? 0.5f * n * n / beta : n - 0.5f * beta;
+}
+
+template <bool SMOOTH>
 __global__ __launch_bounds__(256) void oicr_forward(const float* __restrict__ Zl, int ldz, int ncls,
                                                     const float* __restrict__ Dl, int ldd,
                                                     const int* __restrict__ labels,
                                                     const float* __restrict__ weights,
                                                     const float* __restrict__ prop, const float* __restrict__ gt,
-                                                    int R, float* __restrict__ partials) {
+                                                    int R, float beta, float* __restrict__ partials) {
   __shared__ float red[WAVES][3];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   float ce = 0.f, nv = 0.f, l1 = 0.f;
@@ -347,7 +355,11 @@ __global__ __launch_bounds__(256) void oicr_forward(const float* __restrict__ Zl
       float t[4];
       box_target(prop + 4 * (size_t)r, gt + 4 * (size_t)r, t);
       const float* dr = Dl + (size_t)r * ldd + 4 * y;
-      l1 += w * (fabsf(dr[0] - t[0]) + fabsf(dr[1] - t[1]) + fabsf(dr[2] - t[2]) + fabsf(dr[3] - t[3]));
+      if constexpr (SMOOTH)
+        l1 += w * (smooth_l1(dr[0] - t[0], beta) + smooth_l1(dr[1] - t[1], beta) + smooth_l1(dr[2] - t[2], beta) +
+                   smooth_l1(dr[3] - t[3], beta));
+      else
+        l1 += w * (fabsf(dr[0] - t[0]) + fabsf(dr[1] - t[1]) + fabsf(dr[2] - t[2]) + fabsf(dr[3] - t[3]));
     }
   }
   if (lane == 0) { red[wv][0] = ce; red[wv][1] = nv; red[wv][2] = l1; }
@@ -377,13 +389,15 @@ __global__ void oicr_finish(const float* __restrict__ partials, int nblocks, int
 }
 
 // dZ[r,c] = up_cls * w_r / V * (softmax(z_r)[c] - [c == y_r]);
-// dDl[r, 4y+j] = up_box * w_r / R * sign(d - t), every other column of the row 0.
+// dDl[r, 4y+j] = up_box * w_r / R * sign(d - t) (SMOOTH: (d - t) / beta where |d - t| < beta), every other column of
+// the row 0.
+template <bool SMOOTH>
 __global__ __launch_bounds__(256) void oicr_backward(const float* __restrict__ Zl, int ldz, int ncls,
                                                      const float* __restrict__ Dl, int ldd, int nbox,
                                                      const int* __restrict__ labels,
                                                      const float* __restrict__ weights,
                                                      const float* __restrict__ prop, const float* __restrict__ gt,
-                                                     int R, const float* __restrict__ fin,
+                                                     int R, float beta, const float* __restrict__ fin,
                                                      const float* __restrict__ up_cls, const float* __restrict__ up_box,
                                                      float* __restrict__ dZ, int ldgz, float* __restrict__ dDl, int ldgd) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -418,7 +432,10 @@ __global__ __launch_bounds__(256) void oicr_backward(const float* __restrict__ Z
         float t[4];
         box_target(prop + 4 * (size_t)r, gt + 4 * (size_t)r, t);
         const float diff = Dl[(size_t)r * ldd + 4 * y + lane] - t[lane];
-        drow[4 * y + lane] = ub * w * (diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f));
+        if constexpr (SMOOTH)
+          drow[4 * y + lane] = ub * w * (fabsf(diff) < beta ? diff / beta : (diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f)));
+        else
+          drow[4 * y + lane] = ub * w * (diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f));
       }
     }
   }
@@ -583,22 +600,61 @@ int jtsm_mil_backward_f32(const float* cls_logits, const float* det_logits, int 
 
 size_t jtsm_oicr_workspace_bytes(void) { return (OICR_BLOCKS * 3 + 4) * sizeof(float); }
 
-int jtsm_oicr_forward_f32(const float* cls_logits, int ld_cls, int num_cls, const float* box_deltas, int ld_box,
-                          const int32_t* labels, const float* weights, const float* proposals,
-                          const float* gt_boxes, int R, float* losses, void* workspace, void* stream) {
+namespace {
+constexpr float kSmoothL1MinBeta = 1e-5f;   // below it smooth_l1_loss is L1
+
+int oicr_forward_impl(const float* cls_logits, int ld_cls, int num_cls, const float* box_deltas, int ld_box,
+                      const int32_t* labels, const float* weights, const float* proposals, const float* gt_boxes, int R,
+                      float beta, float* losses, void* workspace, void* stream) {
   JTSM_REQUIRE(num_cls > 1 && num_cls <= 64 * SLOTS && R >= 0 && ld_cls >= num_cls, "oicr: bad sizes");
   JTSM_REQUIRE(cls_logits && labels && weights && losses && workspace, "oicr: null pointer");
   JTSM_REQUIRE(!box_deltas || (proposals && gt_boxes && ld_box >= 4 * (num_cls - 1)), "oicr: box branch needs boxes");
+  JTSM_REQUIRE(beta >= 0.f, "oicr: smooth-L1 beta must not be negative, got %g", (double)beta);
   float* part = (float*)workspace;
   hipStream_t st = as_stream(stream);
   int blocks = (R + WAVES - 1) / WAVES;
   if (blocks > OICR_BLOCKS) blocks = OICR_BLOCKS;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(oicr_forward, dim3(blocks), dim3(256), 0, st, cls_logits, ld_cls, num_cls, box_deltas,
-                     ld_box, labels, weights, proposals, gt_boxes, R, part);
+  if (beta < kSmoothL1MinBeta)
+    hipLaunchKernelGGL(oicr_forward<false>, dim3(blocks), dim3(256), 0, st, cls_logits, ld_cls, num_cls, box_deltas,
+                       ld_box, labels, weights, proposals, gt_boxes, R, 0.f, part);
+  else
+    hipLaunchKernelGGL(oicr_forward<true>, dim3(blocks), dim3(256), 0, st, cls_logits, ld_cls, num_cls, box_deltas,
+                       ld_box, labels, weights, proposals, gt_boxes, R, beta, part);
   hipLaunchKernelGGL(oicr_finish, dim3(1), dim3(64), 0, st, part, blocks, R, losses);
   JTSM_CHECK_LAUNCH("oicr forward");
   return JTSM_OK;
+}
+
+int oicr_backward_impl(const float* cls_logits, int ld_cls, int num_cls, const float* box_deltas, int ld_box,
+                       const int32_t* labels, const float* weights, const float* proposals, const float* gt_boxes, int R,
+                       float beta, const float* losses, const float* up_cls, const float* up_box, float* d_cls,
+                       int ld_dcls, float* d_box, int ld_dbox, void* stream) {
+  JTSM_REQUIRE(num_cls > 1 && num_cls <= 64 * SLOTS && R >= 0, "oicr backward: bad sizes");
+  if (R == 0) return JTSM_OK;
+  JTSM_REQUIRE(cls_logits && labels && weights && losses && d_cls, "oicr backward: null pointer");
+  JTSM_REQUIRE(!d_box || (box_deltas && proposals && gt_boxes), "oicr backward: box branch needs boxes");
+  JTSM_REQUIRE(beta >= 0.f, "oicr backward: smooth-L1 beta must not be negative, got %g", (double)beta);
+  int blocks = (R + WAVES - 1) / WAVES;
+  if (blocks > 2048) blocks = 2048;
+  if (beta < kSmoothL1MinBeta)
+    hipLaunchKernelGGL(oicr_backward<false>, dim3(blocks), dim3(256), 0, as_stream(stream), cls_logits, ld_cls, num_cls,
+                       box_deltas, ld_box, 4 * (num_cls - 1), labels, weights, proposals, gt_boxes, R, 0.f, losses,
+                       up_cls, up_box, d_cls, ld_dcls, d_box, ld_dbox);
+  else
+    hipLaunchKernelGGL(oicr_backward<true>, dim3(blocks), dim3(256), 0, as_stream(stream), cls_logits, ld_cls, num_cls,
+                       box_deltas, ld_box, 4 * (num_cls - 1), labels, weights, proposals, gt_boxes, R, beta, losses,
+                       up_cls, up_box, d_cls, ld_dcls, d_box, ld_dbox);
+  JTSM_CHECK_LAUNCH("oicr backward");
+  return JTSM_OK;
+}
+}  // namespace
+
+int jtsm_oicr_forward_f32(const float* cls_logits, int ld_cls, int num_cls, const float* box_deltas, int ld_box,
+                          const int32_t* labels, const float* weights, const float* proposals,
+                          const float* gt_boxes, int R, float* losses, void* workspace, void* stream) {
+  return oicr_forward_impl(cls_logits, ld_cls, num_cls, box_deltas, ld_box, labels, weights, proposals, gt_boxes, R, 0.f,
+                           losses, workspace, stream);
 }
 
 int jtsm_oicr_backward_f32(const float* cls_logits, int ld_cls, int num_cls, const float* box_deltas, int ld_box,
@@ -606,17 +662,25 @@ int jtsm_oicr_backward_f32(const float* cls_logits, int ld_cls, int num_cls, con
                            const float* gt_boxes, int R, const float* losses, const float* up_cls,
                            const float* up_box, float* d_cls, int ld_dcls, float* d_box, int ld_dbox,
                            void* stream) {
-  JTSM_REQUIRE(num_cls > 1 && num_cls <= 64 * SLOTS && R >= 0, "oicr backward: bad sizes");
-  if (R == 0) return JTSM_OK;
-  JTSM_REQUIRE(cls_logits && labels && weights && losses && d_cls, "oicr backward: null pointer");
-  JTSM_REQUIRE(!d_box || (box_deltas && proposals && gt_boxes), "oicr backward: box branch needs boxes");
-  int blocks = (R + WAVES - 1) / WAVES;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(oicr_backward, dim3(blocks), dim3(256), 0, as_stream(stream), cls_logits, ld_cls, num_cls,
-                     box_deltas, ld_box, 4 * (num_cls - 1), labels, weights, proposals, gt_boxes, R, losses,
-                     up_cls, up_box, d_cls, ld_dcls, d_box, ld_dbox);
-  JTSM_CHECK_LAUNCH("oicr backward");
-  return JTSM_OK;
+  return oicr_backward_impl(cls_logits, ld_cls, num_cls, box_deltas, ld_box, labels, weights, proposals, gt_boxes, R, 0.f,
+                            losses, up_cls, up_box, d_cls, ld_dcls, d_box, ld_dbox, stream);
+}
+
+int jtsm_oicr_smooth_forward_f32(const float* cls_logits, int ld_cls, int num_cls, const float* box_deltas, int ld_box,
+                                 const int32_t* labels, const float* weights, const float* proposals,
+                                 const float* gt_boxes, int R, float beta, float* losses, void* workspace,
+                                 void* stream) {
+  return oicr_forward_impl(cls_logits, ld_cls, num_cls, box_deltas, ld_box, labels, weights, proposals, gt_boxes, R, beta,
+                           losses, workspace, stream);
+}
+
+int jtsm_oicr_smooth_backward_f32(const float* cls_logits, int ld_cls, int num_cls, const float* box_deltas, int ld_box,
+                                  const int32_t* labels, const float* weights, const float* proposals,
+                                  const float* gt_boxes, int R, float beta, const float* losses, const float* up_cls,
+                                  const float* up_box, float* d_cls, int ld_dcls, float* d_box, int ld_dbox,
+                                  void* stream) {
+  return oicr_backward_impl(cls_logits, ld_cls, num_cls, box_deltas, ld_box, labels, weights, proposals, gt_boxes, R,
+                            beta, losses, up_cls, up_box, d_cls, ld_dcls, d_box, ld_dbox, stream);
 }
 
 #define MASK_BCE_BLOCKS 256

@@ -635,7 +635,10 @@ def fc_stack_fused(x2d, fcs, row_scale=None, p=0.0, tail=None):
         return _FcStackFn.apply(x2d, row_scale, float(p), seeds, None, None, *params)[0]
     weights, biases = list(tail[0]), list(tail[1])
     sizes = [w.shape[0] for w in weights]
-    pad = (-sum(sizes)) % 4                      # (16-byte rows: as layers/conv.py linear_fused_split pads)
+    # whole 8-channel chunks: the tail's weight gradient contracts over planes of these columns (x3_eligible's
+    # weight-gradient rule); 16-byte fp32 rows, which layers/conv.py linear_fused_split pads to, follow.  OICR's four
+    # regressing branches make 20 + 20 + 4 * (21 + 80) = 444 columns: a multiple of 4 and not of 8.
+    pad = (-sum(sizes)) % 8
     if pad:
         weights.append(weights[0].new_zeros((pad, weights[0].shape[1])))
         biases.append(biases[0].new_zeros(pad))

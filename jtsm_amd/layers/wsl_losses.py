@@ -3,7 +3,8 @@
 mil_loss      <- TSMOutputLayers.forward + TSMOutputs.binary_cross_entropy_loss
                  (projects/WSL/wsl/modeling/roi_heads/fast_rcnn_tsm.py:548-598,346-379)
 oicr_loss     <- OICROutputs.softmax_cross_entropy_loss + box_reg_loss("smooth_l1_weighted")
-                 (projects/WSL/wsl/modeling/roi_heads/fast_rcnn_oicr.py:282-298,350-380)
+                 (projects/WSL/wsl/modeling/roi_heads/fast_rcnn_oicr.py:282-298,350-380), with
+                 MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA as `beta`
 """
 import torch
 from torch.autograd import Function
@@ -120,7 +121,7 @@ def mil_scores(cls_logits, det_logits, counts):
 
 class _OICRLoss(Function):
     @staticmethod
-    def forward(ctx, cls_logits, box_deltas, labels, weights, proposals, gt_boxes):
+    def forward(ctx, cls_logits, box_deltas, labels, weights, proposals, gt_boxes, beta=None):
         L.require_gpu(cls_logits, labels, weights)
         z, ldz = _rowmajor(cls_logits)
         R, ncls = z.shape
@@ -134,34 +135,48 @@ class _OICRLoss(Function):
         weights = weights.to(torch.float32).contiguous()
         out = torch.empty(4, dtype=torch.float32, device=z.device)
         ws = torch.empty(L.lib().jtsm_oicr_workspace_bytes(), dtype=torch.uint8, device=z.device)
-        L.check(L.lib().jtsm_oicr_forward_f32(L.ptr(z), ldz, ncls, L.ptr(dl), ldd, L.ptr(labels), L.ptr(weights),
-                                              L.ptr(proposals if has_box else None),
-                                              L.ptr(gt_boxes if has_box else None), R, L.ptr(out), L.ptr(ws),
-                                              L.stream()), "oicr_forward")
+        if beta is None:
+            L.check(L.lib().jtsm_oicr_forward_f32(L.ptr(z), ldz, ncls, L.ptr(dl), ldd, L.ptr(labels), L.ptr(weights),
+                                                  L.ptr(proposals if has_box else None),
+                                                  L.ptr(gt_boxes if has_box else None), R, L.ptr(out), L.ptr(ws),
+                                                  L.stream()), "oicr_forward")
+        else:
+            L.check(L.lib().jtsm_oicr_smooth_forward_f32(L.ptr(z), ldz, ncls, L.ptr(dl), ldd, L.ptr(labels),
+                                                         L.ptr(weights), L.ptr(proposals if has_box else None),
+                                                         L.ptr(gt_boxes if has_box else None), R, float(beta),
+                                                         L.ptr(out), L.ptr(ws), L.stream()), "oicr_smooth_forward")
         ctx.save_for_backward(z, dl, labels, weights, proposals if has_box else None,
                               gt_boxes if has_box else None, out)
-        ctx.cfg = (ldz, ncls, ldd, R, has_box)
+        ctx.cfg = (ldz, ncls, ldd, R, has_box, beta)
         return out[0], out[1]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_cls, g_box):
         z, dl, labels, weights, proposals, gt_boxes, out = ctx.saved_tensors
-        ldz, ncls, ldd, R, has_box = ctx.cfg
+        ldz, ncls, ldd, R, has_box, beta = ctx.cfg
         dz = torch.empty((R, ncls), dtype=torch.float32, device=z.device)
         dd = torch.empty((R, 4 * (ncls - 1)), dtype=torch.float32, device=z.device) if has_box else None
         gc = g_cls.to(torch.float32).contiguous()
         gb = g_box.to(torch.float32).contiguous() if has_box else None
-        L.check(L.lib().jtsm_oicr_backward_f32(
-            L.ptr(z), ldz, ncls, L.ptr(dl), ldd, L.ptr(labels), L.ptr(weights), L.ptr(proposals), L.ptr(gt_boxes),
-            R, L.ptr(out), L.ptr(gc), L.ptr(gb), L.ptr(dz), ncls, L.ptr(dd), 4 * (ncls - 1), L.stream()),
-            "oicr_backward")
-        return dz, dd, None, None, None, None
+        if beta is None:
+            L.check(L.lib().jtsm_oicr_backward_f32(
+                L.ptr(z), ldz, ncls, L.ptr(dl), ldd, L.ptr(labels), L.ptr(weights), L.ptr(proposals), L.ptr(gt_boxes),
+                R, L.ptr(out), L.ptr(gc), L.ptr(gb), L.ptr(dz), ncls, L.ptr(dd), 4 * (ncls - 1), L.stream()),
+                "oicr_backward")
+        else:
+            L.check(L.lib().jtsm_oicr_smooth_backward_f32(
+                L.ptr(z), ldz, ncls, L.ptr(dl), ldd, L.ptr(labels), L.ptr(weights), L.ptr(proposals), L.ptr(gt_boxes),
+                R, float(beta), L.ptr(out), L.ptr(gc), L.ptr(gb), L.ptr(dz), ncls, L.ptr(dd), 4 * (ncls - 1),
+                L.stream()), "oicr_smooth_backward")
+        return dz, dd, None, None, None, None, None
 
 
-def oicr_loss(cls_logits, box_deltas, labels, weights, proposals=None, gt_boxes=None):
-    """(loss_cls, loss_box_reg) of one refinement branch.  box_deltas may be None."""
-    return _OICRLoss.apply(cls_logits, box_deltas, labels, weights, proposals, gt_boxes)
+def oicr_loss(cls_logits, box_deltas, labels, weights, proposals=None, gt_boxes=None, beta=None):
+    """(loss_cls, loss_box_reg) of one refinement branch.  box_deltas may be None.  beta: the smooth-L1 transition
+    point of the box term (detectron2's smooth_l1_loss; below 1e-5 it is L1); None is the L1 form through the
+    original entry points, whose bits beta = 0 reproduces."""
+    return _OICRLoss.apply(cls_logits, box_deltas, labels, weights, proposals, gt_boxes, beta)
 
 
 class _MaskBCE(torch.autograd.Function):

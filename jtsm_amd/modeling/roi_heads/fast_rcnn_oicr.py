@@ -84,8 +84,9 @@ def fast_rcnn_inference_single_image(boxes, scores, image_shape: Tuple[int, int]
 
 class OICROutputLayers(nn.Module):
     def __init__(self, input_size, *, num_classes, box2box_transform, refine_k, refine_reg, loss_weight=1.0,
-                 test_score_thresh=0.0, test_nms_thresh=0.5, test_topk_per_image=100):
+                 test_score_thresh=0.0, test_nms_thresh=0.5, test_topk_per_image=100, smooth_l1_beta=0.0):
         super().__init__()
+        self.smooth_l1_beta = float(smooth_l1_beta)
         self.test_score_thresh = test_score_thresh
         self.test_nms_thresh = test_nms_thresh
         self.test_topk_per_image = test_topk_per_image
@@ -111,7 +112,8 @@ class OICROutputLayers(nn.Module):
                    loss_weight={"loss_box_reg": cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT},
                    test_score_thresh=cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST,
                    test_nms_thresh=cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST,
-                   test_topk_per_image=cfg.TEST.DETECTIONS_PER_IMAGE)
+                   test_topk_per_image=cfg.TEST.DETECTIONS_PER_IMAGE,
+                   smooth_l1_beta=cfg.MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA)
 
     @property
     def has_reg(self):
@@ -147,8 +149,9 @@ class OICROutputLayers(nn.Module):
             gt_weights = cat([p.gt_weights for p in proposals], dim=0)
         else:
             proposal_boxes = proposals
+        beta = {"beta": self.smooth_l1_beta} if self.smooth_l1_beta > 0 else {}     # (0: the L1 entry points)
         lc, lb = oicr_loss(scores, deltas if self.has_reg else None, gt_classes, gt_weights,
-                           proposal_boxes if self.has_reg else None, gt_boxes if self.has_reg else None)
+                           proposal_boxes if self.has_reg else None, gt_boxes if self.has_reg else None, **beta)
         k = "_r" + str(self.refine_k)
         out = {"loss_cls" + k: lc}
         if self.has_reg:

@@ -114,6 +114,8 @@ class JTSMROIHeads(ROIHeads):
         self.refine_K = cfg.WSL.REFINE_NUM
         self.refine_reg = cfg.WSL.REFINE_REG
         self.cls_agnostic_bbox_reg = cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG
+        # (the reference's own JTSM head cannot run MIST: roi_heads_jtsm.py:1039-1049 calls get_pgt_top_k without the two
+        # positional arguments that :1168-1181 requires; OICRROIHeads has it)
         assert not self.cls_agnostic_bbox_reg and not cfg.WSL.REFINE_MIST
 
         # ---- box branch (roi_heads_jtsm.py:347-404)
