@@ -29,9 +29,7 @@
 // finds the (roi, block, bin) triples whose bin holds the cell from the integer geometry alone (precomputed per roi
 // by a small kernel) and adds the gradients whose argmax names the cell.  Every cell is written once, no atomics: two
 // calls on the same inputs give the same bits.
-#include <algorithm>
-
-#include "common.h"
+#include "pool_bins.h"
 
 namespace jtsm {
 namespace {
@@ -39,8 +37,6 @@ namespace {
 #pragma clang fp contract(off)
 
 constexpr float kContextRatio = 1.8f;   // ROILoopPool_cuda.cu:309 (a double literal converted to the float parameter)
-
-__device__ __forceinline__ int clampi_(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 struct LoopGeom {
   int b;
@@ -74,26 +70,6 @@ __device__ __forceinline__ LoopGeom loop_geometry(const float* __restrict__ roi,
   return g;
 }
 
-// bin size of a rectangle [s, e] over P bins (MOIPool's arithmetic: ROILoopPool_cuda.cu:88-91)
-__device__ __forceinline__ float bin_size(int s, int e, int P) {
-#pragma clang fp contract(off)
-  return (float)max(e - s + 1, 1) / (float)P;
-}
-// unclipped [lo, hi) of bin p (the clip to the map is applied by the callers that scan)
-__device__ __forceinline__ int bin_lo(int p, float bin, int s) { return (int)floorf((float)p * bin) + s; }
-__device__ __forceinline__ int bin_hi(int p, float bin, int s) { return (int)ceilf((float)(p + 1) * bin) + s; }
-
-template <int VEC> struct VecT;
-template <> struct VecT<4> { using T = float4; };
-template <> struct VecT<1> { using T = float; };
-
-__device__ __forceinline__ float comp(const float4& v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
-__device__ __forceinline__ float comp(const float& v, int) { return v; }
-__device__ __forceinline__ void set_comp(float4& v, int k, float x) {
-  if (k == 0) v.x = x; else if (k == 1) v.y = x; else if (k == 2) v.z = x; else v.w = x;
-}
-__device__ __forceinline__ void set_comp(float& v, int, float x) { v = x; }
-
 // One wavefront per (roi, bin row ph); lane owns channels [c, c + VEC) of every 64*VEC-channel block.
 template <int VEC>
 __global__ __launch_bounds__(256) void loop_pool_fwd_nhwc(const float* __restrict__ in, const float* __restrict__ rois,
@@ -111,14 +87,14 @@ __global__ __launch_bounds__(256) void loop_pool_fwd_nhwc(const float* __restric
   const size_t block = (size_t)R * PH * PW * C;   // elements of one of the three blocks
   const float bbh = bin_size(g.y0, g.y1, PH), bbw = bin_size(g.x0, g.x1, PW);
   const float obh = bin_size(g.oy0, g.oy1, PH), obw = bin_size(g.ox0, g.ox1, PW);
-  const int bhs = clampi_(bin_lo(ph, bbh, g.y0), 0, H), bhe = ok ? clampi_(bin_hi(ph, bbh, g.y0), 0, H) : 0;
-  const int ohs = clampi_(bin_lo(ph, obh, g.oy0), 0, H), ohe = ok ? clampi_(bin_hi(ph, obh, g.oy0), 0, H) : 0;
+  const int bhs = clampi(bin_lo(ph, bbh, g.y0), 0, H), bhe = ok ? clampi(bin_hi(ph, bbh, g.y0), 0, H) : 0;
+  const int ohs = clampi(bin_lo(ph, obh, g.oy0), 0, H), ohe = ok ? clampi(bin_hi(ph, obh, g.oy0), 0, H) : 0;
   for (int c = lane * VEC; c < C; c += 64 * VEC) {
     for (int pw = 0; pw < PW; ++pw) {
       const size_t o = (((size_t)n * PH + ph) * PW + pw) * C + c;
       // ---- box + frame: one scan of the box's bin
       {
-        const int ws = clampi_(bin_lo(pw, bbw, g.x0), 0, W), we = clampi_(bin_hi(pw, bbw, g.x0), 0, W);
+        const int ws = clampi(bin_lo(pw, bbw, g.x0), 0, W), we = clampi(bin_hi(pw, bbw, g.x0), 0, W);
         V mb, mf;
         int ab[VEC], af[VEC];
 #pragma unroll
@@ -132,7 +108,7 @@ __global__ __launch_bounds__(256) void loop_pool_fwd_nhwc(const float* __restric
             const bool frame = !(in_h && w > g.ix0 && w < g.ix1);
             const int idx = h * W + w;
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) {
+            for (int k = 0; k < VEC; ++k) {   // (update_max of both maxima, one pass over the lane's channels)
               const float x = comp(v, k);
               if (x > comp(mb, k)) { set_comp(mb, k, x); ab[k] = idx; }
               if (frame && x > comp(mf, k)) { set_comp(mf, k, x); af[k] = idx; }
@@ -146,7 +122,7 @@ __global__ __launch_bounds__(256) void loop_pool_fwd_nhwc(const float* __restric
       }
       // ---- context: the outer box's bin minus the box's strict interior
       {
-        const int ws = clampi_(bin_lo(pw, obw, g.ox0), 0, W), we = clampi_(bin_hi(pw, obw, g.ox0), 0, W);
+        const int ws = clampi(bin_lo(pw, obw, g.ox0), 0, W), we = clampi(bin_hi(pw, obw, g.ox0), 0, W);
         V mc;
         int ac[VEC];
 #pragma unroll
@@ -158,12 +134,7 @@ __global__ __launch_bounds__(256) void loop_pool_fwd_nhwc(const float* __restric
           for (int w = ws; w < we; ++w) {
             if (in_h && w > g.x0 && w < g.x1) continue;
             const V v = *reinterpret_cast<const V*>(row + (size_t)w * C);
-            const int idx = h * W + w;
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-              const float x = comp(v, k);
-              if (x > comp(mc, k)) { set_comp(mc, k, x); ac[k] = idx; }
-            }
+            update_max<VEC>(v, h * W + w, mc, ac);
           }
         }
         *reinterpret_cast<V*>(out + 2 * block + o) = mc;
@@ -187,44 +158,41 @@ __global__ __launch_bounds__(256) void loop_pool_fwd_nchw(const float* __restric
     const float* __restrict__ p = in + ((size_t)(ok ? g.b : 0) * C + c) * H * W;
     {
       const float bh = bin_size(g.y0, g.y1, PH), bw = bin_size(g.x0, g.x1, PW);
-      const int hs = clampi_(bin_lo(ph, bh, g.y0), 0, H), he = ok ? clampi_(bin_hi(ph, bh, g.y0), 0, H) : 0;
-      const int ws = clampi_(bin_lo(pw, bw, g.x0), 0, W), we = clampi_(bin_hi(pw, bw, g.x0), 0, W);
+      const int hs = clampi(bin_lo(ph, bh, g.y0), 0, H), he = ok ? clampi(bin_hi(ph, bh, g.y0), 0, H) : 0;
+      const int ws = clampi(bin_lo(pw, bw, g.x0), 0, W), we = clampi(bin_hi(pw, bw, g.x0), 0, W);
       float mb = 0.f, mf = 0.f;
       int ab = -1, af = -1;
       for (int h = hs; h < he; ++h)
         for (int w = ws; w < we; ++w) {
           const int idx = h * W + w;
           const float x = p[idx];
-          if (x > mb) { mb = x; ab = idx; }
+          update_max(x, idx, mb, ab);
           if (h > g.iy0 && h < g.iy1 && w > g.ix0 && w < g.ix1) continue;
-          if (x > mf) { mf = x; af = idx; }
+          update_max(x, idx, mf, af);
         }
       out[i] = mb; argmax[i] = ab;
       out[total + i] = mf; argmax[total + i] = af;
     }
     {
       const float bh = bin_size(g.oy0, g.oy1, PH), bw = bin_size(g.ox0, g.ox1, PW);
-      const int hs = clampi_(bin_lo(ph, bh, g.oy0), 0, H), he = ok ? clampi_(bin_hi(ph, bh, g.oy0), 0, H) : 0;
-      const int ws = clampi_(bin_lo(pw, bw, g.ox0), 0, W), we = clampi_(bin_hi(pw, bw, g.ox0), 0, W);
+      const int hs = clampi(bin_lo(ph, bh, g.oy0), 0, H), he = ok ? clampi(bin_hi(ph, bh, g.oy0), 0, H) : 0;
+      const int ws = clampi(bin_lo(pw, bw, g.ox0), 0, W), we = clampi(bin_hi(pw, bw, g.ox0), 0, W);
       float mc = 0.f;
       int ac = -1;
       for (int h = hs; h < he; ++h)
         for (int w = ws; w < we; ++w) {
           if (h > g.y0 && h < g.y1 && w > g.x0 && w < g.x1) continue;
-          const int idx = h * W + w;
-          const float x = p[idx];
-          if (x > mc) { mc = x; ac = idx; }
+          update_max(p[h * W + w], h * W + w, mc, ac);
         }
       out[2 * total + i] = mc; argmax[2 * total + i] = ac;
     }
   }
 }
 
-// Per-roi record of the backward gather: image, and for the box (blocks 0, 1) and outer box (block 2) the rectangle
-// start, the bin sizes and the unclipped reach [start, start + ceil(P * bin)).
+// Per-roi record of the backward gather: image, the box's rectangle (blocks 0, 1) and the outer box's (block 2).
 struct LoopReach {
-  int b, bx0, by0, bxe, bye, ox0, oy0, oxe, oye;
-  float bbw, bbh, obw, obh;
+  int b;
+  BinRect box, outer;
   int pad[3];
 };
 static_assert(sizeof(LoopReach) == 64, "LoopReach is one 64-byte record");
@@ -235,18 +203,12 @@ __global__ __launch_bounds__(256) void loop_pool_reach_kernel(const float* __res
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= R) return;
   const LoopGeom g = loop_geometry(rois + (size_t)n * 5, scale, H, W);
-  LoopReach q = {};
-  q.b = g.b;
-  q.bbh = bin_size(g.y0, g.y1, PH); q.bbw = bin_size(g.x0, g.x1, PW);
-  q.obh = bin_size(g.oy0, g.oy1, PH); q.obw = bin_size(g.ox0, g.ox1, PW);
-  q.bx0 = g.x0; q.by0 = g.y0; q.bxe = bin_hi(PW - 1, q.bbw, g.x0); q.bye = bin_hi(PH - 1, q.bbh, g.y0);
-  q.ox0 = g.ox0; q.oy0 = g.oy0; q.oxe = bin_hi(PW - 1, q.obw, g.ox0); q.oye = bin_hi(PH - 1, q.obh, g.oy0);
-  reach[n] = q;
+  reach[n] = {g.b, BinRect(g.x0, g.y0, g.x1, g.y1, PH, PW), BinRect(g.ox0, g.oy0, g.ox1, g.oy1, PH, PW), {0, 0, 0}};
 }
 
 // grad_in[b, h, w, c] = sum over (roi n, block k, bin (ph, pw)) whose bin holds (h, w) and whose argmax names it of
-// grad[kR + n, ph, pw, c] — roi order, then block, then bin: a fixed order.  One wavefront per (image, cell) and
-// 64*VEC-channel block (grid.y).
+// grad[kR + n, ph, pw, c] — roi order, then the box's bins (block 0, then block 1 of each bin), then the outer box's
+// (block 2): a fixed order.  One wavefront per (image, cell) and 64*VEC-channel block (grid.y).
 template <int VEC>
 __global__ __launch_bounds__(256) void loop_pool_bwd_gather(const float* __restrict__ grad, const int* __restrict__ argmax,
                                                             const LoopReach* __restrict__ reach, float* __restrict__ gin,
@@ -265,37 +227,20 @@ __global__ __launch_bounds__(256) void loop_pool_bwd_gather(const float* __restr
 #pragma unroll
   for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
   auto add = [&](size_t row) {   // row = (n', ph, pw) of one block
-    if (!live) return;
-    const size_t o = row * C + c;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k)
-      if (argmax[o + k] == idx) acc[k] += grad[o + k];
+    if (live) gather_add<VEC>(acc, grad, argmax, row, C, c, idx);
   };
   for (int n = 0; n < R; ++n) {
     const LoopReach q = reach[n];   // (uniform: scalar loads)
     if (q.b != b) continue;
-    const bool in_box = h >= q.by0 && h < q.bye && w >= q.bx0 && w < q.bxe;
-    const bool in_outer = h >= q.oy0 && h < q.oye && w >= q.ox0 && w < q.oxe;
-    if (in_box) {
-      for (int ph = 0; ph < PH; ++ph) {
-        if (h < bin_lo(ph, q.bbh, q.by0) || h >= bin_hi(ph, q.bbh, q.by0)) continue;
-        for (int pw = 0; pw < PW; ++pw) {
-          if (w < bin_lo(pw, q.bbw, q.bx0) || w >= bin_hi(pw, q.bbw, q.bx0)) continue;
-          const size_t row = ((size_t)n * PH + ph) * PW + pw;
-          add(row);
-          add(row + block / C);
-        }
-      }
-    }
-    if (in_outer) {
-      for (int ph = 0; ph < PH; ++ph) {
-        if (h < bin_lo(ph, q.obh, q.oy0) || h >= bin_hi(ph, q.obh, q.oy0)) continue;
-        for (int pw = 0; pw < PW; ++pw) {
-          if (w < bin_lo(pw, q.obw, q.ox0) || w >= bin_hi(pw, q.obw, q.ox0)) continue;
-          add(((size_t)n * PH + ph) * PW + pw + 2 * (block / C));
-        }
-      }
-    }
+    const bool in_box = q.box.reaches(h, w), in_outer = q.outer.reaches(h, w);
+    if (in_box)
+      for_bins_holding(q.box, h, w, PH, PW, [&](int ph, int pw) {
+        const size_t row = ((size_t)n * PH + ph) * PW + pw;
+        add(row);
+        add(row + block / C);
+      });
+    if (in_outer)
+      for_bins_holding(q.outer, h, w, PH, PW, [&](int ph, int pw) { add(((size_t)n * PH + ph) * PW + pw + 2 * (block / C)); });
   }
   if (!live) return;
   V v;
@@ -314,61 +259,18 @@ extern "C" {
 int jtsm_roi_loop_pool_forward_f32(const float* input, const float* rois, float* output, int32_t* argmax, int B, int C,
                                    int H, int W, int R, float spatial_scale, int pooled_h, int pooled_w, int layout,
                                    void* stream) {
-  JTSM_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && R >= 0 && pooled_h > 0 && pooled_w > 0,
-               "roi_loop_pool: negative size");
-  JTSM_REQUIRE(layout == JTSM_NCHW || layout == JTSM_NHWC, "roi_loop_pool: unknown layout %d", layout);
-  if ((long)R * C == 0) return JTSM_OK;
-  JTSM_REQUIRE(input && rois && output && argmax, "roi_loop_pool: null pointer");
-  JTSM_REQUIRE(B > 0 && H > 0 && W > 0, "roi_loop_pool: empty feature map");
-  JTSM_REQUIRE((long)H * W < (1L << 31), "roi_loop_pool: map too large for int32 argmax");
-  hipStream_t st = as_stream(stream);
-  if (layout == JTSM_NHWC) {
-    const int blocks = ceil_div((long)R * pooled_h, 4);
-    const bool v4 = C % 4 == 0 && ((uintptr_t)input & 15) == 0 && ((uintptr_t)output & 15) == 0;
-    if (v4)
-      hipLaunchKernelGGL(loop_pool_fwd_nhwc<4>, dim3(blocks), dim3(256), 0, st, input, rois, output, argmax, B, C, H, W, R,
-                         spatial_scale, pooled_h, pooled_w);
-    else
-      hipLaunchKernelGGL(loop_pool_fwd_nhwc<1>, dim3(blocks), dim3(256), 0, st, input, rois, output, argmax, B, C, H, W, R,
-                         spatial_scale, pooled_h, pooled_w);
-  } else {
-    const long total = (long)R * C * pooled_h * pooled_w;
-    const int blocks = (int)std::min<long>(ceil_div(total, 256), 8192);
-    hipLaunchKernelGGL(loop_pool_fwd_nchw, dim3(blocks), dim3(256), 0, st, input, rois, output, argmax, B, C, H, W, R,
-                       spatial_scale, pooled_h, pooled_w);
-  }
-  JTSM_CHECK_LAUNCH("roi_loop_pool forward");
-  return JTSM_OK;
+  return pool_forward<loop_pool_fwd_nhwc<4>, loop_pool_fwd_nhwc<1>, loop_pool_fwd_nchw>(
+      "roi_loop_pool", input, rois, output, argmax, B, C, H, W, R, spatial_scale, pooled_h, pooled_w, layout, stream);
 }
 
-size_t jtsm_roi_loop_pool_backward_workspace_bytes(int R) { return R > 0 ? (size_t)R * sizeof(LoopReach) : 16; }
+size_t jtsm_roi_loop_pool_backward_workspace_bytes(int R) { return pool_backward_workspace_bytes<LoopReach>(R); }
 
 int jtsm_roi_loop_pool_backward_f32(const float* grad, const float* rois, const int32_t* argmax, float* grad_input,
                                     void* workspace, int B, int C, int H, int W, int R, float spatial_scale, int pooled_h,
                                     int pooled_w, void* stream) {
-  JTSM_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && R >= 0 && pooled_h > 0 && pooled_w > 0,
-               "roi_loop_pool backward: negative size");
-  const long cells = (long)B * H * W;
-  if (cells * C == 0) return JTSM_OK;
-  JTSM_REQUIRE(grad_input && workspace, "roi_loop_pool backward: null grad_input / workspace");
-  JTSM_REQUIRE(R == 0 || (grad && rois && argmax), "roi_loop_pool backward: null pointer");
-  JTSM_REQUIRE(((uintptr_t)workspace & 15) == 0, "roi_loop_pool backward: workspace must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  LoopReach* reach = reinterpret_cast<LoopReach*>(workspace);
-  if (R > 0)
-    hipLaunchKernelGGL(loop_pool_reach_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, st, rois, reach, R, H, W, spatial_scale,
-                       pooled_h, pooled_w);
-  const bool v4 = C % 4 == 0 && ((uintptr_t)grad_input & 15) == 0;
-  const int vec = v4 ? 4 : 1;
-  const dim3 grid(ceil_div(cells, 4), ceil_div(C, 64 * vec));
-  if (v4)
-    hipLaunchKernelGGL(loop_pool_bwd_gather<4>, grid, dim3(256), 0, st, grad, argmax, reach, grad_input, B, C, H, W, R,
-                       pooled_h, pooled_w);
-  else
-    hipLaunchKernelGGL(loop_pool_bwd_gather<1>, grid, dim3(256), 0, st, grad, argmax, reach, grad_input, B, C, H, W, R,
-                       pooled_h, pooled_w);
-  JTSM_CHECK_LAUNCH("roi_loop_pool backward");
-  return JTSM_OK;
+  return pool_backward<LoopReach, loop_pool_reach_kernel, loop_pool_bwd_gather<4>, loop_pool_bwd_gather<1>>(
+      "roi_loop_pool", grad, rois, argmax, grad_input, workspace, B, C, H, W, R, spatial_scale, pooled_h, pooled_w,
+      stream);
 }
 
 }  // extern "C"

@@ -4,117 +4,14 @@ libjtsm_hip.so (jtsm_roi_loop_pool_{forward,backward}_f32).
 forward(input (B,C,H,W), rois (R,5)) -> (3R, C, PH, PW): the box, frame and context blocks of
 ContextLocNet, each in roi order.  The output follows the input's memory format (channels_last in,
 channels_last out).  float16 tensors are widened to float32 here and the result rounded back; max
-pooling only selects values, so that is exact.
+pooling only selects values, so that is exact.  The implementation is layers/roi_pool.py's, with three row blocks.
 """
-import torch
-from torch import nn
-from torch.autograd import Function
-from torch.autograd.function import once_differentiable
-from torch.nn.modules.utils import _pair
+from .roi_pool import MaxPoolModule, MaxPoolOp
 
-from .. import _lib as L
-from .roi_align import _as_layout, _empty_like_layout
-
-CL = torch.channels_last
+_OP = MaxPoolOp("ROILoopPool", 3, "jtsm_roi_loop_pool_forward_f32", "jtsm_roi_loop_pool_backward_workspace_bytes",
+                "jtsm_roi_loop_pool_backward_f32")
+roi_loop_pool_forward, roi_loop_pool_backward, roi_loop_pool = _OP.forward, _OP.backward, _OP.apply
 
 
-def roi_loop_pool_forward(input, rois, spatial_scale, pooled_h, pooled_w):
-    """(output, argmax int32), both (3R, C, PH, PW) in the input's memory format."""
-    L.require_gpu(input, rois)
-    if input.dtype not in (torch.float32, torch.float16):
-        raise RuntimeError('"ROILoopPool_forward" is implemented for float32 and float16, got %s' % input.dtype)
-    if input.dtype != rois.dtype:
-        raise RuntimeError("expected input and rois to have the same dtype")
-    if rois.dim() != 2 or rois.shape[1] != 5:
-        raise RuntimeError("rois must be (R, 5), got %s" % (tuple(rois.shape),))
-    half = input.dtype == torch.float16
-    x, layout = _as_layout(input.float() if half else input)
-    if half and layout == L.NHWC:
-        x = x.contiguous(memory_format=CL)
-    r = rois.float().contiguous()
-    B, Cc, H, W = x.shape
-    R = r.shape[0]
-    out = _empty_like_layout((3 * R, Cc, pooled_h, pooled_w), x, layout)
-    fmt = CL if layout == L.NHWC else torch.contiguous_format
-    arg = torch.empty((3 * R, Cc, pooled_h, pooled_w), dtype=torch.int32, device=x.device, memory_format=fmt)
-    if out.numel():
-        L.note_bytes(4.0 * (2 * out.numel() + r.numel()))
-        L.check(L.lib().jtsm_roi_loop_pool_forward_f32(
-            L.ptr(x), L.ptr(r), L.ptr(out), L.ptr(arg), B, Cc, H, W, R, spatial_scale, pooled_h, pooled_w,
-            layout, L.stream()), "roi_loop_pool_forward")
-    if half:
-        out = out.half()
-    return out, arg
-
-
-def roi_loop_pool_backward(grad, rois, argmax, spatial_scale, pooled_h, pooled_w, B, Cc, H, W, nhwc=None):
-    """grad_input (B, C, H, W) in the forward input's memory format (`nhwc`; None: read from `argmax`), dtype of
-    `grad`.  The kernel reads and writes channels_last; NCHW tensors are converted at this boundary."""
-    L.require_gpu(grad, rois, argmax)
-    nchw = (not nhwc) if nhwc is not None else (not L.is_nhwc(argmax) and argmax.numel() > 0 and argmax.shape[1] > 1)
-    half = grad.dtype == torch.float16
-    g = (grad.float() if half else grad).contiguous(memory_format=CL)
-    a = argmax.contiguous(memory_format=CL)
-    r = rois.float().contiguous()
-    gin = torch.empty((B, Cc, H, W), dtype=torch.float32, device=g.device, memory_format=CL)
-    if gin.numel():
-        lib = L.lib()
-        ws = torch.empty(max(lib.jtsm_roi_loop_pool_backward_workspace_bytes(r.shape[0]), 16), dtype=torch.uint8,
-                         device=g.device)
-        L.note_bytes(4.0 * (2 * g.numel() + gin.numel()))
-        L.check(lib.jtsm_roi_loop_pool_backward_f32(
-            L.ptr(g), L.ptr(r), L.ptr(a), L.ptr(gin), L.ptr(ws), B, Cc, H, W, r.shape[0], spatial_scale,
-            pooled_h, pooled_w, L.stream()), "roi_loop_pool_backward")
-    if nchw:
-        gin = gin.contiguous()
-    return gin.half() if half else gin
-
-
-class _ROILoopPool(Function):
-    @staticmethod
-    def forward(ctx, input, roi, output_size, spatial_scale):
-        ctx.output_size = _pair(output_size)
-        ctx.spatial_scale = spatial_scale
-        ctx.input_shape = input.size()
-        ctx.nhwc = L.is_nhwc(input)
-        output, argmax = roi_loop_pool_forward(input, roi, spatial_scale, ctx.output_size[0], ctx.output_size[1])
-        ctx.save_for_backward(roi, argmax)
-        ctx.mark_non_differentiable(argmax)
-        return output
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output):
-        rois, argmax = ctx.saved_tensors
-        bs, ch, h, w = ctx.input_shape
-        grad_input = roi_loop_pool_backward(grad_output, rois, argmax, ctx.spatial_scale, ctx.output_size[0],
-                                            ctx.output_size[1], bs, ch, h, w, nhwc=ctx.nhwc)
-        return grad_input, None, None, None
-
-
-roi_loop_pool = _ROILoopPool.apply
-
-
-class ROILoopPool(nn.Module):
-    def __init__(self, output_size, spatial_scale):
-        """output_size (h, w); spatial_scale: multiply boxes by this before rounding."""
-        super().__init__()
-        self.output_size = output_size
-        self.spatial_scale = spatial_scale
-
-    def forward(self, input, rois):
-        """
-        Args:
-            input: NCHW features (channels_last storage is kept)
-            rois: Rx5 boxes (batch index, x0, y0, x1, y1)
-        Returns: (3R, C, PH, PW) — box, frame and context blocks
-        """
-        assert rois.dim() == 2 and rois.size(1) == 5
-        return roi_loop_pool(input, rois, self.output_size, self.spatial_scale)
-
-    def __repr__(self):
-        tmpstr = self.__class__.__name__ + "("
-        tmpstr += "output_size=" + str(self.output_size)
-        tmpstr += ", spatial_scale=" + str(self.spatial_scale)
-        tmpstr += ")"
-        return tmpstr
+class ROILoopPool(MaxPoolModule):
+    op = _OP

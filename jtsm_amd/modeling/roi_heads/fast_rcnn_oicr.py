@@ -15,6 +15,7 @@ from ...layers.wrappers import Linear, cat
 from ...layers.wsl_losses import oicr_loss
 from ...structures import Boxes, Instances
 from ..box_regression import Box2BoxTransform
+from .roi_heads import bag_offsets
 
 
 _SIDE = {}
@@ -173,8 +174,7 @@ class OICROutputLayers(nn.Module):
         boxes = cat([p.proposal_boxes.tensor for p in proposals], dim=0)
         assert not boxes.requires_grad, "Proposals should not require gradients!"
         if offsets is None:
-            offsets = torch.tensor([0] + list(torch.tensor(counts).cumsum(0)), dtype=torch.int32).to(
-                scores.device, non_blocking=True)
+            offsets = bag_offsets(counts, scores.device)
         loss, self.pcl_probs, self.pcl_tables = pcl_loss(scores, boxes, offsets, max(max(counts), 1),
                                                          last_scores.detach(), gt_classes_img_oh)
         key = "loss_cls_r" + str(self.refine_k)

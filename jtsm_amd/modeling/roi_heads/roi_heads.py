@@ -40,6 +40,11 @@ def get_image_level_gt(targets, num_classes):
     return gt_classes_img, gt_classes_img_int, oh
 
 
+def bag_offsets(counts, device):
+    """int32 (B+1,) device tensor of the images' first rows in the concatenated proposal list."""
+    return torch.tensor([0] + list(torch.tensor(counts).cumsum(0)), dtype=torch.int32).to(device, non_blocking=True)
+
+
 class ROIHeads(torch.nn.Module):
     def __init__(self, *, num_classes, batch_size_per_image, positive_fraction, proposal_matcher,
                  proposal_append_gt=True):

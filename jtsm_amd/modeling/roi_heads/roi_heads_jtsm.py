@@ -46,7 +46,7 @@ from .box_head import build_box_head
 from .fast_rcnn_oicr import OICROutputLayers
 from .fast_rcnn_tsm import TSMOutputLayers
 from .mask_head import build_mask_head, mask_rcnn_inference, mask_rcnn_loss
-from .roi_heads import ROI_HEADS_REGISTRY, ROIHeads, get_image_level_gt, select_foreground_proposals
+from .roi_heads import ROI_HEADS_REGISTRY, ROIHeads, bag_offsets, get_image_level_gt, select_foreground_proposals
 
 
 @torch.no_grad()
@@ -339,7 +339,7 @@ class JTSMROIHeads(ROIHeads):
         outs, argmax = self._box_features(features, proposals)
         dev = outs[0].device
         cls_logits, det_logits = outs[0], outs[1]
-        offsets = torch.tensor([0] + list(torch.tensor(counts).cumsum(0)), dtype=torch.int32).to(dev, non_blocking=True)
+        offsets = bag_offsets(counts, dev)
         labels_oh = (torch.cat([self.gt_classes_img_oh, self.gt_classes_img_oh_stuff], dim=1)
                      if self.has_stuff else self.gt_classes_img_oh)
         losses, scores, img_probs = self.box_predictor.score_and_loss(cls_logits, det_logits, offsets, labels_oh,

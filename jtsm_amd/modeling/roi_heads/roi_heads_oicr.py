@@ -14,7 +14,7 @@ branch's cls_score / bbox_pred ride in the DAN's node as its tail GEMM.  A refin
 mining (layers/mining.py mine_top1, or layers/mist.py mine_top_p), labelling (match_label, which takes the padded
 survivor list with its device-side count) and the fused loss — and reads nothing back to the host, MIST included,
 where the reference's topk / batched_nms / indexing chain brings the list lengths to the host in every round."""
-from typing import Dict, List, Optional
+from typing import Dict
 
 import torch
 
@@ -22,13 +22,9 @@ from ...layers.conv import linear_fused_split
 from ...layers.mining import match_label, mine_top1, row_lse
 from ...layers.mist import mine_top_p, top_p_counts
 from ...layers.shape_spec import ShapeSpec
-from ...structures import ImageList, Instances
-from ..poolers import ROIPooler
-from .box_head import build_box_head
-from .fast_rcnn_oicr import OICROutputLayers
-from .fast_rcnn_wsddn import WSDDNOutputLayers
-from .roi_heads import ROI_HEADS_REGISTRY, ROIHeads
-from .roi_heads_jtsm import class_lists, present_things
+from .roi_heads import ROI_HEADS_REGISTRY, bag_offsets
+from .roi_heads_jtsm import class_lists
+from .roi_heads_wsl import WSLBoxHeads
 
 MIST_TOP_PRO = 0.15        # get_pgt_mist's top_pro default (:550)
 MIST_NMS_THRESH = 0.2      # (:566)
@@ -36,51 +32,18 @@ MIST_FIRST_BRANCH_WEIGHT = 3
 
 
 @ROI_HEADS_REGISTRY.register()
-class OICRROIHeads(ROIHeads):
+class OICRROIHeads(WSLBoxHeads):
     def __init__(self, cfg, input_shape: Dict[str, ShapeSpec]):
-        super().__init__(**ROIHeads.from_config(cfg))
-        if cfg.MODEL.MASK_ON or cfg.MODEL.KEYPOINT_ON:
-            raise NotImplementedError("OICRROIHeads: only the box branch is implemented (MASK_ON / KEYPOINT_ON)")
         if cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG:
             raise NotImplementedError("OICRROIHeads: CLS_AGNOSTIC_BBOX_REG")
         if cfg.MODEL.ROI_BOX_HEAD.TRAIN_ON_PRED_BOXES:
             raise NotImplementedError("OICRROIHeads: TRAIN_ON_PRED_BOXES")
         if cfg.WSL.SAMPLING.SAMPLING_ON:
             raise NotImplementedError("OICRROIHeads: WSL.SAMPLING (label_and_sample_proposals_wsl)")
-        in_features = cfg.MODEL.ROI_HEADS.IN_FEATURES
-        self.box_in_features = self.in_features = in_features
-        scales = tuple(1.0 / input_shape[k].stride for k in in_features)
-        in_channels = [input_shape[f].channels for f in in_features]
-        assert len(set(in_channels)) == 1, in_channels
-        res = cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION
-        self.box_pooler = ROIPooler(output_size=res, scales=scales,
-                                    sampling_ratio=cfg.MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO,
-                                    pooler_type=cfg.MODEL.ROI_BOX_HEAD.POOLER_TYPE)
-        self.box_head = build_box_head(cfg, ShapeSpec(channels=in_channels[0], height=res, width=res))
-        self.box_predictor = WSDDNOutputLayers.from_config(cfg, self.box_head.output_shape.channels)
-        self.refine_K = cfg.WSL.REFINE_NUM
+        super().__init__(cfg, input_shape)
         self.refine_mist = cfg.WSL.REFINE_MIST
-        assert len(cfg.WSL.REFINE_REG) >= self.refine_K, "WSL.REFINE_REG needs one entry per refinement branch"
-        self.box_refinery = []
-        for k in range(self.refine_K):
-            refinery = OICROutputLayers.from_config(cfg, self.box_head.output_shape.channels, k)
-            self.add_module("box_refinery_{}".format(k), refinery)
-            self.box_refinery.append(refinery)
-        self.aux = {}
-
-    def forward(self, images: ImageList, features: Dict[str, torch.Tensor], proposals: List[Instances],
-                targets: Optional[List[Instances]] = None):
-        del images
-        if self.training:
-            assert targets, "'targets' argument is required during training"
-            self.gt_classes_img_oh = present_things(targets, self.num_classes)
-            return proposals, self._forward_box(features, proposals)
-        pred_instances, all_scores, all_boxes = self._forward_box(features, proposals)
-        return pred_instances, {}, all_scores, all_boxes
-
-    def forward_with_given_boxes(self, features, instances):
-        assert not self.training
-        return instances, [], []
+        assert len(cfg.WSL.REFINE_REG) >= cfg.WSL.REFINE_NUM, "WSL.REFINE_REG needs one entry per refinement branch"
+        self._build_refinery(cfg)
 
     def _predictor_layers(self):
         mods = [self.box_predictor.cls, self.box_predictor.det]
@@ -91,19 +54,9 @@ class OICRROIHeads(ROIHeads):
     def _logits(self, features, proposals):
         """-> [cls (R, K), det (R, K), branch 0 logits (R, K+1), (branch 0 deltas (R, 4K),) ...]: pool, rescale, DAN,
         every predictor in one GEMM."""
-        feats = [features[f] for f in self.box_in_features]
-        pooled = self.box_pooler(feats, [x.proposal_boxes for x in proposals])
-        scale = torch.cat([x.objectness_logits + 1 for x in proposals], dim=0).to(torch.float32).contiguous()
         mods = self._predictor_layers()
-        weights, biases = [m.weight for m in mods], [m.bias for m in mods]
-        if getattr(self.box_head, "takes_roi_scale", False):
-            out = self.box_head(pooled, roi_scale=scale, tail=(weights, biases))
-            if isinstance(out, tuple):                  # (the fused stack: the predictors' GEMM in its node)
-                return list(out[1])
-            h = out
-        else:
-            h = self.box_head(pooled * scale.view(-1, 1, 1, 1))
-        return list(linear_fused_split(h, weights, biases))
+        h, outs = self._pooled_hidden(features, proposals, mods)
+        return outs or list(linear_fused_split(h, [m.weight for m in mods], [m.bias for m in mods]))
 
     def _branch_outputs(self, outs):
         """[(logits, deltas or None)] of the refinement branches from the predictor GEMM's column slices."""
@@ -130,7 +83,7 @@ class OICRROIHeads(ROIHeads):
             return pred_instances, all_scores, all_boxes
 
         dev = c.device
-        offsets = torch.tensor([0] + list(torch.tensor(counts).cumsum(0)), dtype=torch.int32).to(dev, non_blocking=True)
+        offsets = bag_offsets(counts, dev)
         losses, scores, img_probs = self.box_predictor.score_and_loss(c, d, offsets, self.gt_classes_img_oh,
                                                                       max(max(counts), 1))
         self.pred_class_img_logits = img_probs

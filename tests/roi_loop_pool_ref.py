@@ -87,6 +87,8 @@ def forward(x, rois, scale, PH, PW, fused=False):
     out = np.zeros((3 * R, C, PH, PW), np.float32)
     arg = np.full((3 * R, C, PH, PW), -1, np.int32)
     for n in range(R):
+        if not 0 <= int(rois[n][0]) < B:                # (a roi naming no image pools nothing: 0 / -1)
+            continue
         g = geometry(rois[n], scale, H, W, fused)
         plane = x[int(rois[n][0])]
         box, inner, outer = g["box"], g["inner"], g["outer"]
@@ -122,6 +124,8 @@ def backward(grad, rois, argmax, B, C, H, W):
     n3 = argmax.shape[0]
     for n in range(n3):
         b = int(rois[n % R][0])
+        if not 0 <= b < B:
+            continue
         a = argmax[n].reshape(C, -1)
         g = grad[n].reshape(C, -1)
         for c in range(C):

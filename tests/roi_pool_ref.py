@@ -72,6 +72,8 @@ def backward(grad, rois, argmax, B, C, H, W):
     gin = np.zeros((B, C, H * W), np.float64)
     for n in range(argmax.shape[0]):
         b = int(rois[n][0])
+        if not 0 <= b < B:
+            continue
         a = argmax[n].reshape(C, -1)
         g = grad[n].reshape(C, -1)
         for c in range(C):

@@ -2,7 +2,8 @@
 jtsm_amd.layers / ROIPooler surfaces, against the CPU restatement of the CUDA contract (tests/roi_loop_pool_ref.py).
 
 Bars: forward values and argmax bit-exact in both layouts; fp16 at the boundary exact; backward within 1e-6
-(relative to the largest gradient) of the restatement's scatter-add and bit-identical across calls."""
+(relative to the largest gradient) of the restatement's scatter-add, bit-identical across calls, bit-identical to the
+float32 sum taken in the documented order, and unchanged by rois that name no image."""
 import zlib
 
 import numpy as np
@@ -25,7 +26,7 @@ CL = torch.channels_last
 def _rois(kind, rng, B, H, W, stride, R):
     """(R, 5) float32 rois in image coordinates of a (H*stride, W*stride) image."""
     ih, iw = H * stride, W * stride
-    if kind == "random":
+    if kind in ("random", "stray"):
         xy = rng.uniform(0, [iw, ih], (R, 2))
         wh = rng.uniform(1, [iw / 2, ih / 2], (R, 2))
         boxes = np.concatenate([xy, xy + wh], 1)
@@ -53,7 +54,26 @@ def _rois(kind, rng, B, H, W, stride, R):
     else:
         raise ValueError(kind)
     b = rng.integers(0, B, (R, 1))
+    if kind == "stray":           # ordinary boxes, a quarter of them naming no image: -1 and B in turn
+        b[1::4, 0] = np.where(np.arange(len(b[1::4])) % 2 == 0, -1, B)
     return np.concatenate([b, boxes], 1).astype(np.float32)
+
+
+def _sum_in_order(arg, g, b, B, C, H, W):
+    """float32 scatter-add in the order given: row i of arg / g (N, C) adds g[i, c] to cell arg[i, c] of image b[i],
+    channel c, where arg >= 0 and b names an image.  np.add.at adds sequentially in index order (rows, then channels),
+    so per (cell, channel) the terms are added in row order, starting from 0 — as the gather kernels do."""
+    gin = np.zeros((B, C, H * W), np.float32)
+    bb = np.broadcast_to(b.astype(np.int64)[:, None], arg.shape)
+    cc = np.broadcast_to(np.arange(C)[None], arg.shape)
+    ok = (arg >= 0) & (bb >= 0) & (bb < B)
+    np.add.at(gin, (bb[ok], cc[ok], arg[ok]), g[ok].astype(np.float32))
+    return gin.reshape(B, C, H, W)
+
+
+def _rows(t, R):
+    """(R, C, PH, PW) -> (R, PH * PW, C): a roi's bins in ph-outer / pw-inner order."""
+    return t.transpose(0, 2, 3, 1).reshape(R, -1, t.shape[1])
 
 
 def _feat(rng, B, C, H, W, kind="relu"):
@@ -79,7 +99,8 @@ def _gpu_forward(x, rois, scale, P, cuda, nhwc):
 
 CASES = [("random", "relu", 1, 16, 48), ("clustered", "relu", 2, 64, 60), ("large", "relu", 2, 8, 20),
          ("borders", "relu", 2, 12, 40), ("degenerate", "relu", 1, 8, 30), ("random", "zero", 2, 8, 10),
-         ("random", "negative", 1, 4, 10), ("clustered", "signed", 3, 3, 25), ("random", "relu", 2, 8, 0)]
+         ("random", "negative", 1, 4, 10), ("clustered", "signed", 3, 3, 25), ("random", "relu", 2, 8, 0),
+         ("stray", "relu", 2, 8, 40)]
 
 
 @pytest.mark.parametrize("nhwc", [True, False], ids=["nhwc", "nchw"])
@@ -94,6 +115,10 @@ def test_forward_matches_restatement_bit_exact(cuda, kind, feat, B, C, R, nhwc):
     assert got.shape == (3 * R, C, P, P)
     np.testing.assert_array_equal(got_arg, want_arg)
     np.testing.assert_array_equal(got, want)
+    if kind == "stray":           # a roi naming no image pools nothing, in all three blocks
+        bad = np.tile((rois[:, 0] < 0) | (rois[:, 0] >= B), 3)
+        assert bad.sum() == 3 * 10 and (got[bad] == 0).all() and (got_arg[bad] == -1).all()
+        assert (got_arg[~bad] >= 0).any()
 
 
 def test_forward_unfused_reading_on_the_split_boxes(cuda):
@@ -177,7 +202,8 @@ def test_backward_matches_restatement_and_is_reproducible(cuda, C, nhwc):
     B, H, W = 2, 20, 24
     x = _feat(rng, B, C, H, W)
     rois = np.concatenate([_rois("clustered", rng, B, H, W, 8, 20), _rois("borders", rng, B, H, W, 8, 6),
-                           _rois("degenerate", rng, B, H, W, 8, 4), _rois("large", rng, B, H, W, 8, 2)])
+                           _rois("degenerate", rng, B, H, W, 8, 4), _rois("large", rng, B, H, W, 8, 2),
+                           _rois("stray", rng, B, H, W, 8, 12)])
     R = len(rois)
     g = rng.standard_normal((3 * R, C, 7, 7)).astype(np.float32)
     _, arg = ref.forward(x, rois, 0.125, 7, 7)
@@ -197,6 +223,22 @@ def test_backward_matches_restatement_and_is_reproducible(cuda, C, nhwc):
     _, argt = roi_loop_pool_forward(xt.detach(), rt, 0.125, 7, 7)
     again = roi_loop_pool_backward(gt, rt, argt, 0.125, 7, 7, B, C, H, W).cpu().numpy()
     np.testing.assert_array_equal(again, got)
+    # the documented order, in float32: rois ascending; per roi the box's bins (block 0, then block 1 of each bin)
+    # before the outer box's (block 2); bins ph outer, pw inner
+    np.testing.assert_array_equal(argt.cpu().numpy(), arg)
+
+    def in_order(t):
+        box = np.stack([_rows(t[:R], R), _rows(t[R:2 * R], R)], axis=2).reshape(R, -1, C)
+        return np.concatenate([box, _rows(t[2 * R:], R)], axis=1).reshape(-1, C)
+
+    ordered = _sum_in_order(in_order(arg), in_order(g), np.repeat(rois[:, 0], 3 * 49), B, C, H, W)
+    np.testing.assert_array_equal(got, ordered)
+    # the rois that name no image removed from rois, argmax and grad: the same bits
+    keep = torch.from_numpy((rois[:, 0] >= 0) & (rois[:, 0] < B)).to(cuda)
+    assert 0 < int(keep.sum()) < R
+    keep3 = keep.repeat(3)
+    without = roi_loop_pool_backward(gt[keep3], rt[keep], argt[keep3], 0.125, 7, 7, B, C, H, W, nhwc=nhwc).cpu().numpy()
+    np.testing.assert_array_equal(without, got)
 
 
 def test_backward_without_rois_is_zero(cuda):

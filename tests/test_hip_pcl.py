@@ -3,7 +3,8 @@ jtsm_amd.layers / ROIPooler surfaces against tests/roi_pool_ref.py, and the devi
 loss (csrc/pcl.hip, layers/pcl.py) against tests/pcl_ref.py.
 
 Bars: ROIPool forward values and argmax bit-exact in both layouts, backward within 1e-6 (relative to the largest
-gradient) of the restatement's scatter-add and bit-identical across calls.  Clustering: integer tables bit-exact, float
+gradient) of the restatement's scatter-add, bit-identical across calls, bit-identical to the float32 sum taken in the
+documented order, and unchanged by rois that name no image.  Clustering: integer tables bit-exact, float
 tables within 1e-6 relative (fp32 roundings of fp64 sums against exactly summed ones), two runs identical.  Loss and
 logit gradient: 1e-4 of the largest reference entry, the bar tests/test_hip_losses.py uses for OICR."""
 import zlib
@@ -15,7 +16,7 @@ import torch
 import pcl_ref
 import roi_pool_ref as ref
 from conftest import load_cases
-from test_hip_contextlocnet import _feat, _rois
+from test_hip_contextlocnet import _feat, _rois, _rows, _sum_in_order
 from test_hip_losses import rel_close
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +43,8 @@ def _gpu_forward(x, rois, scale, P, cuda, nhwc):
 
 CASES = [("random", "relu", 1, 16, 48), ("clustered", "relu", 2, 64, 60), ("large", "relu", 2, 8, 20),
          ("borders", "relu", 2, 12, 40), ("degenerate", "relu", 1, 8, 30), ("random", "zero", 2, 8, 10),
-         ("random", "negative", 1, 4, 10), ("clustered", "signed", 3, 3, 25), ("random", "relu", 2, 8, 0)]
+         ("random", "negative", 1, 4, 10), ("clustered", "signed", 3, 3, 25), ("random", "relu", 2, 8, 0),
+         ("stray", "relu", 2, 8, 40)]
 
 
 @pytest.mark.parametrize("nhwc", [True, False], ids=["nhwc", "nchw"])
@@ -59,6 +61,10 @@ def test_roi_pool_forward_matches_restatement_bit_exact(cuda, kind, feat, B, C, 
     assert got.shape == (R, C, P, P)
     np.testing.assert_array_equal(got_arg, want_arg)
     np.testing.assert_array_equal(got, want)
+    if kind == "stray":                            # a roi naming no image pools nothing
+        bad = (rois[:, 0] < 0) | (rois[:, 0] >= B)
+        assert bad.sum() == 10 and (got[bad] == 0).all() and (got_arg[bad] == -1).all()
+        assert (got_arg[~bad] >= 0).any()
 
 
 def test_roi_pool_flagship_channels_and_module(cuda):
@@ -107,7 +113,8 @@ def test_roi_pool_backward_matches_restatement_and_is_reproducible(cuda, C, nhwc
     B, H, W = 2, 20, 24
     x = _feat(rng, B, C, H, W)
     rois = np.concatenate([_rois("clustered", rng, B, H, W, 8, 20), _rois("borders", rng, B, H, W, 8, 6),
-                           _rois("degenerate", rng, B, H, W, 8, 4), _rois("large", rng, B, H, W, 8, 2)])
+                           _rois("degenerate", rng, B, H, W, 8, 4), _rois("large", rng, B, H, W, 8, 2),
+                           _rois("stray", rng, B, H, W, 8, 12)])
     R = len(rois)
     g = rng.standard_normal((R, C, 7, 7)).astype(np.float32)
     _, arg = ref.forward(x, rois, 0.125, 7, 7)
@@ -125,6 +132,16 @@ def test_roi_pool_backward_matches_restatement_and_is_reproducible(cuda, C, nhwc
     _, argt = roi_pool_forward(xt.detach(), rt, 0.125, 7, 7)
     again = roi_pool_backward(gt, rt, argt, 0.125, 7, 7, B, C, H, W).cpu().numpy()
     np.testing.assert_array_equal(again, got)
+    # the documented order, in float32: rois ascending, bins ph outer, pw inner
+    np.testing.assert_array_equal(argt.cpu().numpy(), arg)
+    ordered = _sum_in_order(_rows(arg, R).reshape(-1, C), _rows(g, R).reshape(-1, C), np.repeat(rois[:, 0], 49),
+                            B, C, H, W)
+    np.testing.assert_array_equal(got, ordered)
+    # the rois that name no image removed from rois, argmax and grad: the same bits
+    keep = torch.from_numpy((rois[:, 0] >= 0) & (rois[:, 0] < B)).to(cuda)
+    assert 0 < int(keep.sum()) < R
+    without = roi_pool_backward(gt[keep], rt[keep], argt[keep], 0.125, 7, 7, B, C, H, W, nhwc=nhwc).cpu().numpy()
+    np.testing.assert_array_equal(without, got)
 
 
 def test_roi_pool_without_rois_is_zero(cuda):
