@@ -1014,6 +1014,33 @@ int jtsm_panoptic_combine(const uint8_t* masks, const int32_t* order, const floa
                           int32_t* seg_table, float* seg_score, int32_t* num_segments, int max_visits,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Pascal VOC detection AP at IoU 0.50:0.05:0.95 and CorLoc: PascalVOCDetectionEvaluator.process / evaluate with
+ * voc_eval, voc_ap and voc_eval_corloc (detectron2/evaluation/pascal_voc_evaluation.py:55-69, 210-355, 358-452) for all
+ * classes and thresholds in one call that reads nothing back.  Semantics: scores and boxes are first
+ * quantised to what the reference prints and parses again (thousandths; tenths, xmin / ymin after an fp32 + 1); fp64
+ * from there on; detections of a class are ranked by descending quantised score, equal scores in input order.
+ * Detections: det_boxes (D,4) xyxy as the model gives them (0-based), det_scores (D), det_classes (D) in [0, C),
+ * det_images (D) in [0, N).  Ground truth: gt_boxes (G,4) int32 as in the XML (1-based), gt_difficult (G) uint8, sorted
+ * by (class, image); gt_offsets (C*N+1) the CSR over (class, image), class-major.  C < 65536, N <= 2^24 (the bits the
+ * sort keys give them), else JTSM_EINVAL.
+ * Outputs: ap (10,C) and corloc (10,C) double, fractions (not x100), row t = threshold (50 + 5t)/100; ap is the 11-point
+ * form when use_07_metric != 0, else the area form (NaN for a class with detections and no non-difficult ground truth,
+ * as the reference; the 11-point form gives 0).  corloc is 0 for a class without detections and NaN for a class with
+ * detections and no image holding a non-difficult box (the reference divides by zero).  counts (C,2) int32 = {npos,
+ * npos_im}.  stats (4) double = {smallest score, largest score, number of detections whose class or image index is out
+ * of range (they are left out of everything), 0}.  Optional (NULL to skip), each (D) in INPUT order: tp_bits / fp_bits
+ * uint16 with bit t = the detection is a true / false positive at threshold t; order int32 = the detection's position
+ * in its class's ranking (-1 for an out-of-range detection).
+ * det_boxes and gt_boxes 16-byte aligned, workspace 256-byte aligned.  Integer atomics only: deterministic.
+ * ------------------------------------------------------------------------------------------------------------------ */
+size_t jtsm_voc_eval_workspace_bytes(int D, int G, int C);
+int jtsm_voc_eval(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                  const int32_t* det_images, int D, const int32_t* gt_boxes, const uint8_t* gt_difficult,
+                  const int32_t* gt_offsets, int G, int N, int C, int use_07_metric, double* ap, double* corloc,
+                  int32_t* counts, double* stats, uint16_t* tp_bits, uint16_t* fp_bits, int32_t* order,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* Model input boundary: GeneralizedMCNNWSL.preprocess_image
  * (projects/WSL/wsl/modeling/meta_arch/mcnn.py:303-318) + ImageList.from_tensors
  * (detectron2/structures/image_list.py:71-125) in one launch: images[b] is the mapper's uint8 (C, h_b, w_b) planar

@@ -26,7 +26,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # hardware queue was busy ("the side-stream anomaly": 10-11 of 12 forward passes wrong; 0 of 35 without
 # packed arithmetic; idle cycles after the loads / before the store change nothing).  These kernels are bound by
 # their bytes: the scalar form costs nothing measurable.
-FILE_FLAGS = {"semseg_ops.hip": ["-fno-slp-vectorize"]}
+#
+# voc_eval.hip without floating-point contraction: the evaluator's overlap is `a*b + c*d - inters` in fp64 and must have
+# the reference's bits (NumPy rounds each product and each sum); a fused multiply-add rounds once and gives others, and
+# a TP / FP decision at an IoU threshold hangs on the last bit.  No fast-math anywhere in FLAGS either.
+FILE_FLAGS = {"semseg_ops.hip": ["-fno-slp-vectorize"], "voc_eval.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target, deps):

@@ -1,0 +1,32 @@
+"""DatasetEvaluator and the plain inference loop (detectron2/evaluation/evaluator.py: DatasetEvaluator :15-55,
+inference_on_dataset :85-157 without its logging and timing)."""
+import torch
+
+
+class DatasetEvaluator:
+    """reset() / process(inputs, outputs) per batch / evaluate() at the end, as the reference's base class."""
+
+    def reset(self):
+        pass
+
+    def process(self, inputs, outputs):
+        pass
+
+    def evaluate(self):
+        pass
+
+
+def inference_on_dataset(model, data_loader, evaluator):
+    """Run `model` in eval mode under torch.no_grad() over `data_loader`, feed every batch to `evaluator` and return
+    evaluator.evaluate() ({} when that returns None, as the reference).  The model's mode is restored."""
+    evaluator.reset()
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for inputs in data_loader:
+                evaluator.process(inputs, model(inputs))
+    finally:
+        model.train(was_training)
+    results = evaluator.evaluate()
+    return {} if results is None else results
