@@ -1041,6 +1041,44 @@ int jtsm_voc_eval(const float* det_boxes, const float* det_scores, const int32_t
                   int32_t* counts, double* stats, uint16_t* tp_bits, uint16_t* fp_bits, int32_t* order,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Panoptic quality and the semantic confusion matrix on the device: what COCOPanopticEvaluator.process / evaluate do
+ * through PNG files and panopticapi.pq_compute (detectron2/evaluation/panoptic_evaluation.py:66-144) and what
+ * SemSegEvaluator.process does with one np.bincount per image (detectron2/evaluation/sem_seg_evaluation.py:82-93), on
+ * the maps where inference left them.  Semantics: DESIGN.md §4f (pq_compute_single_core of panopticapi).
+ *
+ * jtsm_pq_accumulate — ONE image per call, added into running per-category totals that stay on the device.
+ *   pred (pixels) int32 panoptic ids as jtsm_panoptic_combine writes them, 0 = VOID; pred_table (P,5) int32 rows {id,
+ *   isthing, category_id, instance_id, area} of which the first min(*num_pred, P) count (num_pred on the device; column
+ *   0 is looked up per pixel — ids need not be dense; column 4 is ignored, areas are counted); thing_cat (num_things) /
+ *   stuff_cat (num_stuff) int32: contiguous id -> evaluation category in [0, C), or -1.  gt (pixels) int32: 0 = VOID,
+ *   r + 1 = row r of gt_table (G,2) int32 {category in [0, C), iscrowd}.
+ *   Totals, added to (zero them before the first image): tp, fp, fn (C) int64; iou_sum (C) double, added sequentially
+ *   in gt-row order — bit-reproducible, equal to a sequential fp64 loop over (image, gt row); stats (4) int64 =
+ *   {pixels whose non-zero value names no row (either map; counted as VOID), rows of pred_table without a pixel, rows
+ *   (either table) whose category is -1 or out of range (left out of matching, fp and fn), images accumulated}.
+ *   The (G+1) x (P+1) pair histogram is built in LDS while it has at most jtsm_pq_lds_cells() counters, with global
+ *   atomics above (force_global != 0: always); both give the same integers.  (G+1)(P+1) <= 2^28, else JTSM_EINVAL.
+ *   workspace: jtsm_pq_accumulate_workspace_bytes(G, P, C), 256-byte aligned.
+ *
+ * jtsm_confusion_accumulate — conf[(C+1) * pred + gt'] += 1 per pixel, conf (C+1)^2 int64 with C = num_classes; pred
+ *   (pixels) int64 as jtsm_argmax_channels_f32 writes it; gt (pixels) uint8 or int32 (gt_elem_bytes 1 or 4); gt' = C
+ *   where gt == ignore_label.  A pixel whose pred is outside [0, C) or whose gt' is outside [0, C] is counted in
+ *   *stats (int64) and left out (np.bincount would raise or grow).  LDS histogram while (C+1)^2 <=
+ *   jtsm_confusion_lds_cells(), global atomics above (force_global != 0: always).
+ * Integer atomics only; maps are read with 16-byte loads when their addresses allow.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int jtsm_pq_lds_cells(void);
+int jtsm_confusion_lds_cells(void);
+size_t jtsm_pq_accumulate_workspace_bytes(int G, int P, int C);
+int jtsm_pq_accumulate(const int32_t* pred, const int32_t* pred_table, const int32_t* num_pred, int P,
+                       const int32_t* thing_cat, int num_things, const int32_t* stuff_cat, int num_stuff,
+                       const int32_t* gt, const int32_t* gt_table, int G, long pixels, int C, int64_t* tp, int64_t* fp,
+                       int64_t* fn, double* iou_sum, int64_t* stats, int force_global, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int jtsm_confusion_accumulate(const int64_t* pred, const void* gt, int gt_elem_bytes, long pixels, int num_classes,
+                              int ignore_label, int64_t* conf, int64_t* stats, int force_global, void* stream);
+
 /* Model input boundary: GeneralizedMCNNWSL.preprocess_image
  * (projects/WSL/wsl/modeling/meta_arch/mcnn.py:303-318) + ImageList.from_tensors
  * (detectron2/structures/image_list.py:71-125) in one launch: images[b] is the mapper's uint8 (C, h_b, w_b) planar

@@ -1,8 +1,15 @@
-"""Evaluation of the detectors.  Pascal VOC detection only: AP at IoU 0.50:0.05:0.95 and CorLoc on the device
-(jtsm_amd/csrc/voc_eval.hip).  Not here: gathering detections across ranks (comm.gather — evaluate one rank's
-detections, or concatenate before process()), COCO and panoptic evaluation, the reference's visualisation function and
-the results/VOC2007/Main/comp3_*.txt submission files."""
-from .evaluator import DatasetEvaluator, inference_on_dataset
+"""Evaluation on the device.  Pascal VOC detection: AP at IoU 0.50:0.05:0.95 and CorLoc (jtsm_amd/csrc/voc_eval.hip).
+Panoptic quality (PQ / SQ / RQ, all / things / stuff) and the semantic-segmentation metrics (mIoU, fwIoU, mACC, pACC)
+of the JTSM model (jtsm_amd/csrc/panoptic_eval.hip); with DatasetEvaluators they form the reference's
+`coco_panoptic_seg` evaluator list without its COCO box / mask AP.  Not here: gathering results across ranks
+(comm.gather — evaluate one rank's images, or concatenate before process()), COCO box / mask AP (pycocotools'
+arithmetic), the predictions' JSON / PNG / RLE dumps, the reference's visualisation function and the
+results/VOC2007/Main/comp3_*.txt submission files."""
+from .evaluator import DatasetEvaluator, DatasetEvaluators, inference_on_dataset
+from .panoptic_evaluation import COCOPanopticEvaluator, PanopticGroundTruth, pq_accumulate
 from .pascal_voc_evaluation import PascalVOCDetectionEvaluator, VOCGroundTruth, voc_eval
+from .sem_seg_evaluation import SemSegEvaluator, confusion_accumulate
 
-__all__ = ["DatasetEvaluator", "inference_on_dataset", "PascalVOCDetectionEvaluator", "VOCGroundTruth", "voc_eval"]
+__all__ = ["DatasetEvaluator", "DatasetEvaluators", "inference_on_dataset", "PascalVOCDetectionEvaluator",
+           "VOCGroundTruth", "voc_eval", "COCOPanopticEvaluator", "PanopticGroundTruth", "pq_accumulate",
+           "SemSegEvaluator", "confusion_accumulate"]

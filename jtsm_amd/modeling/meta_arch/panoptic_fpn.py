@@ -8,6 +8,15 @@ import torch
 from ...layers.postprocess import panoptic_combine
 
 
+class SegmentsInfo(list):
+    """The segments_info list, which also keeps `table`: the (n,5) int32 device rows {id, isthing, category_id,
+    instance_id, area} it was made from.  jtsm_amd.evaluation.COCOPanopticEvaluator reads those, not the dicts."""
+
+    def __init__(self, items=(), table=None):
+        super().__init__(items)
+        self.table = table
+
+
 @torch.no_grad()
 def combine_semantic_and_instance_outputs(instance_results, semantic_results, overlap_threshold, stuff_area_limit,
                                           instances_confidence_threshold, num_sem_classes=256):
@@ -20,7 +29,7 @@ def combine_semantic_and_instance_outputs(instance_results, semantic_results, ov
                                           num_sem_classes, overlap_threshold, stuff_area_limit,
                                           instances_confidence_threshold)
     rows, scores = table.tolist(), tscore.tolist()
-    segments_info = []
+    segments_info = SegmentsInfo(table=table)
     for (sid, isthing, category, inst, area), score in zip(rows, scores):
         if isthing:
             segments_info.append({"id": sid, "isthing": True, "score": score, "category_id": category,
