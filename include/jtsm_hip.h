@@ -1079,6 +1079,48 @@ int jtsm_pq_accumulate(const int32_t* pred, const int32_t* pred_table, const int
 int jtsm_confusion_accumulate(const int64_t* pred, const void* gt, int gt_elem_bytes, long pixels, int num_classes,
                               int ignore_label, int64_t* conf, int64_t* stats, int force_global, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * COCO box / mask AP on the device: COCOEvaluator's bbox and segm tasks (detectron2/evaluation/coco_evaluation.py) as
+ * COCOeval_opt computes them (evaluation/fast_eval_api.py; layers/csrc/cocoeval/cocoeval.cpp: EvaluateImages,
+ * Accumulate) with pycocotools' default parameters.  Semantics: DESIGN.md §4g.  T = 10 IoU thresholds and A = 4 area
+ * ranges are fixed; bit a * 10 + t of a record word belongs to (area range a, threshold t).
+ *
+ * jtsm_coco_image — ONE image and ONE task per call: ranks, IoUs and matches of the image's detections, one 32-byte
+ *   record each, and the image's non-ignored ground truth added into npos.
+ *   det_boxes (n,4) float32 XYXY, det_scores (n), det_classes (n) int32 in [0, K) (another value: counted in stats[0],
+ *   the detection is left out); det_masks (n, H, W) uint8 / bool, non-zero = set, or NULL.  Ground truth of the image
+ *   sorted by category, annotation order inside: gt_boxes (G,4) double XYWH, gt_area (G) double (the annotation's area
+ *   field), gt_crowd (G) uint8 (ignore := iscrowd), gt_cat_start (K+1) int32 CSR over the categories, gt_masks (G,
+ *   ceil(H W / 64)) 64-bit words — pixel p of the flat map is bit p % 64 of word p / 64, tail zero — or NULL.  The
+ *   task is segm when det_masks or gt_masks is given (then both where n > 0 / G > 0), else bbox.
+ *   iou_thrs (10) and area_rng (4,2) double ON THE DEVICE, used as passed.  max_det: detections kept per (image,
+ *   category), <= 128.
+ *   records (n, 4) int64 <- {int32 category (K: left out — a bad class or rank >= max_det), int32 image_index, int32
+ *   rank, float32 score, uint64 matched bits, uint64 ignore bits}, detection row order.  npos (K, 4) int64 and stats
+ *   (2) int64 are ADDED to (zero them before the first image).
+ *   Optional (NULL to skip): ious_debug (n, G) double <- the IoU of every same-category pair of a kept detection, -1
+ *   elsewhere; rank_debug (n) int32 <- rank or -1.
+ *   n <= 65535, G <= 4096 (one matched bit per 64 ground-truth rows in a lane's word), n G <= 2^28, else JTSM_EINVAL.
+ *   workspace: jtsm_coco_image_workspace_bytes(n, G, K, H, W, max_det) (H = W = 0 for bbox), 256-byte aligned.
+ *
+ * jtsm_coco_accumulate — the precision / scores (10, R, K, 4, M) and recall (10, K, 4, M) double tables, -1 where a
+ *   (category, area range) has no non-ignored ground truth, from the concatenated records (D, 4) of all images, in any
+ *   order: image_index in [0, N) must rise with the image id.  rec_thrs (R <= 1024) double and max_dets (M <= 8) int32
+ *   on the device.  bits(K) + bits(N-1) <= 25 (the sort key beside 32 score and 7 rank bits), else JTSM_EINVAL.
+ * Integer atomics only: deterministic.  Nothing is allocated or synchronised.
+ * ------------------------------------------------------------------------------------------------------------------ */
+size_t jtsm_coco_image_workspace_bytes(int n, int G, int K, int H, int W, int max_det);
+int jtsm_coco_image(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                    const uint8_t* det_masks, int n, int H, int W, const double* gt_boxes, const double* gt_area,
+                    const uint8_t* gt_crowd, const int32_t* gt_cat_start, const uint64_t* gt_masks, int G, int K,
+                    int image_index, int max_det, const double* iou_thrs, const double* area_rng, int64_t* records,
+                    int64_t* npos, int64_t* stats, double* ious_debug, int32_t* rank_debug, void* workspace,
+                    size_t workspace_bytes, void* stream);
+size_t jtsm_coco_accumulate_workspace_bytes(int D, int K);
+int jtsm_coco_accumulate(const int64_t* records, int D, int K, int N, const int64_t* npos, const double* rec_thrs,
+                         int R, const int32_t* max_dets, int M, double* precision, double* scores, double* recall,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Model input boundary: GeneralizedMCNNWSL.preprocess_image
  * (projects/WSL/wsl/modeling/meta_arch/mcnn.py:303-318) + ImageList.from_tensors
  * (detectron2/structures/image_list.py:71-125) in one launch: images[b] is the mapper's uint8 (C, h_b, w_b) planar

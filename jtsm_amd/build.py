@@ -30,7 +30,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # voc_eval.hip without floating-point contraction: the evaluator's overlap is `a*b + c*d - inters` in fp64 and must have
 # the reference's bits (NumPy rounds each product and each sum); a fused multiply-add rounds once and gives others, and
 # a TP / FP decision at an IoU threshold hangs on the last bit.  No fast-math anywhere in FLAGS either.
-FILE_FLAGS = {"semseg_ops.hip": ["-fno-slp-vectorize"], "voc_eval.hip": ["-ffp-contract=off"]}
+# coco_eval.hip likewise: the box IoU is `i = w*h; u = da + ga - i; o = i / u` as pycocotools rounds it.
+FILE_FLAGS = {"semseg_ops.hip": ["-fno-slp-vectorize"], "voc_eval.hip": ["-ffp-contract=off"],
+              "coco_eval.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target, deps):

@@ -1,10 +1,13 @@
 """Evaluation on the device.  Pascal VOC detection: AP at IoU 0.50:0.05:0.95 and CorLoc (jtsm_amd/csrc/voc_eval.hip).
 Panoptic quality (PQ / SQ / RQ, all / things / stuff) and the semantic-segmentation metrics (mIoU, fwIoU, mACC, pACC)
-of the JTSM model (jtsm_amd/csrc/panoptic_eval.hip); with DatasetEvaluators they form the reference's
-`coco_panoptic_seg` evaluator list without its COCO box / mask AP.  Not here: gathering results across ranks
-(comm.gather — evaluate one rank's images, or concatenate before process()), COCO box / mask AP (pycocotools'
-arithmetic), the predictions' JSON / PNG / RLE dumps, the reference's visualisation function and the
-results/VOC2007/Main/comp3_*.txt submission files."""
+of the JTSM model (jtsm_amd/csrc/panoptic_eval.hip).  COCO box / mask AP (AP, AP50, AP75, APs, APm, APl and per-category
+AP; jtsm_amd/csrc/coco_eval.hip).  DatasetEvaluators([SemSegEvaluator, COCOEvaluator, COCOPanopticEvaluator]) is the
+reference's `coco_panoptic_seg` evaluator list (projects/WSL/tools/train_net.py:163-174); COCOEvaluator alone serves its
+COCO detection configs.  Not here: gathering results across ranks (comm.gather — evaluate one rank's images, or
+concatenate before process()), keypoint and proposal (AR) evaluation, LVIS, polygon rasterisation, the predictions'
+JSON / PNG / RLE dumps, the reference's visualisation function and the results/VOC2007/Main/comp3_*.txt submission
+files."""
+from .coco_evaluation import COCOEvaluator, COCOGroundTruth, coco_accumulate, coco_image
 from .evaluator import DatasetEvaluator, DatasetEvaluators, inference_on_dataset
 from .panoptic_evaluation import COCOPanopticEvaluator, PanopticGroundTruth, pq_accumulate
 from .pascal_voc_evaluation import PascalVOCDetectionEvaluator, VOCGroundTruth, voc_eval
@@ -12,4 +15,5 @@ from .sem_seg_evaluation import SemSegEvaluator, confusion_accumulate
 
 __all__ = ["DatasetEvaluator", "DatasetEvaluators", "inference_on_dataset", "PascalVOCDetectionEvaluator",
            "VOCGroundTruth", "voc_eval", "COCOPanopticEvaluator", "PanopticGroundTruth", "pq_accumulate",
-           "SemSegEvaluator", "confusion_accumulate"]
+           "SemSegEvaluator", "confusion_accumulate", "COCOEvaluator", "COCOGroundTruth", "coco_image",
+           "coco_accumulate"]
