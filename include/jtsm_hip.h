@@ -937,6 +937,50 @@ int jtsm_mine_top_p_f32(const float* scores, int ld, const float* lse, const flo
                         int32_t* out_classes, float* out_scores, float* out_weights, int32_t* out_rows,
                         int32_t* out_num, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * C-MIL (cmil.hip).  Both operators take all images of the step (rows [bag_offsets[b], bag_offsets[b+1]) of every
+ * per-row array), compute pairwise_iou's expression where they need an IoU — no R x R matrix — and read nothing back.
+ *
+ * jtsm_roi_merge_forward_f32 <- ROIMerge_forward_cpu(S, J, C, D, P)
+ *   (projects/WSL/wsl/layers/csrc/ROIMerge/ROIMerge_cpu.cpp:33-232): S (R) the rows' summed MIL scores, boxes (R,4) in
+ *   place of J, C / D (R,K) with leading dimensions ldc / ldd, lam = getlambda(cur_iter / size_epoch, max_epoch)
+ *   (:11-17) evaluated by the caller in place of P.  Per image: rows ranked by S descending (equal S: lower row), the
+ *   first min(rows, 200) ranks walked greedily in windows of 40 (a rank joins the seed's clique unless its IoU with a
+ *   member is < lam), every other row its own clique in row order.  The cliques of all images are compacted: image
+ *   b's clique id is merged row merged_offsets[b] + id.  MC / MD (R,K) contiguous: the clique means, sum over the
+ *   members in ascending row order of C[n] / IC, un-contracted; I (R): a row's merged row; IC (R): members of a
+ *   merged row; merged_offsets (B+1).  Rows at and behind merged_offsets[B] are dead: MC = MD = 0, IC = 0.
+ *   max_bag_rows >= every image's rows (host int).  boxes 16-byte, workspace 256-byte aligned.
+ * jtsm_roi_merge_backward_f32 <- ROIMerge_backward_cpu (:234-287): dC[n] = gMC[I[n]] / IC[I[n]], dD likewise; gMC /
+ *   gMD (R,K) with leading dimension ld, dC / dD with ld_grad.  Dead rows of gMC / gMD are not read.
+ *
+ * jtsm_roi_label_f32 <- ROILabel_forward_cpu(S, U, L, CW, P) (.../ROILabel/ROILabel_cpu.cpp:16-194): S (R, ld) class
+ *   scores (score = S[r,c], or exp(S[r,c] - lse[r]) when lse != NULL), boxes (R,4) in place of U, classes (B,G) /
+ *   counts (B) the present classes ascending in place of L, CW (B, ld_cw) the image probabilities (NULL: the seed's
+ *   score is the weight), and fg, bg_hi, bg_lo, num_pos, num_neg, top_k in place of P.  perm (R): for every image a
+ *   permutation of 0 .. rows-1 at its rows' positions — the visiting order the reference draws with
+ *   srand(time(0)).  Seeds: per present class, top_k times, the best-scoring row no seed holds yet (first maximum);
+ *   none once the rows have run out.  Every row takes the seed of largest IoU (first maximum); visited in perm order it
+ *   gets the seed's class and weight when IoU >= fg and at most num_pos positives were taken before it, label
+ *   num_classes and the weight when bg_lo <= IoU < bg_hi and at most num_neg negatives were taken, otherwise the
+ *   seed's class and weight 0 (an image without seeds: num_classes, 0).  fg >= bg_hi is required.  labels (R),
+ *   weights (R); seed_rows (B, G * top_k): the seeds' rows within the image in picking order, -1 behind seed_num (B).
+ *   At most 256 seeds per image (G * top_k).  boxes 16-byte aligned.
+ * Deterministic: no atomics.
+ * ------------------------------------------------------------------------- */
+size_t jtsm_roi_merge_workspace_bytes(int B, int R);
+int jtsm_roi_merge_forward_f32(const float* S, const float* boxes, const float* C, int ldc, const float* D, int ldd,
+                               int K, const int32_t* bag_offsets, int B, int R, int max_bag_rows, float lam, float* MC,
+                               float* MD, int32_t* I, int32_t* IC, int32_t* merged_offsets, void* workspace,
+                               void* stream);
+int jtsm_roi_merge_backward_f32(const float* gMC, const float* gMD, int ld, int K, const int32_t* I, const int32_t* IC,
+                                int R, float* dC, float* dD, int ld_grad, void* stream);
+int jtsm_roi_label_f32(const float* S, int ld, const float* lse, const float* boxes, const int32_t* bag_offsets,
+                       const int32_t* classes, const int32_t* counts, int B, int G, const float* CW, int ld_cw,
+                       const int32_t* perm, float fg, float bg_hi, float bg_lo, int num_pos, int num_neg, int top_k,
+                       int num_classes, int32_t* labels, float* weights, int32_t* seed_rows, int32_t* seed_num,
+                       void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Inference / post-processing.  None of these entry points synchronises with the host: counts
  * that depend on the data are written to device memory.

@@ -31,8 +31,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # the reference's bits (NumPy rounds each product and each sum); a fused multiply-add rounds once and gives others, and
 # a TP / FP decision at an IoU threshold hangs on the last bit.  No fast-math anywhere in FLAGS either.
 # coco_eval.hip likewise: the box IoU is `i = w*h; u = da + ga - i; o = i / u` as pycocotools rounds it.
+# cmil.hip likewise: ROIMerge's clique means are `sum += C[n] / IC`, each quotient and each sum rounded.
 FILE_FLAGS = {"semseg_ops.hip": ["-fno-slp-vectorize"], "voc_eval.hip": ["-ffp-contract=off"],
-              "coco_eval.hip": ["-ffp-contract=off"]}
+              "coco_eval.hip": ["-ffp-contract=off"], "cmil.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target, deps):

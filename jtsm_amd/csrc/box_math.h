@@ -21,6 +21,21 @@ __device__ __forceinline__ void decode_box(const float* __restrict__ p, const fl
   out[3] = pcy + 0.5f * ph;
 }
 
+// detectron2's pairwise_iou in float32, every step rounded on its own (PCL's graph and cluster assignment, C-MIL's
+// ROIMerge and ROILabel: none of them builds the R x R matrix the reference reads these values from)
+__device__ __forceinline__ float box_iou(const float4 a, const float4 b) {
+#pragma clang fp contract(off)
+  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f);
+  const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
+  const float inter = w * h;
+  const float aa = (a.z - a.x) * (a.w - a.y), ab = (b.z - b.x) * (b.w - b.y);
+  return inter > 0.f ? inter / (aa + ab - inter) : 0.f;
+}
+
+__device__ __forceinline__ float4 load_box(const float* __restrict__ boxes, long r) {
+  return *reinterpret_cast<const float4*>(boxes + r * 4);
+}
+
 // torchvision's nms IoU test (ops/csrc/cuda/nms_cuda.cu devIoU @0.8.1; the CPU kernel computes the same expression)
 __device__ __forceinline__ bool iou_above(const float4& a, const float4& b, float thr) {
 #pragma clang fp contract(off)

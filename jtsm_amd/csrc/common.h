@@ -42,6 +42,19 @@ inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 // +0 — the plane of a stored -0 then depended on the element's position (tests/test_hip_planes.py).
 __device__ __forceinline__ _Float16 f16_plane(float v, int shift) { return (_Float16)__builtin_ldexpf(v, shift); }
 
+// float -> unsigned whose order is the float order, NaN above everything (torch.topk / sort put NaN first in a
+// descending order), -0 = +0
+__device__ __forceinline__ unsigned ordered_bits(float v) {
+  if (v != v) return 0xffffffffu;
+  const unsigned u = __float_as_uint(v + 0.f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// Total order of (value, index) pairs — higher key = earlier: value descending, then index ascending.  A position in
+// that order is the NUMBER OF KEYS ABOVE one's own: counted, not sorted (mist.hip, cmil.hip).
+__device__ __forceinline__ unsigned long long order_key(float v, int index) {
+  return ((unsigned long long)ordered_bits(v) << 32) | (unsigned long long)(0xffffffffu - (unsigned)index);
+}
+
 // ordered compaction of a per-thread flag over the 256 threads of the workgroup: returns this thread's slot (if
 // flagged) and the total; two barriers.
 __device__ __forceinline__ int compact256(bool flag, int* __restrict__ wave_count, int& total) {

@@ -40,17 +40,7 @@ constexpr int kThreads = 1024;
 constexpr int kOwn = 8;         // rows a thread counts for in one pass of mist_topk
 constexpr int kTile = 4096;     // keys in LDS at a time
 
-// float -> unsigned whose order is the float order, NaN above everything (torch.topk / sort put NaN first in a
-// descending order), -0 = +0
-__device__ __forceinline__ unsigned ordered_bits(float v) {
-  if (v != v) return 0xffffffffu;
-  const unsigned u = __float_as_uint(v + 0.f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-// higher key = earlier: score descending, then index ascending
-__device__ __forceinline__ u64 order_key(float v, int index) {
-  return ((u64)ordered_bits(v) << 32) | (u64)(0xffffffffu - (unsigned)index);
-}
+// (ordered_bits, order_key — score descending, then index ascending: common.h)
 
 __device__ __forceinline__ float class_score(const float* __restrict__ scores, int ld, const float* __restrict__ lse,
                                              int r, int cls) {

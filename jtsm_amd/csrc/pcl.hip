@@ -35,6 +35,7 @@
 // the same inputs give the same tables on every run.
 #include <algorithm>
 
+#include "box_math.h"
 #include "common.h"
 
 namespace jtsm {
@@ -54,19 +55,7 @@ using u64 = unsigned long long;
 
 __device__ __forceinline__ float clip_prob(float v) { return fminf(fmaxf(v, kClipLo), kClipHi); }
 
-// detectron2's pairwise_iou in float32, every step rounded on its own
-__device__ __forceinline__ float box_iou(const float4 a, const float4 b) {
-#pragma clang fp contract(off)
-  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f);
-  const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
-  const float inter = w * h;
-  const float aa = (a.z - a.x) * (a.w - a.y), ab = (b.z - b.x) * (b.w - b.y);
-  return inter > 0.f ? inter / (aa + ab - inter) : 0.f;
-}
-
-__device__ __forceinline__ float4 load_box(const float* __restrict__ boxes, long r) {
-  return *reinterpret_cast<const float4*>(boxes + r * 4);
-}
+// (box_iou — detectron2's pairwise_iou, un-contracted — and load_box: box_math.h)
 
 // Workgroup reductions: a butterfly inside the wavefront (both partners form the same sum, so every lane holds the
 // same value), then a fold of the per-wave values in wave order.  `slot` is a __shared__ array of one value per wave.

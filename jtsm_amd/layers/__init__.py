@@ -1,6 +1,7 @@
 """Operator layer of the MI355X JTSM hot path: the names model code imports from
 ``detectron2.layers`` / ``wsl.layers`` (detectron2/layers/__init__.py:1-13,
 projects/WSL/wsl/layers/__init__.py:1-11) that lie on the path."""
+from .cmil import ROILabel, ROIMerge, roi_label, roi_merge
 from .mist import mine_top_p
 from .moi_pool import MOIPool, moi_pool
 from .roi_align import ROIAlign, roi_align

@@ -8,5 +8,6 @@ from .roi_heads import ROI_HEADS_REGISTRY, ROIHeads, StandardROIHeads, build_roi
 from .roi_heads_jtsm import JTSMROIHeads
 from .roi_heads_contextlocnet import ContextLocNetROIHeads
 from .fast_rcnn_wsddn import WSDDNOutputLayers
+from .roi_heads_cmil import CMILROIHeads
 from .roi_heads_oicr import OICRROIHeads
 from .roi_heads_pcl import PCLROIHeads

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ...layers.cmil import ROIMerge
 from ...layers.wrappers import Linear, cat
 from ...layers.wsl_losses import mil_loss, mil_scores
 from ...structures import Instances
@@ -20,10 +21,12 @@ from .fast_rcnn_oicr import fast_rcnn_inference
 
 class WSDDNOutputLayers(nn.Module):
     def __init__(self, input_size, *, num_classes, box2box_transform, test_score_thresh=0.0, test_nms_thresh=0.5,
-                 test_topk_per_image=100, mean_loss=True, loss_weight=1.0, cmil=False):
+                 test_topk_per_image=100, mean_loss=True, loss_weight=1.0, cmil=False, display=1280, max_epoch=40,
+                 size_epoch=5000):
         super().__init__()
+        self.cmil = cmil
         if cmil:
-            raise NotImplementedError("WSDDNOutputLayers: the CMIL variant (WSL.CMIL) is not implemented")
+            self.roi_merge = ROIMerge(display, max_epoch, size_epoch)
         self.num_classes = num_classes
         self.box_dim = 4
         self.cls = Linear(input_size, num_classes)
@@ -46,7 +49,8 @@ class WSDDNOutputLayers(nn.Module):
                    test_score_thresh=cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST,
                    test_nms_thresh=cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST,
                    test_topk_per_image=cfg.TEST.DETECTIONS_PER_IMAGE, mean_loss=cfg.WSL.MEAN_LOSS,
-                   cmil=cfg.WSL.CMIL)
+                   cmil=cfg.WSL.CMIL, display=int(1280 / cfg.SOLVER.IMS_PER_BATCH),
+                   max_epoch=int(cfg.SOLVER.MAX_ITER / cfg.WSL.SIZE_EPOCH), size_epoch=cfg.WSL.SIZE_EPOCH)
 
     def logits(self, x, context=False):
         """(C, D): cls(x) and det(x); with context=True x = (box, frame, context) features and D = det(frame) -
@@ -74,6 +78,21 @@ class WSDDNOutputLayers(nn.Module):
         loss, scores, probs = mil_loss(cls_logits, det_logits, bag_offsets, gt_classes_img_oh, self.mean_loss,
                                        max_bag_rows)
         return {"loss_cls": loss * self.loss_weight.get("loss_cls", 1.0)}, scores, probs
+
+    def score_and_loss_cmil(self, cls_logits, det_logits, boxes, bag_offsets, gt_classes_img_oh, max_bag_rows):
+        """The fused C-MIL form (forward_cmil :621-667 + losses): the un-merged MIL scores (detached), their row sums
+        as ROIMerge's ranking, the merge of C and D, and the MIL loss on the merged bags, whose offsets and row counts
+        never leave the device.  -> (losses, un-merged scores detached, image probabilities of the merged bags, aux)."""
+        with torch.no_grad():
+            _, scores, _ = mil_loss(cls_logits.detach(), det_logits.detach(), bag_offsets, gt_classes_img_oh,
+                                    self.mean_loss, max_bag_rows)
+            row_sums = scores.sum(dim=1)
+        lam = self.roi_merge.lam
+        MC, MD, I, IC, merged_offsets = self.roi_merge(row_sums, boxes, cls_logits, det_logits, bag_offsets, max_bag_rows)
+        loss, _, probs = mil_loss(MC, MD, merged_offsets, gt_classes_img_oh, self.mean_loss, max_bag_rows)
+        aux = {"merge_scores": row_sums, "merge_rows": I, "merge_counts": IC, "merged_offsets": merged_offsets,
+               "merge_lambda": lam}
+        return {"loss_cls": loss * self.loss_weight.get("loss_cls", 1.0)}, scores, probs, aux
 
     def predict_probs_img(self, predictions, proposals: List[Instances]):
         scores, _ = predictions
