@@ -1007,6 +1007,26 @@ int jtsm_batched_nms_f32(const float* boxes, const float* scores, const int64_t*
                          int max_per_class, float iou_threshold, int coordinate_trick, int64_t* keep,
                          int32_t* num_keep, int32_t* overflow, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Rotated boxes (cx, cy, w, h, angle in degrees): detectron2/layers/rotated_boxes.py:6-21 pairwise_iou_rotated ->
+ * csrc/box_iou_rotated/box_iou_rotated_cuda.cu, and detectron2/layers/nms.py:35-139 nms_rotated / batched_nms_rotated
+ * -> csrc/nms_rotated/nms_rotated_cuda.cu.  The IoU of a pair is the device branch of box_iou_rotated_utils.h, every
+ * operation rounded on its own (no fused multiply-add), in that header's types.
+ *
+ * jtsm_box_iou_rotated_f32: ious (N,M) <- IoU of boxes1 (N,5) and boxes2 (M,5).  N == 0 or M == 0: nothing to do.
+ *
+ * jtsm_batched_nms_rotated_f32: greedy NMS within each class.  boxes (n,5), scores (n), idxs (n) int64 in
+ * [0, num_classes) (anything else drops the element) or NULL: one class (num_classes must be 1; that is nms_rotated).
+ * Classes are segments of the sorted list and the boxes are NOT offset: the reference's `boxes + idxs * (max - min +
+ * 1)` on the fp32 centres is a way to the same separation that perturbs the centres' low bits.  max_per_class, keep
+ * (survivors first, descending score, equal scores: lower index first), *num_keep (device), *overflow (device,
+ * optional) and "nothing is read back" as jtsm_batched_nms_f32.  IoU test: iou > iou_threshold, as
+ * nms_rotated_cuda.cu (the reference's CPU kernel tests >=). */
+int jtsm_box_iou_rotated_f32(const float* boxes1, const float* boxes2, int N, int M, float* ious, void* stream);
+size_t jtsm_batched_nms_rotated_workspace_bytes(int n, int num_classes, int max_per_class);
+int jtsm_batched_nms_rotated_f32(const float* boxes, const float* scores, const int64_t* idxs, int n, int num_classes,
+                                 int max_per_class, float iou_threshold, int64_t* keep, int32_t* num_keep,
+                                 int32_t* overflow, void* workspace, size_t workspace_bytes, void* stream);
+
 /* fast_rcnn_inference_single_image (projects/WSL/wsl/modeling/roi_heads/fast_rcnn_oicr.py:100-163) in one call:
  * rows with a non-finite box or score are dropped, boxes (R, Kb*4), Kb in {1, K}, are clipped to (img_h, img_w),
  * every (row, class < K) with scores (R, K+1) > score_thresh becomes a candidate, batched_nms (above, trick mode 2),

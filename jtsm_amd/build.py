@@ -32,8 +32,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # a TP / FP decision at an IoU threshold hangs on the last bit.  No fast-math anywhere in FLAGS either.
 # coco_eval.hip likewise: the box IoU is `i = w*h; u = da + ga - i; o = i / u` as pycocotools rounds it.
 # cmil.hip likewise: ROIMerge's clique means are `sum += C[n] / IC`, each quotient and each sum rounded.
+# rotated_boxes.hip likewise: the IoU is box_iou_rotated_utils.h with every product and sum rounded, as tests/rotated_ref.py.
 FILE_FLAGS = {"semseg_ops.hip": ["-fno-slp-vectorize"], "voc_eval.hip": ["-ffp-contract=off"],
-              "coco_eval.hip": ["-ffp-contract=off"], "cmil.hip": ["-ffp-contract=off"]}
+              "coco_eval.hip": ["-ffp-contract=off"], "cmil.hip": ["-ffp-contract=off"],
+              "rotated_boxes.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target, deps):

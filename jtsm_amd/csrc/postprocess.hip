@@ -5,16 +5,13 @@
 // (data-dependent counts stay in device memory until the caller asks for them).
 #include "box_math.h"
 #include "common.h"
-
-#include <hipcub/hipcub.hpp>
+#include "nms_stages.h"
 
 #include <algorithm>
 #include <cstdint>
 
 namespace jtsm {
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kMaxHeads = 8;
 struct HeadPtrs { const float* p[kMaxHeads]; };
@@ -75,34 +72,8 @@ __global__ __launch_bounds__(256) void oicr_predict_kernel(HeadPtrs logits, Head
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Greedy per-class NMS.  Elements live in a flat array (box, score, class); class == num_classes marks a dropped
-// element.  Stages: 64-bit keys (class, descending score) -> radix sort -> class segment starts -> 64x64 IoU bit
-// matrix restricted to W column words per row (a class never has more than max_per_class members) -> one wavefront
-// per class walks its segment -> second radix sort puts the survivors first, by descending score, ties by index.
-struct NmsHeader {
-  int n_valid;      // elements with class < num_classes
-  int max_coord;    // order-preserving int image of the largest coordinate among valid boxes
-  int num_keep;
-  int overflow;     // a class had more members than max_per_class allows
-};
-
-__device__ __forceinline__ unsigned ordered_desc(float f) {   // larger float -> smaller key (-0 sorts after +0)
-  unsigned u = __float_as_uint(f);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~u;
-}
-__device__ __forceinline__ int float_to_ordered_int(float f) {
-  const int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float ordered_int_to_float(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-
-__global__ void nms_header_init(NmsHeader* h) {
-  h->n_valid = 0;
-  h->max_coord = float_to_ordered_int(-INFINITY);
-  h->num_keep = 0;
-  h->overflow = 0;
-}
+// Greedy per-class NMS.  The stages that do not look at a box (keys, sort, segments, scan, final order) are in
+// nms_stages.h; here are the element writers, the axis-aligned 64x64 IoU bit-matrix kernel and the detection output.
 
 // per-row validity of fast_rcnn_inference_single_image (fast_rcnn_oicr.py:129-133): every box coordinate and every
 // score (background column included) finite.  One wavefront per row.
@@ -116,17 +87,6 @@ __global__ __launch_bounds__(256) void det_row_valid_kernel(const float* __restr
   for (int j = lane; j < lds_; j += 64) ok = ok && isfinite(scores[(size_t)r * lds_ + j]);
   ok = __all(ok);
   if (lane == 0) valid[r] = ok ? 1 : 0;
-}
-
-__device__ __forceinline__ void header_accumulate(NmsHeader* h, bool ok, float cmax) {
-  // wave-level reduction, then one atomic per wavefront (integer atomics: order-independent results)
-  const u64 b = __ballot(ok);
-  int m = ok ? float_to_ordered_int(cmax) : float_to_ordered_int(-INFINITY);
-  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0 && b) {
-    atomicAdd(&h->n_valid, __popcll(b));
-    atomicMax(&h->max_coord, m);
-  }
 }
 
 // elements of fast_rcnn_inference_single_image: e = r * K + k; clipped class-k box of row r, its score, class k or
@@ -179,26 +139,6 @@ __global__ __launch_bounds__(256) void nms_elements_kernel(const float4* __restr
     cmax = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
   }
   header_accumulate(h, ok, cmax);
-}
-
-__global__ __launch_bounds__(256) void nms_keys_kernel(const float* __restrict__ escore, const int* __restrict__ eclass,
-                                                       int N, u64* __restrict__ key, int* __restrict__ iota) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= N) return;
-  key[e] = ((u64)(unsigned)eclass[e] << 32) | ordered_desc(escore[e]);
-  iota[e] = e;
-}
-
-// seg[c] = first sorted position whose class is >= c, c = 0..K (seg[K] = number of valid elements)
-__global__ void nms_segments_kernel(const u64* __restrict__ keys, int N, int K, int* __restrict__ seg) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c > K) return;
-  int lo = 0, hi = N;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if ((int)(keys[mid] >> 32) < c) lo = mid + 1; else hi = mid;
-  }
-  seg[c] = lo;
 }
 
 // trick: 0 plain per-class, 1 torchvision's coordinate offsets, 2 offsets iff fewer than 40000 valid elements
@@ -255,81 +195,6 @@ __global__ __launch_bounds__(64) void nms_bits_kernel(const float4* __restrict__
   mask[(size_t)p * W + y] = bits;
 }
 
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-  const int lo = __shfl((int)(unsigned)(v & 0xffffffffull), src);
-  const int hi = __shfl((int)(unsigned)(v >> 32), src);
-  return ((u64)(unsigned)hi << 32) | (unsigned)lo;
-}
-
-// One wavefront per class walks its segment in score order.  Per 64-row block: the intra-block decisions are made
-// from register-resident words (no memory latency in the serial chain), then every lane ORs the kept rows' words
-// of one later column block into the LDS-resident `removed` vector (independent loads, all in flight together).
-__global__ __launch_bounds__(64) void nms_scan_kernel(const u64* __restrict__ mask, int W,
-                                                      const int* __restrict__ seg, uint8_t* __restrict__ kept,
-                                                      NmsHeader* h) {
-  extern __shared__ u64 removed[];   // 2W words
-  const int c = blockIdx.x, lane = threadIdx.x;
-  const int s = seg[c], e = seg[c + 1];
-  if (s >= e) return;
-  const int b0 = s >> 6, b1 = (e - 1) >> 6;
-  if (b1 - b0 >= W) {   // more members than the caller promised
-    if (lane == 0) atomicExch(&h->overflow, 1);
-    return;
-  }
-  for (int w = lane; w < 2 * W; w += 64) removed[w] = 0;
-  __syncthreads();
-  int total = 0;
-  for (int b = b0; b <= b1; ++b) {
-    const int p = b * 64 + lane;
-    const bool valid = p >= s && p < e;
-    const u64 own = valid ? mask[(size_t)p * W] : 0ull;
-    u64 cur = removed[b - b0];
-    const u64 vbits = __ballot(valid);
-    u64 keptbits = 0;
-    for (int j = 0; j < 64; ++j) {
-      const u64 o = shfl64(own, j);
-      if (((vbits >> j) & 1) && !((cur >> j) & 1)) {
-        keptbits |= 1ull << j;
-        cur |= o;
-      }
-    }
-    if (valid) kept[p] = (uint8_t)((keptbits >> lane) & 1);
-    total += __popcll(keptbits);
-    for (int w = 1 + lane; w < W; w += 64) {
-      // every row of the block is read (independent loads, all in flight together) and masked by its kept bit:
-      // cheaper than a dependent load per kept row
-      const u64* col = mask + (size_t)b * 64 * W + w;
-      u64 acc = 0;
-#pragma unroll 16
-      for (int j = 0; j < 64; ++j) acc |= col[(size_t)j * W] & (0ull - ((keptbits >> j) & 1ull));
-      removed[b - b0 + w] |= acc;
-    }
-    __syncthreads();
-  }
-  if (lane == 0) atomicAdd(&h->num_keep, total);
-}
-
-__global__ __launch_bounds__(256) void nms_final_keys_kernel(const int* __restrict__ sidx,
-                                                             const uint8_t* __restrict__ kept,
-                                                             const float* __restrict__ escore, int N,
-                                                             u64* __restrict__ key2) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= N) return;
-  const int e = sidx[p];
-  key2[e] = ((u64)(kept[p] ? 0u : 1u) << 32) | ordered_desc(escore[e]);
-}
-
-__global__ __launch_bounds__(256) void nms_emit_keep_kernel(const int* __restrict__ order, int n,
-                                                            const NmsHeader* __restrict__ h, int64_t* __restrict__ keep,
-                                                            int* __restrict__ num_keep, int* __restrict__ overflow) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) keep[i] = order[i];
-  if (i == 0) {
-    *num_keep = h->num_keep;
-    if (overflow) *overflow = h->overflow;
-  }
-}
-
 __global__ __launch_bounds__(256) void det_emit_kernel(const int* __restrict__ order, const float4* __restrict__ ebox,
                                                        const float* __restrict__ escore, int K, int topk, int cap,
                                                        const NmsHeader* __restrict__ h, float4* __restrict__ out_boxes,
@@ -355,88 +220,15 @@ __global__ __launch_bounds__(256) void det_emit_kernel(const int* __restrict__ o
   }
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct NmsLayout {
-  int N, W, nblk, K;
-  size_t header, ebox, escore, eclass, key_a, key_b, iota, sidx, order, seg, kept, rowvalid, mask, cub, total;
-  size_t cub_bytes;
-};
-
-size_t cub_temp_bytes(int N) {
-  size_t a = 0, b = 0;
-  u64* k = nullptr;
-  int* v = nullptr;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, k, k, v, v, N, 0, 64, (hipStream_t) nullptr);
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, k, k, v, v, N, 0, 33, (hipStream_t) nullptr);
-  return a > b ? a : b;
-}
-
-NmsLayout nms_layout(int N, int K, int max_per_class, int R) {
-  NmsLayout l = {};
-  l.N = N; l.K = K;
-  l.W = ceil_div(max_per_class > 0 ? max_per_class : 1, 64) + 1;
-  l.nblk = ceil_div(N > 0 ? N : 1, 64);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += align256(bytes); return at; };
-  l.header = take(sizeof(NmsHeader));
-  l.ebox = take((size_t)N * 16);
-  l.escore = take((size_t)N * 4);
-  l.eclass = take((size_t)N * 4);
-  l.key_a = take((size_t)N * 8);
-  l.key_b = take((size_t)N * 8);
-  l.iota = take((size_t)N * 4);
-  l.sidx = take((size_t)N * 4);
-  l.order = take((size_t)N * 4);
-  l.seg = take((size_t)(K + 2) * 4);
-  l.kept = take((size_t)l.nblk * 64);
-  l.rowvalid = take((size_t)(R > 0 ? R : 1));
-  l.mask = take((size_t)l.nblk * 64 * l.W * 8);
-  l.cub_bytes = N > 0 ? cub_temp_bytes(N) : 0;
-  l.cub = take(l.cub_bytes);
-  l.total = o;
-  return l;
-}
-
-int bits_for(int k) {   // bits needed to hold values 0..k
-  int b = 1;
-  while ((1 << b) <= k) ++b;
-  return b;
-}
-
-// elements already written (ebox / escore / eclass / header); runs sort -> bits -> scan -> sort
+// elements already written (ebox / escore / eclass / header); runs sort -> bits -> scan -> sort (nms_stages.h)
 int nms_core(char* ws, const NmsLayout& l, float thr, int trick, hipStream_t st) {
-  const int N = l.N, K = l.K;
-  NmsHeader* h = reinterpret_cast<NmsHeader*>(ws + l.header);
-  float4* ebox = reinterpret_cast<float4*>(ws + l.ebox);
-  float* escore = reinterpret_cast<float*>(ws + l.escore);
-  int* eclass = reinterpret_cast<int*>(ws + l.eclass);
-  u64* key_a = reinterpret_cast<u64*>(ws + l.key_a);
-  u64* key_b = reinterpret_cast<u64*>(ws + l.key_b);
-  int* iota = reinterpret_cast<int*>(ws + l.iota);
-  int* sidx = reinterpret_cast<int*>(ws + l.sidx);
-  int* order = reinterpret_cast<int*>(ws + l.order);
-  int* seg = reinterpret_cast<int*>(ws + l.seg);
-  uint8_t* kept = reinterpret_cast<uint8_t*>(ws + l.kept);
-  u64* mask = reinterpret_cast<u64*>(ws + l.mask);
-  size_t cub_bytes = l.cub_bytes;
-  hipLaunchKernelGGL(nms_keys_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, escore, eclass, N, key_a, iota);
-  JTSM_CHECK_LAUNCH("nms keys");
-  JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + l.cub, cub_bytes, key_a, key_b, iota, sidx, N, 0,
-                                                    32 + bits_for(K), st));
-  hipLaunchKernelGGL(nms_segments_kernel, dim3(ceil_div(K + 1, 64)), dim3(64), 0, st, key_b, N, K, seg);
-  JTSM_CHECK_LAUNCH("nms segments");
-  hipLaunchKernelGGL(nms_bits_kernel, dim3(l.nblk, l.W), dim3(64), 0, st, ebox, key_b, sidx, N, K, l.W, thr, trick, h,
-                     mask);
-  JTSM_CHECK_LAUNCH("nms bits");
-  JTSM_CHECK_HIP(hipMemsetAsync(kept, 0, (size_t)l.nblk * 64, st));
-  hipLaunchKernelGGL(nms_scan_kernel, dim3(K), dim3(64), (size_t)2 * l.W * sizeof(u64), st, mask, l.W, seg, kept, h);
-  JTSM_CHECK_LAUNCH("nms scan");
-  hipLaunchKernelGGL(nms_final_keys_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, sidx, kept, escore, N, key_a);
-  JTSM_CHECK_LAUNCH("nms final keys");
-  cub_bytes = l.cub_bytes;
-  JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + l.cub, cub_bytes, key_a, key_b, iota, order, N, 0, 33, st));
-  return JTSM_OK;
+  const float4* ebox = reinterpret_cast<const float4*>(ws + l.ebox);
+  return nms_stages(ws, l, st, [&](const u64* keys, const int* sidx, NmsHeader* h, u64* mask) {
+    hipLaunchKernelGGL(nms_bits_kernel, dim3(l.nblk, l.W), dim3(64), 0, st, ebox, keys, sidx, l.N, l.K, l.W, thr, trick, h,
+                       mask);
+    JTSM_CHECK_LAUNCH("nms bits");
+    return (int)JTSM_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------

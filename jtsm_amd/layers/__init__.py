@@ -4,9 +4,11 @@ projects/WSL/wsl/layers/__init__.py:1-11) that lie on the path."""
 from .cmil import ROILabel, ROIMerge, roi_label, roi_merge
 from .mist import mine_top_p
 from .moi_pool import MOIPool, moi_pool
+from .nms import batched_nms, batched_nms_rotated, nms_rotated
 from .roi_align import ROIAlign, roi_align
 from .roi_align_rotated import ROIAlignRotated, roi_align_rotated
 from .roi_loop_pool import ROILoopPool, roi_loop_pool
 from .roi_pool import ROIPool, roi_pool
+from .rotated_boxes import pairwise_iou_rotated
 
 __all__ = [k for k in globals().keys() if not k.startswith("_")]

@@ -66,6 +66,28 @@ def batched_nms_device(boxes, scores, idxs, iou_threshold, num_classes, max_per_
 
 
 @torch.no_grad()
+def batched_nms_rotated_device(boxes, scores, idxs, iou_threshold, num_classes, max_per_class):
+    """Rotated (n,5) boxes (csrc/rotated_boxes.hip); idxs None: one class.  Returns as batched_nms_device."""
+    L.require_gpu(boxes, scores, idxs)
+    n = boxes.shape[0]
+    dev = boxes.device
+    keep = torch.empty(n, dtype=torch.int64, device=dev)
+    num = torch.zeros(1, dtype=torch.int32, device=dev)
+    ovf = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return keep, num, ovf
+    boxes = boxes.to(torch.float32).contiguous()
+    scores = scores.to(torch.float32).contiguous()
+    idxs = None if idxs is None else idxs.to(torch.int64).contiguous()
+    lib = L.lib()
+    ws = _ws(lib.jtsm_batched_nms_rotated_workspace_bytes(n, int(num_classes), int(max_per_class)), dev)
+    L.check(lib.jtsm_batched_nms_rotated_f32(L.ptr(boxes), L.ptr(scores), L.ptr(idxs), n, int(num_classes),
+                                             int(max_per_class), iou_threshold, L.ptr(keep), L.ptr(num), L.ptr(ovf),
+                                             L.ptr(ws), ws.numel(), L.stream()), "batched_nms_rotated")
+    return keep, num, ovf
+
+
+@torch.no_grad()
 def fast_rcnn_inference_device(boxes, scores, image_shape, score_thresh, nms_thresh, topk):
     """One image of fast_rcnn_inference_single_image on the device.  boxes (R, 4*Kb), scores (R, K+1).
     -> dict(boxes (cap,4), scores, classes, rows, count (1,) int32); cap = topk, or R*K when topk < 0."""

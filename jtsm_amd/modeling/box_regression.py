@@ -41,3 +41,36 @@ class Box2BoxTransform:
         new_size = torch.exp(torch.clamp(d[..., 2:] / w[2:], max=self.scale_clamp)) * size
         out = torch.cat((new_centre - 0.5 * new_size, new_centre + 0.5 * new_size), dim=-1)
         return out.reshape(n, -1)
+
+
+class Box2BoxTransformRotated:
+    """Call surface of detectron2/modeling/box_regression.py:115-222: deltas (dx, dy, dw, dh, da) between
+    (cx, cy, w, h, angle) boxes.  Box angles are degrees, angle deltas are radians; a decoded angle is brought to
+    [-180, 180)."""
+
+    def __init__(self, weights, scale_clamp: float = _DEFAULT_SCALE_CLAMP):
+        self.weights = weights          # (wx, wy, ww, wh, wa)
+        self.scale_clamp = scale_clamp
+
+    def get_deltas(self, src_boxes, target_boxes):
+        """Deltas that map src_boxes (N,5) onto target_boxes (N,5)."""
+        assert isinstance(src_boxes, torch.Tensor) and isinstance(target_boxes, torch.Tensor)
+        assert bool((src_boxes[:, 2] > 0).all()), "Input boxes to Box2BoxTransformRotated are not valid!"
+        w = src_boxes.new_tensor(self.weights)
+        shift = w[:2] * (target_boxes[:, :2] - src_boxes[:, :2]) / src_boxes[:, 2:4]
+        scale = w[2:4] * torch.log(target_boxes[:, 2:4] / src_boxes[:, 2:4])
+        turn = (target_boxes[:, 4:5] - src_boxes[:, 4:5] + 180.0) % 360.0 - 180.0
+        return torch.cat((shift, scale, turn * (w[4] * math.pi / 180.0)), dim=1)
+
+    def apply_deltas(self, deltas, boxes):
+        """deltas (N, k*5) for k classes, boxes (N,5) -> predicted boxes (N, k*5)."""
+        assert deltas.shape[1] % 5 == 0 and boxes.shape[1] == 5
+        boxes = boxes.to(deltas.dtype)
+        n = deltas.shape[0]
+        d = deltas.reshape(n, -1, 5)
+        centre, size, angle = boxes[:, None, :2], boxes[:, None, 2:4], boxes[:, None, 4:5]
+        w = deltas.new_tensor(self.weights)
+        new_centre = d[..., :2] / w[:2] * size + centre
+        new_size = torch.exp(torch.clamp(d[..., 2:4] / w[2:4], max=self.scale_clamp)) * size
+        new_angle = (d[..., 4:5] / w[4] * 180.0 / math.pi + angle + 180.0) % 360.0 - 180.0
+        return torch.cat((new_centre, new_size, new_angle), dim=-1).reshape(n, -1)

@@ -106,7 +106,7 @@ class RPN(nn.Module):
         n = len(gt_labels)
         labels = torch.stack(gt_labels)                                  # (N, sum A)
         pos = labels == 1
-        flat = Boxes.cat(anchors).tensor
+        flat = type(anchors[0]).cat(anchors).tensor
         target = torch.stack([self.box2box_transform.get_deltas(flat, b) for b in gt_boxes])
         diff = (cat(pred_anchor_deltas, dim=1)[pos] - target[pos]).abs()
         if self.smooth_l1_beta >= 1e-5:

@@ -11,3 +11,4 @@ from .fast_rcnn_wsddn import WSDDNOutputLayers
 from .roi_heads_cmil import CMILROIHeads
 from .roi_heads_oicr import OICRROIHeads
 from .roi_heads_pcl import PCLROIHeads
+from .rotated_fast_rcnn import RotatedFastRCNNOutputLayers, RROIHeads, fast_rcnn_inference_rotated

@@ -15,15 +15,17 @@ from .fast_rcnn_oicr import fast_rcnn_inference
 
 
 class FastRCNNOutputLayers(nn.Module):
+    box_dim, transform_type = 4, Box2BoxTransform     # (5, Box2BoxTransformRotated in RotatedFastRCNNOutputLayers)
+
     def __init__(self, cfg, input_shape):
         super().__init__()
         size = input_shape.channels * (input_shape.width or 1) * (input_shape.height or 1)
         b, h = cfg.MODEL.ROI_BOX_HEAD, cfg.MODEL.ROI_HEADS
         self.num_classes = h.NUM_CLASSES
-        self.box2box_transform = Box2BoxTransform(weights=b.BBOX_REG_WEIGHTS)
+        self.box2box_transform = self.transform_type(weights=b.BBOX_REG_WEIGHTS)
         reg_classes = 1 if b.CLS_AGNOSTIC_BBOX_REG else self.num_classes
         self.cls_score = Linear(size, self.num_classes + 1)
-        self.bbox_pred = Linear(size, reg_classes * 4)
+        self.bbox_pred = Linear(size, reg_classes * self.box_dim)
         nn.init.normal_(self.cls_score.weight, std=0.01)
         nn.init.normal_(self.bbox_pred.weight, std=0.001)
         for layer in (self.cls_score, self.bbox_pred):
@@ -49,10 +51,10 @@ class FastRCNNOutputLayers(nn.Module):
         gt_boxes = cat([(p.gt_boxes if p.has("gt_boxes") else p.proposal_boxes).tensor for p in proposals], dim=0)
         loss_cls = F.cross_entropy(scores, gt_classes, reduction="mean")
         fg = torch.nonzero((gt_classes >= 0) & (gt_classes < self.num_classes)).squeeze(1)
-        if deltas.shape[1] == 4:
+        if deltas.shape[1] == self.box_dim:
             picked = deltas[fg]
         else:
-            picked = deltas.view(-1, self.num_classes, 4)[fg, gt_classes[fg]]
+            picked = deltas.view(-1, self.num_classes, self.box_dim)[fg, gt_classes[fg]]
         diff = (picked - self.box2box_transform.get_deltas(boxes[fg], gt_boxes[fg])).abs()
         if self.smooth_l1_beta >= 1e-5:
             b = self.smooth_l1_beta

@@ -108,13 +108,14 @@ class StandardROIHeads(torch.nn.Module):
     MASK_ON, ROIAlign 14 x 14 of the foreground rois -> mask head -> per-class BCE against the matched instance's
     bitmask cropped to the roi (structures/masks.py:169-200, the same ROIAlign).  Plumbing over this repo's kernels."""
 
+    pairwise_iou = staticmethod(pairwise_iou)      # (the rotated IoU in RROIHeads)
+
     def __init__(self, cfg, input_shape):
         super().__init__()
         from ...layers.shape_spec import ShapeSpec
         from ..poolers import ROIPooler
         from ..sampling import subsample_labels  # noqa: F401  (used in label_and_sample_proposals)
         from .box_head import build_box_head
-        from .fast_rcnn import FastRCNNOutputLayers
         from .mask_head import build_mask_head
 
         h = cfg.MODEL.ROI_HEADS
@@ -130,7 +131,7 @@ class StandardROIHeads(torch.nn.Module):
         self.box_pooler = ROIPooler(output_size=b.POOLER_RESOLUTION, scales=scales, sampling_ratio=b.POOLER_SAMPLING_RATIO,
                                     pooler_type=b.POOLER_TYPE)
         self.box_head = build_box_head(cfg, ShapeSpec(channels=c, height=b.POOLER_RESOLUTION, width=b.POOLER_RESOLUTION))
-        self.box_predictor = FastRCNNOutputLayers(cfg, self.box_head.output_shape)
+        self.box_predictor = self._box_predictor(cfg, self.box_head.output_shape)
         self.mask_on = cfg.MODEL.MASK_ON
         if self.mask_on:
             m = cfg.MODEL.ROI_MASK_HEAD
@@ -138,6 +139,10 @@ class StandardROIHeads(torch.nn.Module):
                                          sampling_ratio=m.POOLER_SAMPLING_RATIO, pooler_type=m.POOLER_TYPE)
             self.mask_head = build_mask_head(cfg, ShapeSpec(channels=c, width=m.POOLER_RESOLUTION,
                                                             height=m.POOLER_RESOLUTION))
+
+    def _box_predictor(self, cfg, input_shape):
+        from .fast_rcnn import FastRCNNOutputLayers
+        return FastRCNNOutputLayers(cfg, input_shape)
 
     @torch.no_grad()
     def label_and_sample_proposals(self, proposals: List[Instances], targets: List[Instances]):
@@ -149,7 +154,7 @@ class StandardROIHeads(torch.nn.Module):
         out = []
         for prop, tgt in zip(proposals, targets):
             has_gt = len(tgt) > 0
-            idx, lab = self.proposal_matcher(pairwise_iou(tgt.gt_boxes, prop.proposal_boxes))
+            idx, lab = self.proposal_matcher(self.pairwise_iou(tgt.gt_boxes, prop.proposal_boxes))
             if has_gt:
                 cls = tgt.gt_classes[idx].clone()
                 cls[lab == 0] = self.num_classes
