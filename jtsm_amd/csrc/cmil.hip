@@ -47,6 +47,7 @@
 
 #include "box_math.h"
 #include "common.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
@@ -256,21 +257,16 @@ __global__ __launch_bounds__(256) void merge_backward_kernel(const float* __rest
   dD[(size_t)r * ld_grad + c] = gMD[m * ldg + c] / fc;
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 struct MergeWs { int* slot; int* top_row; int* rank_id; int* sorted_row; int* sorted_id; int* num_top; };
-inline size_t merge_bytes(int B, int R) {
-  return align256((size_t)R * 4) + 4 * align256((size_t)B * kTop * 4) + align256((size_t)B * 4);
-}
-inline MergeWs merge_carve(void* ws, int B, int R) {
-  char* p = reinterpret_cast<char*>(ws);
-  const size_t tab = align256((size_t)B * kTop * 4);
+MergeWs carve(Arena& a, int B, int R) {
+  const size_t tab = (size_t)B * kTop;
   MergeWs k;
-  k.slot = reinterpret_cast<int*>(p); p += align256((size_t)R * 4);
-  k.top_row = reinterpret_cast<int*>(p); p += tab;
-  k.rank_id = reinterpret_cast<int*>(p); p += tab;
-  k.sorted_row = reinterpret_cast<int*>(p); p += tab;
-  k.sorted_id = reinterpret_cast<int*>(p); p += tab;
-  k.num_top = reinterpret_cast<int*>(p);
+  k.slot = a.take<int>(R);
+  k.top_row = a.take<int>(tab);
+  k.rank_id = a.take<int>(tab);
+  k.sorted_row = a.take<int>(tab);
+  k.sorted_id = a.take<int>(tab);
+  k.num_top = a.take<int>(B);
   return k;
 }
 
@@ -394,7 +390,9 @@ extern "C" {
 
 size_t jtsm_roi_merge_workspace_bytes(int B, int R) {
   if (B <= 0 || R < 0) return 256;
-  return merge_bytes(B, R);
+  Arena a{nullptr};
+  carve(a, B, R);
+  return a.off;
 }
 
 int jtsm_roi_merge_forward_f32(const float* S, const float* boxes, const float* C, int ldc, const float* D, int ldd,
@@ -413,7 +411,8 @@ int jtsm_roi_merge_forward_f32(const float* S, const float* boxes, const float* 
   JTSM_REQUIRE(S && boxes && C && D && MC && MD && I && IC, "roi_merge: null pointer");
   JTSM_REQUIRE((reinterpret_cast<uintptr_t>(boxes) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                "roi_merge: boxes must be 16-byte and the workspace 256-byte aligned");
-  const MergeWs k = merge_carve(workspace, B, R);
+  Arena arena{static_cast<char*>(workspace)};
+  const MergeWs k = carve(arena, B, R);
   hipLaunchKernelGGL(merge_rank_kernel, dim3(ceil_div(max_bag_rows, kThreads), B), dim3(kThreads), 0, st, S, bag_offsets,
                      k.slot, k.top_row);
   hipLaunchKernelGGL(merge_walk_kernel, dim3(B), dim3(64), 0, st, boxes, bag_offsets, k.top_row, lam, k.rank_id,

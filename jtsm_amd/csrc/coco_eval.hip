@@ -15,23 +15,23 @@
 //              the matched set is one bit per chunk in a lane's register; results are OR-ed into the records' words.
 //   jtsm_coco_accumulate over the concatenated records:
 //     key      (category, descending score, image index, rank) -> one hipcub radix sort over the bits in use;
-//     start    category starts by binary search;
+//     start    category starts by binary search (sorted_segments.h);
 //     pr       one workgroup per (category, area range, maxDet): totals, then the chunks from the right with a block scan
 //              of tp / fp and a reversed max scan for the envelope, all ten thresholds per chunk; the record that first
-//              reaches a recall threshold writes its precision and score.
+//              reaches a recall threshold writes its precision and score (the chunk step: eval_walk.h).
+// Workspaces: carve_image() / carve_acc() below, over workspace.h's Arena.
 //
 // fp64 arithmetic only in single correctly rounded operations in the reference's order; compiled with
 // -ffp-contract=off (jtsm_amd/build.py): the box IoU's `da + ga - i` after `w * h` must not fuse.
-#include <hipcub/hipcub.hpp>
-
 #include <climits>
 
-#include "common.h"
+#include "eval_walk.h"
+#include "sorted_segments.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
 
-typedef unsigned long long u64;
 typedef unsigned int u32;
 
 constexpr int kT = 10;            // IoU thresholds
@@ -52,11 +52,6 @@ struct Record {                   // 32 bytes; the Python side holds them as (D,
   u64 ignore;                     // bit a * kT + t: ignored there
 };
 
-__device__ __forceinline__ u32 ordered(float f) {
-  const u32 u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // One thread per detection.  cat_count zeroed by the caller.
 __global__ __launch_bounds__(256) void coco_rank_kernel(const float4* __restrict__ boxes,
                                                         const float* __restrict__ scores,
@@ -75,9 +70,9 @@ __global__ __launch_bounds__(256) void coco_rank_kernel(const float4* __restrict
   if (ok) {
     // compared through the sort key's encoding (the order of the floats, the two zeros equal): a total order even
     // for a NaN, so the ranks of a category are always a permutation
-    const u32 ks = ordered(s + 0.0f);
+    const u32 ks = float_order_bits(s + 0.0f);
     for (int e = 0; e < n; ++e) {
-      const u32 ke = ordered(scores[e] + 0.0f);
+      const u32 ke = float_order_bits(scores[e] + 0.0f);
       if (classes[e] == c && (ke > ks || (ke == ks && e < d))) ++r;
     }
     atomicAdd(&cat_count[c], 1);
@@ -287,36 +282,31 @@ __global__ __launch_bounds__(256) void coco_match_kernel(const int* __restrict__
   }
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int bits_for(long k) {   // bits needed to hold values 0..k
-  int b = 1;
-  while ((1L << b) <= k) ++b;
-  return b;
-}
-
-struct ImageLayout {
-  size_t zeroed, cat_count, area_i, zeroed_end;
-  size_t dbox, darea, rank, det_of, dwords, ious, total;
+struct ImageWs {
+  size_t zeroed, zeroed_end;        // arena marks around cat_count and area_i: cleared by one memset
+  int *cat_count, *area_i;
+  double4* dbox;
+  double* darea;
+  int *rank, *det_of;
+  u64* dwords;
+  double* ious;
 };
 
-ImageLayout image_layout(int n, int G, int K, long W64, int max_det) {
-  ImageLayout l = {};
-  const size_t d = n > 0 ? n : 0, g = G > 0 ? G : 0, k = K > 0 ? K : 0, w = W64 > 0 ? W64 : 0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += align256(bytes ? bytes : 1); return at; };
-  l.zeroed = o;
-  l.cat_count = take(k * 4);
-  l.area_i = take(d * 4);
-  l.zeroed_end = o;
-  l.dbox = take(d * 32);
-  l.darea = take(d * 8);
-  l.rank = take(d * 4);
-  l.det_of = take(k * (size_t)(max_det > 0 ? max_det : 0) * 4);
-  l.dwords = take(d * w * 8);
-  l.ious = take(d * g * 8);
-  l.total = o;
-  return l;
+ImageWs carve_image(Arena& a, int n, int G, int K, long W64, int max_det) {
+  const size_t d = n > 0 ? n : 0, g = G > 0 ? G : 0, k = K > 0 ? K : 0, w64 = W64 > 0 ? W64 : 0;
+  a.pad_empty = true;
+  ImageWs w;
+  w.zeroed = a.mark();
+  w.cat_count = a.take<int>(k);
+  w.area_i = a.take<int>(d);
+  w.zeroed_end = a.mark();
+  w.dbox = a.take<double4>(d);
+  w.darea = a.take<double>(d);
+  w.rank = a.take<int>(d);
+  w.det_of = a.take<int>(k * (size_t)(max_det > 0 ? max_det : 0));
+  w.dwords = a.take<u64>(d * w64);
+  w.ious = a.take<double>(d * g);
+  return w;
 }
 
 // ----------------------------------------------------------------------------------------------------- accumulate
@@ -327,24 +317,10 @@ __global__ __launch_bounds__(256) void coco_key_kernel(const Record* __restrict_
   const Record r = rec[d];
   int c = r.cat, im = r.image, rk = r.rank;
   if (c < 0 || c >= K || im < 0 || im >= N || rk < 0 || rk >= kMaxDet) { c = K; im = 0; rk = 0; }
-  const u32 s = ~ordered(r.score + 0.0f);                               // (-0 + 0 = +0: the two zeros compare equal)
+  const u32 s = ~float_order_bits(r.score + 0.0f);                     // (-0 + 0 = +0: the two zeros compare equal)
   key[d] = ((u64)c << (32 + image_bits + kRankBits)) | ((u64)s << (image_bits + kRankBits)) | ((u64)im << kRankBits) |
            (u64)rk;
   iota[d] = d;
-}
-
-// start[c] = first sorted position of category c, c in [0, K]; start[K] = number of ranked records
-__global__ __launch_bounds__(64) void coco_start_kernel(const u64* __restrict__ key_sorted, int D, int K, int shift,
-                                                        int* __restrict__ start) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  if (c > K) return;
-  const u64 want = (u64)c << shift;
-  int lo = 0, hi = D;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo) / 2;
-    if (key_sorted[mid] < want) lo = mid + 1; else hi = mid;
-  }
-  start[c] = lo;
 }
 
 // One workgroup per (category, area range, maxDet).
@@ -355,21 +331,17 @@ __global__ __launch_bounds__(kChunk) void coco_pr_kernel(const Record* __restric
                                                          const int* __restrict__ max_dets, int M, int K,
                                                          double* __restrict__ precision, double* __restrict__ scores,
                                                          double* __restrict__ recall) {
-  typedef hipcub::BlockScan<u64, kChunk> SumScan;
-  typedef hipcub::BlockScan<double, kChunk> MaxScan;
+  typedef RankedWalk<kChunk> Walk;                 // (eval_walk.h)
   typedef hipcub::BlockScan<int, kChunk> IntScan;
   typedef hipcub::BlockReduce<u64, kChunk> ReduceU;
   __shared__ union {
-    typename SumScan::TempStorage sum;
-    typename MaxScan::TempStorage mx;
+    typename Walk::Temp walk;
     typename IntScan::TempStorage cnt;
     typename ReduceU::TempStorage redu;
   } temp;
   __shared__ double sh_thr[kMaxR];
-  __shared__ double sh_a[kChunk];
-  __shared__ double sh_b[kChunk];
+  __shared__ typename Walk::Shared sh;
   __shared__ u64 sh_tot[kT + 1];
-  __shared__ u64 sh_u;
   const int c = blockIdx.x, a = blockIdx.y, m = blockIdx.z, tid = threadIdx.x;
   const int base = start[c], n = start[c + 1] - base;
   const long long np = npos_table[c * kA + a];
@@ -437,31 +409,19 @@ __global__ __launch_bounds__(kChunk) void coco_pr_kernel(const Record* __restric
     const bool valid = k < n && r.rank < max_det;
     int vinc;
     IntScan(temp.cnt).InclusiveSum(valid ? 1 : 0, vinc);
-    if (tid == kChunk - 1) sh_u = (u64)vinc;
+    if (tid == kChunk - 1) sh.u = (u64)vinc;
     __syncthreads();
-    const int begin_valid = end_valid - (int)sh_u;
+    const int begin_valid = end_valid - (int)sh.u;
     const int before = begin_valid + vinc - (valid ? 1 : 0);            // records within max_det in front of this one
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < kT; ++t) {
       const u64 b = valid ? bits_of(r.matched, r.ignore, t) : 0ull;
-      u64 inc;
-      SumScan(temp.sum).InclusiveSum(b, inc);
-      if (tid == kChunk - 1) sh_u = inc;
-      __syncthreads();
-      const u64 begin = end[t] - sh_u;
-      inc += begin;
+      const u64 inc = Walk::running_sum(temp.walk, sh, b, end[t]);   // (one barrier; end[t] is now the chunk's begin)
       const long long tpc = (long long)(inc >> 32), fpc = (long long)(inc & 0xffffffffull);
       const double rc = (double)tpc / npd;
       const double prec = (valid && tpc + fpc > 0) ? (double)tpc / (double)(tpc + fpc) : 0.0;
-      sh_a[tid] = prec;
-      __syncthreads();
-      double smax;                        // suffix maximum inside the chunk: a prefix scan of the reversed chunk
-      MaxScan(temp.mx).InclusiveScan(sh_a[kChunk - 1 - tid], smax, hipcub::Max());
-      sh_b[kChunk - 1 - tid] = fmax(smax, env_carry[t]);
-      __syncthreads();
-      const double env = sh_b[tid];
-      env_carry[t] = sh_b[0];
+      const double env = Walk::envelope(temp.walk, sh, prec, env_carry[t]);     // (two barriers)
       const bool tpbit = (b >> 32) != 0;
       if (valid && (tpbit || before == 0)) {
         // the first record whose recall reaches thr: the one in front of it (if any) is still below
@@ -475,40 +435,32 @@ __global__ __launch_bounds__(kChunk) void coco_pr_kernel(const Record* __restric
           }
         }
       }
-      end[t] = begin;
-      __syncthreads();
+      __syncthreads();                    // temp and sh are free for the next threshold
     }
     end_valid = begin_valid;
   }
 }
 
-struct AccLayout {
-  size_t start, key_a, key_b, iota, idx, cub, total;
+struct AccWs {
+  int* start;
+  u64 *key_a, *key_b;
+  int *iota, *idx;
+  char* cub;
   size_t cub_bytes;
 };
 
-size_t cub_temp_bytes(int D) {
-  size_t a = 0;
-  u64* k = nullptr;
-  int* v = nullptr;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, k, k, v, v, D, 0, 64, (hipStream_t) nullptr);
-  return a;
-}
-
-AccLayout acc_layout(int D, int K) {
-  AccLayout l = {};
+AccWs carve_acc(Arena& a, int D, int K) {
   const size_t d = D > 0 ? D : 0, k = K > 0 ? K : 0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += align256(bytes ? bytes : 1); return at; };
-  l.start = take((k + 2) * 4);
-  l.key_a = take(d * 8);
-  l.key_b = take(d * 8);
-  l.iota = take(d * 4);
-  l.idx = take(d * 4);
-  l.cub_bytes = D > 0 ? cub_temp_bytes(D) : 0;
-  l.cub = take(l.cub_bytes);
-  l.total = o;
-  return l;
+  a.pad_empty = true;
+  AccWs w;
+  w.start = a.take<int>(k + 2);
+  w.key_a = a.take<u64>(d);
+  w.key_b = a.take<u64>(d);
+  w.iota = a.take<int>(d);
+  w.idx = a.take<int>(d);
+  w.cub_bytes = D > 0 ? sort_pairs_temp_bytes(D) : 0;
+  w.cub = a.take<char>(w.cub_bytes);
+  return w;
 }
 
 }  // namespace
@@ -518,7 +470,9 @@ using namespace jtsm;
 
 extern "C" size_t jtsm_coco_image_workspace_bytes(int n, int G, int K, int H, int W, int max_det) {
   if (n < 0 || G < 0 || K < 1 || H < 0 || W < 0 || max_det < 1 || max_det > kMaxDet) return 0;
-  return image_layout(n, G, K, ((long)H * W + 63) / 64, max_det).total;
+  Arena a{nullptr};
+  carve_image(a, n, G, K, ((long)H * W + 63) / 64, max_det);
+  return a.off;
 }
 
 extern "C" int jtsm_coco_image(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
@@ -548,55 +502,53 @@ extern "C" int jtsm_coco_image(const float* det_boxes, const float* det_scores, 
     JTSM_REQUIRE(HW >= 1 && HW <= INT_MAX, "coco_image: masks of %d x %d", H, W);
     JTSM_REQUIRE((n == 0 || det_masks) && (G == 0 || gt_masks), "coco_image: segm needs det_masks and gt_masks");
   }
-  const ImageLayout l = image_layout(n, G, K, segm ? W64 : 0, max_det);
-  JTSM_REQUIRE(workspace && workspace_bytes >= l.total && ((size_t)workspace & 255) == 0,
-               "coco_image: workspace of %zu bytes (256-byte aligned) needed", l.total);
+  Arena arena{static_cast<char*>(workspace)};
+  const ImageWs w = carve_image(arena, n, G, K, segm ? W64 : 0, max_det);
+  JTSM_REQUIRE(workspace && workspace_bytes >= arena.off && ((size_t)workspace & 255) == 0,
+               "coco_image: workspace of %zu bytes (256-byte aligned) needed", arena.off);
   hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  int* cat_count = reinterpret_cast<int*>(ws + l.cat_count);
-  int* area_i = reinterpret_cast<int*>(ws + l.area_i);
-  double4* dbox = reinterpret_cast<double4*>(ws + l.dbox);
-  double* darea = reinterpret_cast<double*>(ws + l.darea);
-  int* rank = rank_debug ? rank_debug : reinterpret_cast<int*>(ws + l.rank);
-  int* det_of = reinterpret_cast<int*>(ws + l.det_of);
-  u64* dwords = reinterpret_cast<u64*>(ws + l.dwords);
-  double* ious = ious_debug ? ious_debug : reinterpret_cast<double*>(ws + l.ious);
+  int* rank = rank_debug ? rank_debug : w.rank;
+  double* ious = ious_debug ? ious_debug : w.ious;
   Record* rec = reinterpret_cast<Record*>(records);
 
-  JTSM_CHECK_HIP(hipMemsetAsync(ws + l.zeroed, 0, l.zeroed_end - l.zeroed, st));
+  JTSM_CHECK_HIP(hipMemsetAsync(arena.base + w.zeroed, 0, w.zeroed_end - w.zeroed, st));
   if (n > 0) {
     hipLaunchKernelGGL(coco_rank_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st,
                        reinterpret_cast<const float4*>(det_boxes), det_scores, det_classes, n, K, image_index, max_det,
-                       segm ? 1 : 0, dbox, darea, rank, cat_count, det_of, rec, reinterpret_cast<u64*>(stats));
+                       segm ? 1 : 0, w.dbox, w.darea, rank, w.cat_count, w.det_of, rec, reinterpret_cast<u64*>(stats));
     JTSM_CHECK_LAUNCH("coco rank");
     if (segm) {
       const long per_mask = (W64 + 3) / 4;
       hipLaunchKernelGGL(coco_pack_kernel, dim3((unsigned)(per_mask < 64 ? per_mask : 64), n), dim3(256), 0, st,
-                         det_masks, HW, W64, dwords, area_i);
+                         det_masks, HW, W64, w.dwords, w.area_i);
       JTSM_CHECK_LAUNCH("coco pack");
-      hipLaunchKernelGGL(coco_area_to_double_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, area_i, n, darea);
+      hipLaunchKernelGGL(coco_area_to_double_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, w.area_i, n, w.darea);
       JTSM_CHECK_LAUNCH("coco area");
     }
     if (G > 0) {
       if (segm) {
-        hipLaunchKernelGGL(coco_mask_iou_kernel, dim3(G, n), dim3(256), 0, st, dwords, area_i, det_classes, rank,
+        hipLaunchKernelGGL(coco_mask_iou_kernel, dim3(G, n), dim3(256), 0, st, w.dwords, w.area_i, det_classes, rank,
                            reinterpret_cast<const u64*>(gt_masks), gt_crowd, gt_cat_start, K, G, W64, ious);
         JTSM_CHECK_LAUNCH("coco mask iou");
       } else {
-        hipLaunchKernelGGL(coco_box_iou_kernel, dim3(ceil_div((long)n * G, 256)), dim3(256), 0, st, dbox, det_classes,
+        hipLaunchKernelGGL(coco_box_iou_kernel, dim3(ceil_div((long)n * G, 256)), dim3(256), 0, st, w.dbox, det_classes,
                            rank, n, reinterpret_cast<const double4*>(gt_boxes), gt_crowd, gt_cat_start, K, G, ious);
         JTSM_CHECK_LAUNCH("coco box iou");
       }
     }
   }
-  hipLaunchKernelGGL(coco_match_kernel, dim3(ceil_div((long)K * kA * kT, 4)), dim3(256), 0, st, cat_count, det_of,
-                     darea, n, max_det, gt_area, gt_crowd, gt_cat_start, K, G, ious, iou_thrs, area_rng, rec,
+  hipLaunchKernelGGL(coco_match_kernel, dim3(ceil_div((long)K * kA * kT, 4)), dim3(256), 0, st, w.cat_count, w.det_of,
+                     w.darea, n, max_det, gt_area, gt_crowd, gt_cat_start, K, G, ious, iou_thrs, area_rng, rec,
                      reinterpret_cast<u64*>(npos));
   JTSM_CHECK_LAUNCH("coco match");
   return JTSM_OK;
 }
 
-extern "C" size_t jtsm_coco_accumulate_workspace_bytes(int D, int K) { return acc_layout(D, K).total; }
+extern "C" size_t jtsm_coco_accumulate_workspace_bytes(int D, int K) {
+  Arena a{nullptr};
+  carve_acc(a, D, K);
+  return a.off;
+}
 
 extern "C" int jtsm_coco_accumulate(const int64_t* records, int D, int K, int N, const int64_t* npos,
                                     const double* rec_thrs, int R, const int32_t* max_dets, int M, double* precision,
@@ -612,28 +564,24 @@ extern "C" int jtsm_coco_accumulate(const int64_t* records, int D, int K, int N,
   JTSM_REQUIRE(npos && rec_thrs && max_dets && precision && scores && recall, "coco_accumulate: null table");
   JTSM_REQUIRE(D == 0 || records, "coco_accumulate: null records");
   JTSM_REQUIRE(((size_t)records & 7) == 0, "coco_accumulate: records must be 8-byte aligned");
-  const AccLayout l = acc_layout(D, K);
-  JTSM_REQUIRE(workspace && workspace_bytes >= l.total && ((size_t)workspace & 255) == 0,
-               "coco_accumulate: workspace of %zu bytes (256-byte aligned) needed", l.total);
+  Arena arena{static_cast<char*>(workspace)};
+  const AccWs w = carve_acc(arena, D, K);
+  JTSM_REQUIRE(workspace && workspace_bytes >= arena.off && ((size_t)workspace & 255) == 0,
+               "coco_accumulate: workspace of %zu bytes (256-byte aligned) needed", arena.off);
   hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  int* start = reinterpret_cast<int*>(ws + l.start);
-  u64* key_a = reinterpret_cast<u64*>(ws + l.key_a);
-  u64* key_b = reinterpret_cast<u64*>(ws + l.key_b);
-  int* iota = reinterpret_cast<int*>(ws + l.iota);
-  int* idx = reinterpret_cast<int*>(ws + l.idx);
   const Record* rec = reinterpret_cast<const Record*>(records);
   const int shift = 32 + image_bits + kRankBits;
   if (D > 0) {
-    hipLaunchKernelGGL(coco_key_kernel, dim3(ceil_div(D, 256)), dim3(256), 0, st, rec, D, K, N, image_bits, key_a, iota);
+    hipLaunchKernelGGL(coco_key_kernel, dim3(ceil_div(D, 256)), dim3(256), 0, st, rec, D, K, N, image_bits, w.key_a,
+                       w.iota);
     JTSM_CHECK_LAUNCH("coco key");
-    size_t cub_bytes = l.cub_bytes;
-    JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + l.cub, cub_bytes, key_a, key_b, iota, idx, D, 0,
+    size_t cub_bytes = w.cub_bytes;
+    JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, cub_bytes, w.key_a, w.key_b, w.iota, w.idx, D, 0,
                                                       shift + class_bits, st));
   }
-  hipLaunchKernelGGL(coco_start_kernel, dim3(ceil_div(K + 1, 64)), dim3(64), 0, st, key_b, D, K, shift, start);
+  hipLaunchKernelGGL(segment_starts_kernel, dim3(ceil_div(K + 1, 64)), dim3(64), 0, st, w.key_b, D, K, shift, w.start);
   JTSM_CHECK_LAUNCH("coco start");
-  hipLaunchKernelGGL(coco_pr_kernel, dim3(K, kA, M), dim3(kChunk), 0, st, rec, idx, start,
+  hipLaunchKernelGGL(coco_pr_kernel, dim3(K, kA, M), dim3(kChunk), 0, st, rec, w.idx, w.start,
                      reinterpret_cast<const long long*>(npos), rec_thrs, R, max_dets, M, K, precision, scores, recall);
   JTSM_CHECK_LAUNCH("coco pr");
   return JTSM_OK;

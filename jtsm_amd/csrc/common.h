@@ -42,33 +42,30 @@ inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 // +0 — the plane of a stored -0 then depended on the element's position (tests/test_hip_planes.py).
 __device__ __forceinline__ _Float16 f16_plane(float v, int shift) { return (_Float16)__builtin_ldexpf(v, shift); }
 
-// float -> unsigned whose order is the float order, NaN above everything (torch.topk / sort put NaN first in a
-// descending order), -0 = +0
-__device__ __forceinline__ unsigned ordered_bits(float v) {
-  if (v != v) return 0xffffffffu;
-  const unsigned u = __float_as_uint(v + 0.f);
+// float -> unsigned whose order is the float order, and back.  The raw map: -0 below +0, a NaN by its bits (above +inf
+// with the sign clear, below -inf with it set).  Who wants what:
+//   voc_eval.hip    raw, and the inverse: only the largest and smallest score come back out, for evaluate()'s range
+//                   check — they must be the floats that went in, -0 and NaN included.
+//   coco_eval.hip   raw on `s + 0.0f`: ranks and sort keys must call the two zeros equal (the reference compares
+//                   floats); a NaN keeps its place by its bits, which is still a total order, so ranks stay a permutation.
+//   nms_stages.h    ordered_desc, the complement (an ascending radix sort gives descending scores), raw: -0 sorts
+//                   after +0; and the raw pair for the largest coordinate, which comes back out as the float it was.
+//   order_key's users (mist.hip, cmil.hip, ...)   ordered_bits: -0 = +0 and EVERY NaN on top, as torch.topk / sort put NaN first in a
+//                   descending order whatever its sign.
+__device__ __forceinline__ unsigned float_order_bits(float f) {
+  const unsigned u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+__device__ __forceinline__ float float_from_order_bits(unsigned e) {
+  return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
+}
+__device__ __forceinline__ unsigned ordered_bits(float v) { return v != v ? 0xffffffffu : float_order_bits(v + 0.f); }
+__device__ __forceinline__ unsigned ordered_desc(float f) { return ~float_order_bits(f); }
 // Total order of (value, index) pairs — higher key = earlier: value descending, then index ascending.  A position in
 // that order is the NUMBER OF KEYS ABOVE one's own: counted, not sorted (mist.hip, cmil.hip).
 __device__ __forceinline__ unsigned long long order_key(float v, int index) {
   return ((unsigned long long)ordered_bits(v) << 32) | (unsigned long long)(0xffffffffu - (unsigned)index);
 }
-
-// ordered compaction of a per-thread flag over the 256 threads of the workgroup: returns this thread's slot (if
-// flagged) and the total; two barriers.
-__device__ __forceinline__ int compact256(bool flag, int* __restrict__ wave_count, int& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(flag);
-  __syncthreads();                       // previous readers of wave_count are done
-  if (lane == 0) wave_count[wv] = __popcll(bal);
-  __syncthreads();
-  int off = 0;
-  total = 0;
-  for (int w = 0; w < 4; ++w) { if (w < wv) off += wave_count[w]; total += wave_count[w]; }
-  return off + __popcll(bal & ((1ull << lane) - 1ull));
-}
-
 
 // Ordered compaction of a per-thread flag over the NW wavefronts of the workgroup: this thread's slot (if flagged) and
 // the total; two barriers.

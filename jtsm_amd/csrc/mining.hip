@@ -456,8 +456,8 @@ __device__ __forceinline__ void emit_class_list(bool present, int c, int C, int 
                                                 int* __restrict__ cls, int* __restrict__ cnt, int* wave_count) {
   int npresent, nabsent;
   const bool valid = c < C;
-  const int ps = compact256(valid && present, wave_count, npresent);
-  const int as = compact256(valid && !present, wave_count, nabsent);
+  const int ps = compact_wg<4>(valid && present, wave_count, npresent);
+  const int as = compact_wg<4>(valid && !present, wave_count, nabsent);
   if (valid) {
     oh[c] = present ? 1.f : 0.f;
     cls[present ? ps : npresent + as] = c + offset;

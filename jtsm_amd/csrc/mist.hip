@@ -30,6 +30,7 @@
 
 #include "box_math.h"
 #include "common.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
@@ -219,22 +220,15 @@ __global__ __launch_bounds__(kThreads) void mist_nms_kernel(
   if (threadIdx.x == 0) out_num[b] = K;
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 struct MistWs { float* cand_score; int* cand_row; float4* cand_box; float4* sorted_box; int* sorted_idx; };
-inline size_t mist_bytes(int B, int P) {
+MistWs carve(Arena& a, int B, int P) {
   const size_t n = (size_t)B * (size_t)P;
-  return 2 * align256(n * sizeof(float4)) + 3 * align256(n * sizeof(float));
-}
-inline MistWs mist_carve(void* ws, int B, int P) {
-  const size_t n = (size_t)B * (size_t)P;
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = 0;
   MistWs k;
-  k.cand_box = reinterpret_cast<float4*>(p + off); off += align256(n * sizeof(float4));
-  k.sorted_box = reinterpret_cast<float4*>(p + off); off += align256(n * sizeof(float4));
-  k.cand_score = reinterpret_cast<float*>(p + off); off += align256(n * sizeof(float));
-  k.cand_row = reinterpret_cast<int*>(p + off); off += align256(n * sizeof(int));
-  k.sorted_idx = reinterpret_cast<int*>(p + off);
+  k.cand_box = a.take<float4>(n);
+  k.sorted_box = a.take<float4>(n);
+  k.cand_score = a.take<float>(n);
+  k.cand_row = a.take<int>(n);
+  k.sorted_idx = a.take<int>(n);
   return k;
 }
 
@@ -247,7 +241,9 @@ extern "C" {
 
 size_t jtsm_mine_top_p_workspace_bytes(int B, int G, int t_max) {
   if (B <= 0 || G <= 0 || t_max <= 0) return 256;
-  return mist_bytes(B, G * t_max);
+  Arena a{nullptr};
+  carve(a, B, G * t_max);
+  return a.off;
 }
 
 int jtsm_mine_top_p_f32(const float* scores, int ld, const float* lse, const float* proposals, const float* deltas,
@@ -270,7 +266,8 @@ int jtsm_mine_top_p_f32(const float* scores, int ld, const float* lse, const flo
   JTSM_REQUIRE(!deltas || ld_deltas >= 4, "mine_top_p: deltas need their leading dimension");
   JTSM_REQUIRE((reinterpret_cast<uintptr_t>(out_boxes) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                "mine_top_p: out_boxes must be 16-byte and the workspace 256-byte aligned");
-  const MistWs k = mist_carve(workspace, B, P);
+  Arena arena{static_cast<char*>(workspace)};
+  const MistWs k = carve(arena, B, P);
   hipLaunchKernelGGL(mist_topk_kernel, dim3(B * G), dim3(kThreads), 0, st, scores, ld, lse, proposals, deltas, ld_deltas,
                      decode_zero_deltas, bag_offsets, classes, counts, top_t, G, t_max, P, k.cand_score, k.cand_row,
                      k.cand_box);

@@ -788,7 +788,7 @@ __global__ __launch_bounds__(256) void moi_roi_lists_kernel(const float* __restr
     const int n = base + threadIdx.x;
     const bool hit = n < M && roi_level[n] == l && (int)rois[(size_t)n * 5] == b;
     int cnt;
-    const int slot = compact256(hit, wave_count, cnt);
+    const int slot = compact_wg<4>(hit, wave_count, cnt);
     if (hit) mine[filled + slot] = n;
     filled += cnt;
   }
@@ -945,7 +945,7 @@ __global__ __launch_bounds__(256) void moi_pool_bwd_tiled(
       hit = r.x0 <= x1 && r.x1 >= x0 && r.y0 <= y1 && r.y1 >= y0;
     }
     int nroi;
-    const int slot = compact256(hit, wave_count, nroi);
+    const int slot = compact_wg<4>(hit, wave_count, nroi);
     if (hit) {
       roi_list[slot] = n;
       roi_box[slot] = r;
@@ -967,7 +967,7 @@ __global__ __launch_bounds__(256) void moi_pool_bwd_tiled(
         row = m * nbins + bin;
       }
       int cnt;
-      const int ps = compact256(bh, wave_count, cnt);
+      const int ps = compact_wg<4>(bh, wave_count, cnt);
       if (bh) pair_list[np + ps] = row;
       np += cnt;
     }

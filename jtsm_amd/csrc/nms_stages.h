@@ -6,38 +6,26 @@
 // words per row (a class never has more than max_per_class members; the includer's kernel) -> one wavefront per class
 // walks its segment -> second radix sort puts the survivors first, by descending score, ties by index.
 #pragma once
-#include "common.h"
-
-#include <hipcub/hipcub.hpp>
+#include "sorted_segments.h"
+#include "workspace.h"
 
 #include <cstdint>
 
 namespace jtsm {
 namespace {
 
-typedef unsigned long long u64;
-
 struct NmsHeader {
   int n_valid;      // elements with class < num_classes
-  int max_coord;    // order-preserving int image of the largest coordinate among valid boxes
+  unsigned max_coord;   // float_order_bits of the largest coordinate among valid boxes
   int num_keep;
   int overflow;     // a class had more members than max_per_class allows
 };
 
-__device__ __forceinline__ unsigned ordered_desc(float f) {   // larger float -> smaller key (-0 sorts after +0)
-  unsigned u = __float_as_uint(f);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~u;
-}
-__device__ __forceinline__ int float_to_ordered_int(float f) {
-  const int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float ordered_int_to_float(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
+// (score keys: ordered_desc, common.h — larger float -> smaller key, -0 sorts after +0)
 
 __global__ void nms_header_init(NmsHeader* h) {
   h->n_valid = 0;
-  h->max_coord = float_to_ordered_int(-INFINITY);
+  h->max_coord = float_order_bits(-INFINITY);
   h->num_keep = 0;
   h->overflow = 0;
 }
@@ -45,8 +33,8 @@ __global__ void nms_header_init(NmsHeader* h) {
 __device__ __forceinline__ void header_accumulate(NmsHeader* h, bool ok, float cmax) {
   // wave-level reduction, then one atomic per wavefront (integer atomics: order-independent results)
   const u64 b = __ballot(ok);
-  int m = ok ? float_to_ordered_int(cmax) : float_to_ordered_int(-INFINITY);
-  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
+  unsigned m = float_order_bits(ok ? cmax : -INFINITY);
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
   if ((threadIdx.x & 63) == 0 && b) {
     atomicAdd(&h->n_valid, __popcll(b));
     atomicMax(&h->max_coord, m);
@@ -59,18 +47,6 @@ __global__ __launch_bounds__(256) void nms_keys_kernel(const float* __restrict__
   if (e >= N) return;
   key[e] = ((u64)(unsigned)eclass[e] << 32) | ordered_desc(escore[e]);
   iota[e] = e;
-}
-
-// seg[c] = first sorted position whose class is >= c, c = 0..K (seg[K] = number of valid elements)
-__global__ void nms_segments_kernel(const u64* __restrict__ keys, int N, int K, int* __restrict__ seg) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c > K) return;
-  int lo = 0, hi = N;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if ((int)(keys[mid] >> 32) < c) lo = mid + 1; else hi = mid;
-  }
-  seg[c] = lo;
 }
 
 __device__ __forceinline__ u64 shfl64(u64 v, int src) {
@@ -148,89 +124,68 @@ __global__ __launch_bounds__(256) void nms_emit_keep_kernel(const int* __restric
   }
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct NmsLayout {
+struct NmsWs {
   int N, W, nblk, K;
-  size_t header, ebox, escore, eclass, key_a, key_b, iota, sidx, order, seg, kept, rowvalid, mask, cub, total;
+  NmsHeader* header;
+  void* ebox;           // N boxes of box_bytes each
+  float* escore;
+  int* eclass;
+  u64 *key_a, *key_b;
+  int *iota, *sidx, *order, *seg;
+  uint8_t *kept, *rowvalid;
+  u64* mask;
+  char* cub;
   size_t cub_bytes;
 };
 
-size_t cub_temp_bytes(int N) {
-  size_t a = 0, b = 0;
-  u64* k = nullptr;
-  int* v = nullptr;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, k, k, v, v, N, 0, 64, (hipStream_t) nullptr);
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, k, k, v, v, N, 0, 33, (hipStream_t) nullptr);
-  return a > b ? a : b;
-}
-
 // box_bytes: 16 for an xyxy box, 20 for a rotated (cx, cy, w, h, angle) box
-NmsLayout nms_layout(int N, int K, int max_per_class, int R, int box_bytes = 16) {
-  NmsLayout l = {};
-  l.N = N; l.K = K;
-  l.W = ceil_div(max_per_class > 0 ? max_per_class : 1, 64) + 1;
-  l.nblk = ceil_div(N > 0 ? N : 1, 64);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += align256(bytes); return at; };
-  l.header = take(sizeof(NmsHeader));
-  l.ebox = take((size_t)N * box_bytes);
-  l.escore = take((size_t)N * 4);
-  l.eclass = take((size_t)N * 4);
-  l.key_a = take((size_t)N * 8);
-  l.key_b = take((size_t)N * 8);
-  l.iota = take((size_t)N * 4);
-  l.sidx = take((size_t)N * 4);
-  l.order = take((size_t)N * 4);
-  l.seg = take((size_t)(K + 2) * 4);
-  l.kept = take((size_t)l.nblk * 64);
-  l.rowvalid = take((size_t)(R > 0 ? R : 1));
-  l.mask = take((size_t)l.nblk * 64 * l.W * 8);
-  l.cub_bytes = N > 0 ? cub_temp_bytes(N) : 0;
-  l.cub = take(l.cub_bytes);
-  l.total = o;
-  return l;
-}
-
-int bits_for(int k) {   // bits needed to hold values 0..k
-  int b = 1;
-  while ((1 << b) <= k) ++b;
-  return b;
+NmsWs carve(Arena& a, int N, int K, int max_per_class, int R, int box_bytes = 16) {
+  NmsWs w;
+  w.N = N; w.K = K;
+  w.W = ceil_div(max_per_class > 0 ? max_per_class : 1, 64) + 1;
+  w.nblk = ceil_div(N > 0 ? N : 1, 64);
+  w.header = a.take<NmsHeader>(1);
+  w.ebox = a.take<char>((size_t)N * box_bytes);
+  w.escore = a.take<float>(N);
+  w.eclass = a.take<int>(N);
+  w.key_a = a.take<u64>(N);
+  w.key_b = a.take<u64>(N);
+  w.iota = a.take<int>(N);
+  w.sidx = a.take<int>(N);
+  w.order = a.take<int>(N);
+  w.seg = a.take<int>(K + 2);
+  w.kept = a.take<uint8_t>((size_t)w.nblk * 64);
+  w.rowvalid = a.take<uint8_t>(R > 0 ? R : 1);
+  w.mask = a.take<u64>((size_t)w.nblk * 64 * w.W);
+  w.cub_bytes = N > 0 ? sort_pairs_temp_bytes(N) : 0;
+  w.cub = a.take<char>(w.cub_bytes);
+  return w;
 }
 
 // elements already written (ebox / escore / eclass / header); runs sort -> bits -> scan -> sort.
 // launch_bits(sorted keys, sorted element indices, header, mask) launches the includer's bit-matrix kernel on a
 // (nblk, W) grid of one-wavefront workgroups and returns JTSM_OK or an error code.
 template <class LaunchBits>
-int nms_stages(char* ws, const NmsLayout& l, hipStream_t st, LaunchBits launch_bits) {
-  const int N = l.N, K = l.K;
-  NmsHeader* h = reinterpret_cast<NmsHeader*>(ws + l.header);
-  float* escore = reinterpret_cast<float*>(ws + l.escore);
-  int* eclass = reinterpret_cast<int*>(ws + l.eclass);
-  u64* key_a = reinterpret_cast<u64*>(ws + l.key_a);
-  u64* key_b = reinterpret_cast<u64*>(ws + l.key_b);
-  int* iota = reinterpret_cast<int*>(ws + l.iota);
-  int* sidx = reinterpret_cast<int*>(ws + l.sidx);
-  int* order = reinterpret_cast<int*>(ws + l.order);
-  int* seg = reinterpret_cast<int*>(ws + l.seg);
-  uint8_t* kept = reinterpret_cast<uint8_t*>(ws + l.kept);
-  u64* mask = reinterpret_cast<u64*>(ws + l.mask);
-  size_t cub_bytes = l.cub_bytes;
-  hipLaunchKernelGGL(nms_keys_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, escore, eclass, N, key_a, iota);
+int nms_stages(const NmsWs& w, hipStream_t st, LaunchBits launch_bits) {
+  const int N = w.N, K = w.K;
+  size_t cub_bytes = w.cub_bytes;
+  hipLaunchKernelGGL(nms_keys_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, w.escore, w.eclass, N, w.key_a, w.iota);
   JTSM_CHECK_LAUNCH("nms keys");
-  JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + l.cub, cub_bytes, key_a, key_b, iota, sidx, N, 0,
+  JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, cub_bytes, w.key_a, w.key_b, w.iota, w.sidx, N, 0,
                                                     32 + bits_for(K), st));
-  hipLaunchKernelGGL(nms_segments_kernel, dim3(ceil_div(K + 1, 64)), dim3(64), 0, st, key_b, N, K, seg);
+  hipLaunchKernelGGL(segment_starts_kernel, dim3(ceil_div(K + 1, 64)), dim3(64), 0, st, w.key_b, N, K, 32, w.seg);
   JTSM_CHECK_LAUNCH("nms segments");
-  const int rc = launch_bits(key_b, sidx, h, mask);
+  const int rc = launch_bits(w.key_b, w.sidx, w.header, w.mask);
   if (rc) return rc;
-  JTSM_CHECK_HIP(hipMemsetAsync(kept, 0, (size_t)l.nblk * 64, st));
-  hipLaunchKernelGGL(nms_scan_kernel, dim3(K), dim3(64), (size_t)2 * l.W * sizeof(u64), st, mask, l.W, seg, kept, h);
+  JTSM_CHECK_HIP(hipMemsetAsync(w.kept, 0, (size_t)w.nblk * 64, st));
+  hipLaunchKernelGGL(nms_scan_kernel, dim3(K), dim3(64), (size_t)2 * w.W * sizeof(u64), st, w.mask, w.W, w.seg, w.kept,
+                     w.header);
   JTSM_CHECK_LAUNCH("nms scan");
-  hipLaunchKernelGGL(nms_final_keys_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, sidx, kept, escore, N, key_a);
+  hipLaunchKernelGGL(nms_final_keys_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, w.sidx, w.kept, w.escore, N,
+                     w.key_a);
   JTSM_CHECK_LAUNCH("nms final keys");
-  cub_bytes = l.cub_bytes;
-  JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + l.cub, cub_bytes, key_a, key_b, iota, order, N, 0, 33, st));
+  cub_bytes = w.cub_bytes;
+  JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, cub_bytes, w.key_a, w.key_b, w.iota, w.order, N, 0, 33, st));
   return JTSM_OK;
 }
 

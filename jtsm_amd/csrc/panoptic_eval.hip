@@ -18,6 +18,7 @@
 #include <climits>
 
 #include "common.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
@@ -156,33 +157,30 @@ __global__ __launch_bounds__(kThreads) void pq_hist_kernel(const int* __restrict
   }
 }
 
-struct PqLayout {
-  size_t zeroed, hist, keys, vals, pmatched, crowd_row, zeroed_end;
-  size_t pcat, area_p, match_p, iou, total;
+struct PqWs {
+  size_t zeroed, zeroed_end;        // arena marks around hist .. crowd_row: cleared by one memset
+  int *hist, *keys, *vals, *pmatched, *crowd_row;
+  int *pcat, *area_p, *match_p;
+  double* iou;
   int slots;
 };
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-PqLayout pq_layout(int G, int P, int C) {
-  PqLayout l = {};
+PqWs carve(Arena& a, int G, int P, int C) {
   const size_t g1 = (size_t)(G > 0 ? G : 0) + 1, p1 = (size_t)(P > 0 ? P : 0) + 1, c = C > 0 ? C : 1;
-  l.slots = hash_slots(P > 0 ? P : 0);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += align256(bytes); return at; };
-  l.zeroed = o;
-  l.hist = take(g1 * p1 * 4);
-  l.keys = take((size_t)l.slots * 4);
-  l.vals = take((size_t)l.slots * 4);
-  l.pmatched = take(p1 * 4);
-  l.crowd_row = take(c * 4);
-  l.zeroed_end = o;
-  l.pcat = take(p1 * 4);
-  l.area_p = take(p1 * 4);
-  l.match_p = take(g1 * 4);
-  l.iou = take(g1 * 8);
-  l.total = o;
-  return l;
+  PqWs w;
+  w.slots = hash_slots(P > 0 ? P : 0);
+  w.zeroed = a.mark();
+  w.hist = a.take<int>(g1 * p1);
+  w.keys = a.take<int>(w.slots);
+  w.vals = a.take<int>(w.slots);
+  w.pmatched = a.take<int>(p1);
+  w.crowd_row = a.take<int>(c);
+  w.zeroed_end = a.mark();
+  w.pcat = a.take<int>(p1);
+  w.area_p = a.take<int>(p1);
+  w.match_p = a.take<int>(g1);
+  w.iou = a.take<double>(g1);
+  return w;
 }
 
 // One workgroup.  hist is complete (the stream orders the launches); everything else here is this workgroup's own.
@@ -346,7 +344,9 @@ extern "C" int jtsm_confusion_lds_cells(void) { return kConfLdsCells; }
 
 extern "C" size_t jtsm_pq_accumulate_workspace_bytes(int G, int P, int C) {
   if ((long)((G > 0 ? G : 0) + 1L) * ((P > 0 ? P : 0) + 1L) > kMaxCells) return 0;
-  return pq_layout(G, P, C).total;
+  Arena a{nullptr};
+  carve(a, G, P, C);
+  return a.off;
 }
 
 extern "C" int jtsm_pq_accumulate(const int32_t* pred, const int32_t* pred_table, const int32_t* num_pred, int P,
@@ -364,31 +364,28 @@ extern "C" int jtsm_pq_accumulate(const int32_t* pred, const int32_t* pred_table
   JTSM_REQUIRE(P == 0 || (pred_table && num_pred), "pq_accumulate: null pred_table / num_pred");
   JTSM_REQUIRE(G == 0 || gt_table, "pq_accumulate: null gt_table");
   JTSM_REQUIRE((num_things == 0 || thing_cat) && (num_stuff == 0 || stuff_cat), "pq_accumulate: null category map");
-  const PqLayout l = pq_layout(G, P, C);
-  JTSM_REQUIRE(workspace && workspace_bytes >= l.total && ((size_t)workspace & 255) == 0,
-               "pq_accumulate: workspace of %zu bytes (256-byte aligned) needed", l.total);
+  Arena arena{static_cast<char*>(workspace)};
+  const PqWs w = carve(arena, G, P, C);
+  JTSM_REQUIRE(workspace && workspace_bytes >= arena.off && ((size_t)workspace & 255) == 0,
+               "pq_accumulate: workspace of %zu bytes (256-byte aligned) needed", arena.off);
   hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  int* hist = reinterpret_cast<int*>(ws + l.hist);
-  int* keys = reinterpret_cast<int*>(ws + l.keys);
-  int* vals = reinterpret_cast<int*>(ws + l.vals);
   u64* st64 = reinterpret_cast<u64*>(stats);
-  const int mask = l.slots - 1;
+  const int mask = w.slots - 1;
 
-  JTSM_CHECK_HIP(hipMemsetAsync(ws + l.zeroed, 0, l.zeroed_end - l.zeroed, st));
+  JTSM_CHECK_HIP(hipMemsetAsync(arena.base + w.zeroed, 0, w.zeroed_end - w.zeroed, st));
   if (P > 0) {
-    hipLaunchKernelGGL(pq_lookup_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, pred_table, num_pred, P, mask, keys,
-                       vals);
+    hipLaunchKernelGGL(pq_lookup_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, pred_table, num_pred, P, mask,
+                       w.keys, w.vals);
     JTSM_CHECK_LAUNCH("pq lookup");
   }
   if (pixels > 0) {
     const bool aligned = (((size_t)pred | (size_t)gt) & 15) == 0;
     const long nvec = aligned ? pixels / 4 : 0;
-    const bool hist_lds = !force_global && cells <= kPqLdsCells, hash_lds = l.slots <= kLdsHash;
+    const bool hist_lds = !force_global && cells <= kPqLdsCells, hash_lds = w.slots <= kLdsHash;
     const dim3 grid(hist_blocks(nvec, pixels)), block(kThreads);
-#define JTSM_PQ_HIST(A, B)                                                                                       \
-  hipLaunchKernelGGL((pq_hist_kernel<A, B>), grid, block, 0, st, pred, gt, pixels, nvec, G, P, (int)cells, keys, \
-                     vals, mask, hist, st64)
+#define JTSM_PQ_HIST(A, B)                                                                                         \
+  hipLaunchKernelGGL((pq_hist_kernel<A, B>), grid, block, 0, st, pred, gt, pixels, nvec, G, P, (int)cells, w.keys, \
+                     w.vals, mask, w.hist, st64)
     if (hist_lds && hash_lds) JTSM_PQ_HIST(true, true);
     else if (hist_lds) JTSM_PQ_HIST(true, false);
     else if (hash_lds) JTSM_PQ_HIST(false, true);
@@ -396,11 +393,9 @@ extern "C" int jtsm_pq_accumulate(const int32_t* pred, const int32_t* pred_table
 #undef JTSM_PQ_HIST
     JTSM_CHECK_LAUNCH("pq hist");
   }
-  hipLaunchKernelGGL(pq_finish_kernel, dim3(1), dim3(kThreads), 0, st, hist, pred_table, num_pred, P, thing_cat,
-                     num_things, stuff_cat, num_stuff, gt_table, G, C, reinterpret_cast<int*>(ws + l.pcat),
-                     reinterpret_cast<int*>(ws + l.area_p), reinterpret_cast<int*>(ws + l.pmatched),
-                     reinterpret_cast<int*>(ws + l.crowd_row), reinterpret_cast<int*>(ws + l.match_p),
-                     reinterpret_cast<double*>(ws + l.iou), reinterpret_cast<u64*>(tp), reinterpret_cast<u64*>(fp),
+  hipLaunchKernelGGL(pq_finish_kernel, dim3(1), dim3(kThreads), 0, st, w.hist, pred_table, num_pred, P, thing_cat,
+                     num_things, stuff_cat, num_stuff, gt_table, G, C, w.pcat, w.area_p, w.pmatched, w.crowd_row,
+                     w.match_p, w.iou, reinterpret_cast<u64*>(tp), reinterpret_cast<u64*>(fp),
                      reinterpret_cast<u64*>(fn), iou_sum, st64);
   JTSM_CHECK_LAUNCH("pq finish");
   return JTSM_OK;

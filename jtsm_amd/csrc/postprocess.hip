@@ -173,7 +173,7 @@ __global__ __launch_bounds__(64) void nms_bits_kernel(const float4* __restrict__
   }
   if (live) {
     const bool use_trick = trick == 1 || (trick == 2 && h->n_valid < 40000);
-    const float step = use_trick ? ordered_int_to_float(h->max_coord) + 1.0f : 0.f;
+    const float step = use_trick ? float_from_order_bits(h->max_coord) + 1.0f : 0.f;
     const int q = col0 + t;
     int qc = K;
     if (q < N) {
@@ -221,10 +221,10 @@ __global__ __launch_bounds__(256) void det_emit_kernel(const int* __restrict__ o
 }
 
 // elements already written (ebox / escore / eclass / header); runs sort -> bits -> scan -> sort (nms_stages.h)
-int nms_core(char* ws, const NmsLayout& l, float thr, int trick, hipStream_t st) {
-  const float4* ebox = reinterpret_cast<const float4*>(ws + l.ebox);
-  return nms_stages(ws, l, st, [&](const u64* keys, const int* sidx, NmsHeader* h, u64* mask) {
-    hipLaunchKernelGGL(nms_bits_kernel, dim3(l.nblk, l.W), dim3(64), 0, st, ebox, keys, sidx, l.N, l.K, l.W, thr, trick, h,
+int nms_core(const NmsWs& w, float thr, int trick, hipStream_t st) {
+  const float4* ebox = static_cast<const float4*>(w.ebox);
+  return nms_stages(w, st, [&](const u64* keys, const int* sidx, NmsHeader* h, u64* mask) {
+    hipLaunchKernelGGL(nms_bits_kernel, dim3(w.nblk, w.W), dim3(64), 0, st, ebox, keys, sidx, w.N, w.K, w.W, thr, trick, h,
                        mask);
     JTSM_CHECK_LAUNCH("nms bits");
     return (int)JTSM_OK;
@@ -541,7 +541,9 @@ int jtsm_oicr_predict_f32(const float* const* logits, const float* const* deltas
 
 size_t jtsm_batched_nms_workspace_bytes(int n, int num_classes, int max_per_class) {
   if (n <= 0 || num_classes <= 0) return 256;
-  return nms_layout(n, num_classes, max_per_class, 0).total;
+  Arena a{nullptr};
+  carve(a, n, num_classes, max_per_class, 0);
+  return a.off;
 }
 
 int jtsm_batched_nms_f32(const float* boxes, const float* scores, const int64_t* idxs, int n, int num_classes,
@@ -558,29 +560,29 @@ int jtsm_batched_nms_f32(const float* boxes, const float* scores, const int64_t*
   }
   JTSM_REQUIRE(boxes && scores && idxs && keep, "batched_nms: null pointer");
   JTSM_REQUIRE(((size_t)boxes & 15) == 0, "batched_nms: boxes must be 16-byte aligned");
-  const NmsLayout l = nms_layout(n, num_classes, max_per_class, 0);
-  JTSM_REQUIRE(workspace && workspace_bytes >= l.total && ((size_t)workspace & 255) == 0,
-               "batched_nms: workspace of %zu bytes (256-byte aligned) needed", l.total);
-  JTSM_REQUIRE((size_t)2 * l.W * 8 <= 64 * 1024, "batched_nms: max_per_class %d too large", max_per_class);
-  char* ws = reinterpret_cast<char*>(workspace);
-  NmsHeader* h = reinterpret_cast<NmsHeader*>(ws + l.header);
-  hipLaunchKernelGGL(nms_header_init, dim3(1), dim3(1), 0, st, h);
+  Arena arena{static_cast<char*>(workspace)};
+  const NmsWs w = carve(arena, n, num_classes, max_per_class, 0);
+  JTSM_REQUIRE(workspace && workspace_bytes >= arena.off && ((size_t)workspace & 255) == 0,
+               "batched_nms: workspace of %zu bytes (256-byte aligned) needed", arena.off);
+  JTSM_REQUIRE((size_t)2 * w.W * 8 <= 64 * 1024, "batched_nms: max_per_class %d too large", max_per_class);
+  hipLaunchKernelGGL(nms_header_init, dim3(1), dim3(1), 0, st, w.header);
   hipLaunchKernelGGL(nms_elements_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st,
                      reinterpret_cast<const float4*>(boxes), scores, idxs, n, num_classes,
-                     reinterpret_cast<float4*>(ws + l.ebox), reinterpret_cast<float*>(ws + l.escore),
-                     reinterpret_cast<int*>(ws + l.eclass), h);
+                     static_cast<float4*>(w.ebox), w.escore, w.eclass, w.header);
   JTSM_CHECK_LAUNCH("nms elements");
-  int rc = nms_core(ws, l, iou_threshold, coordinate_trick, st);
+  int rc = nms_core(w, iou_threshold, coordinate_trick, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(nms_emit_keep_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st,
-                     reinterpret_cast<const int*>(ws + l.order), n, h, keep, num_keep, overflow);
+  hipLaunchKernelGGL(nms_emit_keep_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, w.order, n, w.header, keep,
+                     num_keep, overflow);
   JTSM_CHECK_LAUNCH("nms emit");
   return JTSM_OK;
 }
 
 size_t jtsm_fast_rcnn_inference_workspace_bytes(int R, int K) {
   if (R <= 0 || K <= 0) return 256;
-  return nms_layout(R * K, K, R, R).total;
+  Arena a{nullptr};
+  carve(a, R * K, K, R, R);
+  return a.off;
 }
 
 int jtsm_fast_rcnn_inference_f32(const float* boxes, const float* scores, int R, int K, int Kb, float img_h,
@@ -598,26 +600,23 @@ int jtsm_fast_rcnn_inference_f32(const float* boxes, const float* scores, int R,
   JTSM_REQUIRE(boxes && scores && out_boxes && out_scores && out_classes && out_rows, "fast_rcnn_inference: null pointer");
   JTSM_REQUIRE(((size_t)out_boxes & 15) == 0, "fast_rcnn_inference: out_boxes must be 16-byte aligned");
   const int N = R * K;
-  const NmsLayout l = nms_layout(N, K, R, R);
-  JTSM_REQUIRE(workspace && workspace_bytes >= l.total && ((size_t)workspace & 255) == 0,
-               "fast_rcnn_inference: workspace of %zu bytes (256-byte aligned) needed", l.total);
-  JTSM_REQUIRE((size_t)2 * l.W * 8 <= 64 * 1024, "fast_rcnn_inference: R=%d too large", R);
-  char* ws = reinterpret_cast<char*>(workspace);
-  NmsHeader* h = reinterpret_cast<NmsHeader*>(ws + l.header);
-  uint8_t* valid = reinterpret_cast<uint8_t*>(ws + l.rowvalid);
-  float4* ebox = reinterpret_cast<float4*>(ws + l.ebox);
-  float* escore = reinterpret_cast<float*>(ws + l.escore);
-  hipLaunchKernelGGL(nms_header_init, dim3(1), dim3(1), 0, st, h);
-  hipLaunchKernelGGL(det_row_valid_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, st, boxes, Kb * 4, scores, K + 1, R, valid);
+  Arena arena{static_cast<char*>(workspace)};
+  const NmsWs w = carve(arena, N, K, R, R);
+  JTSM_REQUIRE(workspace && workspace_bytes >= arena.off && ((size_t)workspace & 255) == 0,
+               "fast_rcnn_inference: workspace of %zu bytes (256-byte aligned) needed", arena.off);
+  JTSM_REQUIRE((size_t)2 * w.W * 8 <= 64 * 1024, "fast_rcnn_inference: R=%d too large", R);
+  float4* ebox = static_cast<float4*>(w.ebox);
+  hipLaunchKernelGGL(nms_header_init, dim3(1), dim3(1), 0, st, w.header);
+  hipLaunchKernelGGL(det_row_valid_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, st, boxes, Kb * 4, scores, K + 1, R,
+                     w.rowvalid);
   JTSM_CHECK_LAUNCH("det row valid");
-  hipLaunchKernelGGL(det_elements_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, boxes, Kb, scores, R, K, valid, img_h,
-                     img_w, score_thresh, ebox, escore, reinterpret_cast<int*>(ws + l.eclass), h);
+  hipLaunchKernelGGL(det_elements_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, boxes, Kb, scores, R, K, w.rowvalid,
+                     img_h, img_w, score_thresh, ebox, w.escore, w.eclass, w.header);
   JTSM_CHECK_LAUNCH("det elements");
-  int rc = nms_core(ws, l, nms_thresh, 2, st);
+  int rc = nms_core(w, nms_thresh, 2, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(det_emit_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st,
-                     reinterpret_cast<const int*>(ws + l.order), ebox, escore, K, topk, cap, h,
-                     reinterpret_cast<float4*>(out_boxes), out_scores, out_classes, out_rows, out_count);
+  hipLaunchKernelGGL(det_emit_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st, w.order, ebox, w.escore, K, topk, cap,
+                     w.header, reinterpret_cast<float4*>(out_boxes), out_scores, out_classes, out_rows, out_count);
   JTSM_CHECK_LAUNCH("det emit");
   return JTSM_OK;
 }

@@ -263,7 +263,9 @@ int jtsm_box_iou_rotated_f32(const float* boxes1, const float* boxes2, int N, in
 
 size_t jtsm_batched_nms_rotated_workspace_bytes(int n, int num_classes, int max_per_class) {
   if (n <= 0 || num_classes <= 0) return 256;
-  return nms_layout(n, num_classes, max_per_class, 0, 20).total;
+  Arena a{nullptr};
+  carve(a, n, num_classes, max_per_class, 0, 20);
+  return a.off;
 }
 
 int jtsm_batched_nms_rotated_f32(const float* boxes, const float* scores, const int64_t* idxs, int n, int num_classes,
@@ -279,26 +281,25 @@ int jtsm_batched_nms_rotated_f32(const float* boxes, const float* scores, const 
     return JTSM_OK;
   }
   JTSM_REQUIRE(boxes && scores && keep, "batched_nms_rotated: null pointer");
-  const NmsLayout l = nms_layout(n, num_classes, max_per_class, 0, 20);
-  JTSM_REQUIRE(workspace && workspace_bytes >= l.total && ((size_t)workspace & 255) == 0,
-               "batched_nms_rotated: workspace of %zu bytes (256-byte aligned) needed", l.total);
-  JTSM_REQUIRE((size_t)2 * l.W * 8 <= 64 * 1024, "batched_nms_rotated: max_per_class %d too large", max_per_class);
-  char* ws = reinterpret_cast<char*>(workspace);
-  NmsHeader* h = reinterpret_cast<NmsHeader*>(ws + l.header);
-  float* ebox = reinterpret_cast<float*>(ws + l.ebox);
-  hipLaunchKernelGGL(nms_header_init, dim3(1), dim3(1), 0, st, h);
+  Arena arena{static_cast<char*>(workspace)};
+  const NmsWs w = carve(arena, n, num_classes, max_per_class, 0, 20);
+  JTSM_REQUIRE(workspace && workspace_bytes >= arena.off && ((size_t)workspace & 255) == 0,
+               "batched_nms_rotated: workspace of %zu bytes (256-byte aligned) needed", arena.off);
+  JTSM_REQUIRE((size_t)2 * w.W * 8 <= 64 * 1024, "batched_nms_rotated: max_per_class %d too large", max_per_class);
+  float* ebox = static_cast<float*>(w.ebox);
+  hipLaunchKernelGGL(nms_header_init, dim3(1), dim3(1), 0, st, w.header);
   hipLaunchKernelGGL(rnms_elements_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, boxes, scores, idxs, n, num_classes,
-                     ebox, reinterpret_cast<float*>(ws + l.escore), reinterpret_cast<int*>(ws + l.eclass));
+                     ebox, w.escore, w.eclass);
   JTSM_CHECK_LAUNCH("nms rotated elements");
-  const int rc = nms_stages(ws, l, st, [&](const u64* keys, const int* sidx, NmsHeader*, u64* mask) {
-    hipLaunchKernelGGL(rnms_bits_kernel, dim3(l.nblk, l.W), dim3(64), 0, st, ebox, keys, sidx, n, num_classes, l.W,
+  const int rc = nms_stages(w, st, [&](const u64* keys, const int* sidx, NmsHeader*, u64* mask) {
+    hipLaunchKernelGGL(rnms_bits_kernel, dim3(w.nblk, w.W), dim3(64), 0, st, ebox, keys, sidx, n, num_classes, w.W,
                        iou_threshold, mask);
     JTSM_CHECK_LAUNCH("nms rotated bits");
     return (int)JTSM_OK;
   });
   if (rc) return rc;
-  hipLaunchKernelGGL(nms_emit_keep_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st,
-                     reinterpret_cast<const int*>(ws + l.order), n, h, keep, num_keep, overflow);
+  hipLaunchKernelGGL(nms_emit_keep_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, w.order, n, w.header, keep,
+                     num_keep, overflow);
   JTSM_CHECK_LAUNCH("nms rotated emit");
   return JTSM_OK;
 }

@@ -12,21 +12,21 @@
 //             order; the ten thresholds' claimed sets are one 16-bit word per ground-truth box in the workspace.  The
 //             segment's first detection settles CorLoc of that image (integer atomics: order-independent).
 //   ap        one workgroup per (class, threshold): the class's ranked TP / FP bits in chunks of kApChunk with a block
-//             scan carrying the running sums; 11-point and area form.
+//             scan carrying the running sums; 11-point and area form (the latter's chunk step: eval_walk.h).
+// Key width, sort scratch and class starts: sorted_segments.h; the workspace: carve() below, over workspace.h's Arena.
 //
 // Everything after the quantisation is fp64.  This file is compiled with -ffp-contract=off (jtsm_amd/build.py): `uni`
 // is a*b + c*d - inters, and a fused multiply-add rounds once where the reference rounds twice.
-#include <hipcub/hipcub.hpp>
-
 #include <cfloat>
 #include <climits>
 
-#include "common.h"
+#include "eval_walk.h"
+#include "sorted_segments.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
 
-typedef unsigned long long u64;
 typedef unsigned int u32;
 typedef unsigned short u16;
 
@@ -40,14 +40,6 @@ struct EvalHeader {
   u32 score_min_inv;   // ~ordered encoding of the smallest score
   u32 pad[2];
 };
-
-__device__ __forceinline__ u32 ordered(float f) {
-  const u32 u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unordered(u32 e) {
-  return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
-}
 
 __device__ __forceinline__ double thr_of(int t) { return (double)(50 + 5 * t) / 100.0; }
 
@@ -79,7 +71,7 @@ __global__ __launch_bounds__(256) void voc_quantise_kernel(const float4* __restr
     mkey[d] = ((u64)c << (image_bits + kScoreBits)) | ((u64)im << kScoreBits) | low;
     rkey[d] = ((u64)c << kScoreBits) | low;
     iota[d] = d;
-    emax = ordered(s);
+    emax = float_order_bits(s);
     emin_inv = ~emax;
   }
   for (int o = 32; o > 0; o >>= 1) {
@@ -90,20 +82,6 @@ __global__ __launch_bounds__(256) void voc_quantise_kernel(const float4* __restr
     atomicMax(&hdr->score_max, emax);
     atomicMax(&hdr->score_min_inv, emin_inv);
   }
-}
-
-// start[c] = first rank position of class c, c in [0, C]; start[C] = number of valid detections
-__global__ __launch_bounds__(64) void voc_class_start_kernel(const u64* __restrict__ rkey_sorted, int D, int C,
-                                                             int* __restrict__ start) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  if (c > C) return;
-  const u64 want = (u64)c << kScoreBits;
-  int lo = 0, hi = D;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo) / 2;
-    if (rkey_sorted[mid] < want) lo = mid + 1; else hi = mid;
-  }
-  start[c] = lo;
 }
 
 // counts[c] = {npos: non-difficult boxes of the class, npos_im: images holding at least one}
@@ -217,19 +195,15 @@ __global__ __launch_bounds__(kApChunk) void voc_ap_kernel(const int* __restrict_
                                                           double* __restrict__ ap_out, double* __restrict__ corloc_out,
                                                           double* __restrict__ stats, int* __restrict__ order) {
 #pragma clang fp contract(off)
-  typedef hipcub::BlockScan<u64, kApChunk> SumScan;
-  typedef hipcub::BlockScan<double, kApChunk> MaxScan;
+  typedef RankedWalk<kApChunk> Walk;              // (eval_walk.h)
   typedef hipcub::BlockReduce<double, kApChunk> Reduce;
   typedef hipcub::BlockReduce<u64, kApChunk> ReduceU;
   __shared__ union {
-    typename SumScan::TempStorage sum;
-    typename MaxScan::TempStorage mx;
+    typename Walk::Temp walk;
     typename Reduce::TempStorage red;
     typename ReduceU::TempStorage redu;
   } temp;
-  __shared__ double sh_a[kApChunk];
-  __shared__ double sh_b[kApChunk];
-  __shared__ u64 sh_u;
+  __shared__ typename Walk::Shared sh;
   const int c = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
   const int base = start[c], n = start[c + 1] - base;
   const double npos = (double)counts[2 * c];
@@ -239,8 +213,8 @@ __global__ __launch_bounds__(kApChunk) void voc_ap_kernel(const int* __restrict_
     const int npos_im = counts[2 * c + 1];
     corloc_out[t * C + c] = n == 0 ? 0.0 : (npos_im == 0 ? (double)NAN : (double)corloc_cnt[c * kThr + t] / (double)npos_im);
     if (c == 0 && t == 0) {
-      stats[0] = D > 0 ? (double)unordered(~hdr->score_min_inv) : 0.0;
-      stats[1] = D > 0 ? (double)unordered(hdr->score_max) : 0.0;
+      stats[0] = D > 0 ? (double)float_from_order_bits(~hdr->score_min_inv) : 0.0;
+      stats[1] = D > 0 ? (double)float_from_order_bits(hdr->score_max) : 0.0;
       stats[2] = (double)(D - start[C]);      // detections whose class or image index was out of range
       stats[3] = 0.0;
     }
@@ -262,11 +236,11 @@ __global__ __launch_bounds__(kApChunk) void voc_ap_kernel(const int* __restrict_
       const bool valid = k < n;
       if (valid && t == 0 && order) order[ridx[base + k]] = k;
       u64 inc;
-      SumScan(temp.sum).InclusiveSum(valid ? bits_of(k) : 0ull, inc);
+      typename Walk::SumScan(temp.walk.sum).InclusiveSum(valid ? bits_of(k) : 0ull, inc);
       inc += carry;
-      if (tid == kApChunk - 1) sh_u = inc;
+      if (tid == kApChunk - 1) sh.u = inc;
       __syncthreads();
-      carry = sh_u;
+      carry = sh.u;
       __syncthreads();
       if (valid) {
         const double tpc = (double)(inc >> 32), fpc = (double)(inc & 0xffffffffull);
@@ -289,89 +263,66 @@ __global__ __launch_bounds__(kApChunk) void voc_ap_kernel(const int* __restrict_
       if (t == 0 && order) order[ridx[base + k]] = k;
     }
     const u64 tot = ReduceU(temp.redu).Sum(mine);
-    if (tid == 0) sh_u = tot;
+    if (tid == 0) sh.u = tot;
     __syncthreads();
-    u64 end = sh_u;                            // running sums at the end of the current chunk
+    u64 end = sh.u;                            // running sums at the end of the current chunk
     __syncthreads();
     double env_carry = 0.0;                    // the envelope right of the current chunk (the sentinel 0 at the end)
     for (int ch = nchunk - 1; ch >= 0; --ch) {
       const int k = ch * kApChunk + tid;
       const bool valid = k < n;
       const u64 b = valid ? bits_of(k) : 0ull;
-      u64 inc;
-      SumScan(temp.sum).InclusiveSum(b, inc);
-      if (tid == kApChunk - 1) sh_u = inc;
-      __syncthreads();
-      const u64 begin = end - sh_u;
-      inc += begin;
+      const u64 inc = Walk::running_sum(temp.walk, sh, b, end);      // (one barrier; `end` is now the chunk's begin)
       const double tpc = (double)(inc >> 32), fpc = (double)(inc & 0xffffffffull);
       const double rec = tpc / npos, prec = valid ? tpc / fmax(tpc + fpc, DBL_EPSILON) : 0.0;
       const double prev = k == 0 ? 0.0 : (double)((inc - b) >> 32) / npos;
-      sh_a[tid] = prec;
-      __syncthreads();
-      double smax;                             // suffix maximum inside the chunk: a prefix scan of the reversed chunk
-      MaxScan(temp.mx).InclusiveScan(sh_a[kApChunk - 1 - tid], smax, hipcub::Max());
-      sh_b[kApChunk - 1 - tid] = fmax(smax, env_carry);
-      __syncthreads();
-      const double env = sh_b[tid];
-      env_carry = sh_b[0];
+      const double env = Walk::envelope(temp.walk, sh, prec, env_carry);          // (two barriers)
       const double term = (valid && rec != prev) ? (rec - prev) * env : 0.0;
       const double s = Reduce(temp.red).Sum(term);
       ap = ap + s;                             // (thread 0)
-      end = begin;
-      __syncthreads();
+      __syncthreads();                         // temp and sh are free for the next chunk
     }
   }
   if (tid == 0) ap_out[t * C + c] = ap;
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int bits_for(long k) {   // bits needed to hold values 0..k
-  int b = 1;
-  while ((1L << b) <= k) ++b;
-  return b;
-}
-
-struct EvalLayout {
-  size_t zeroed, header, corloc_cnt, claimed, zeroed_end;
-  size_t start, mkey_a, mkey_b, rkey_a, rkey_b, iota, midx, ridx, bbq, tp, fp, cub, total;
+struct EvalWs {
+  size_t zeroed, zeroed_end;        // arena marks around header, corloc_cnt and claimed: cleared by one memset
+  EvalHeader* header;
+  int* corloc_cnt;
+  u16* claimed;
+  int* start;
+  u64 *mkey_a, *mkey_b, *rkey_a, *rkey_b;
+  int *iota, *midx, *ridx;
+  double4* bbq;
+  u16 *tp, *fp;
+  char* cub;
   size_t cub_bytes;
 };
 
-size_t cub_temp_bytes(int D) {
-  size_t a = 0;
-  u64* k = nullptr;
-  int* v = nullptr;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, k, k, v, v, D, 0, 64, (hipStream_t) nullptr);
-  return a;
-}
-
-EvalLayout eval_layout(int D, int G, int C) {
-  EvalLayout l = {};
+EvalWs carve(Arena& a, int D, int G, int C) {
   const size_t d = D > 0 ? D : 0, g = G > 0 ? G : 0, c = C > 0 ? C : 0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += align256(bytes ? bytes : 1); return at; };
-  l.zeroed = o;
-  l.header = take(sizeof(EvalHeader));
-  l.corloc_cnt = take(c * kThr * 4);
-  l.claimed = take(g * 2);
-  l.zeroed_end = o;
-  l.start = take((c + 2) * 4);
-  l.mkey_a = take(d * 8);
-  l.mkey_b = take(d * 8);
-  l.rkey_a = take(d * 8);
-  l.rkey_b = take(d * 8);
-  l.iota = take(d * 4);
-  l.midx = take(d * 4);
-  l.ridx = take(d * 4);
-  l.bbq = take(d * 32);
-  l.tp = take(d * 2);
-  l.fp = take(d * 2);
-  l.cub_bytes = D > 0 ? cub_temp_bytes(D) : 0;
-  l.cub = take(l.cub_bytes);
-  l.total = o;
-  return l;
+  a.pad_empty = true;
+  EvalWs w;
+  w.zeroed = a.mark();
+  w.header = a.take<EvalHeader>(1);
+  w.corloc_cnt = a.take<int>(c * kThr);
+  w.claimed = a.take<u16>(g);
+  w.zeroed_end = a.mark();
+  w.start = a.take<int>(c + 2);
+  w.mkey_a = a.take<u64>(d);
+  w.mkey_b = a.take<u64>(d);
+  w.rkey_a = a.take<u64>(d);
+  w.rkey_b = a.take<u64>(d);
+  w.iota = a.take<int>(d);
+  w.midx = a.take<int>(d);
+  w.ridx = a.take<int>(d);
+  w.bbq = a.take<double4>(d);
+  w.tp = a.take<u16>(d);
+  w.fp = a.take<u16>(d);
+  w.cub_bytes = D > 0 ? sort_pairs_temp_bytes(D) : 0;
+  w.cub = a.take<char>(w.cub_bytes);
+  return w;
 }
 
 }  // namespace
@@ -379,7 +330,11 @@ EvalLayout eval_layout(int D, int G, int C) {
 
 using namespace jtsm;
 
-extern "C" size_t jtsm_voc_eval_workspace_bytes(int D, int G, int C) { return eval_layout(D, G, C).total; }
+extern "C" size_t jtsm_voc_eval_workspace_bytes(int D, int G, int C) {
+  Arena a{nullptr};
+  carve(a, D, G, C);
+  return a.off;
+}
 
 extern "C" int jtsm_voc_eval(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
                              const int32_t* det_images, int D, const int32_t* gt_boxes, const uint8_t* gt_difficult,
@@ -395,28 +350,16 @@ extern "C" int jtsm_voc_eval(const float* det_boxes, const float* det_scores, co
   JTSM_REQUIRE(D == 0 || (det_boxes && det_scores && det_classes && det_images), "voc_eval: null detections");
   JTSM_REQUIRE(G == 0 || (gt_boxes && gt_difficult), "voc_eval: null ground truth");
   JTSM_REQUIRE(((size_t)det_boxes & 15) == 0 && ((size_t)gt_boxes & 15) == 0, "voc_eval: boxes must be 16-byte aligned");
-  const EvalLayout l = eval_layout(D, G, C);
-  JTSM_REQUIRE(workspace && workspace_bytes >= l.total && ((size_t)workspace & 255) == 0,
-               "voc_eval: workspace of %zu bytes (256-byte aligned) needed", l.total);
+  Arena arena{static_cast<char*>(workspace)};
+  const EvalWs w = carve(arena, D, G, C);
+  JTSM_REQUIRE(workspace && workspace_bytes >= arena.off && ((size_t)workspace & 255) == 0,
+               "voc_eval: workspace of %zu bytes (256-byte aligned) needed", arena.off);
   hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  EvalHeader* hdr = reinterpret_cast<EvalHeader*>(ws + l.header);
-  int* corloc_cnt = reinterpret_cast<int*>(ws + l.corloc_cnt);
-  u16* claimed = reinterpret_cast<u16*>(ws + l.claimed);
-  int* start = reinterpret_cast<int*>(ws + l.start);
-  u64* mkey_a = reinterpret_cast<u64*>(ws + l.mkey_a);
-  u64* mkey_b = reinterpret_cast<u64*>(ws + l.mkey_b);
-  u64* rkey_a = reinterpret_cast<u64*>(ws + l.rkey_a);
-  u64* rkey_b = reinterpret_cast<u64*>(ws + l.rkey_b);
-  int* iota = reinterpret_cast<int*>(ws + l.iota);
-  int* midx = reinterpret_cast<int*>(ws + l.midx);
-  int* ridx = reinterpret_cast<int*>(ws + l.ridx);
-  double4* bbq = reinterpret_cast<double4*>(ws + l.bbq);
-  u16* tp = tp_bits ? tp_bits : reinterpret_cast<u16*>(ws + l.tp);
-  u16* fp = fp_bits ? fp_bits : reinterpret_cast<u16*>(ws + l.fp);
+  u16* tp = tp_bits ? tp_bits : w.tp;
+  u16* fp = fp_bits ? fp_bits : w.fp;
   const int image_bits = bits_for(N - 1), class_bits = bits_for(C);
 
-  JTSM_CHECK_HIP(hipMemsetAsync(ws + l.zeroed, 0, l.zeroed_end - l.zeroed, st));
+  JTSM_CHECK_HIP(hipMemsetAsync(arena.base + w.zeroed, 0, w.zeroed_end - w.zeroed, st));
   JTSM_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)C * 2 * sizeof(int32_t), st));
   hipLaunchKernelGGL(voc_counts_kernel, dim3(ceil_div((long)N * C, 256)), dim3(256), 0, st, gt_difficult, gt_offsets, N,
                      C, counts);
@@ -427,24 +370,26 @@ extern "C" int jtsm_voc_eval(const float* det_boxes, const float* det_scores, co
     if (order) JTSM_CHECK_HIP(hipMemsetAsync(order, 0xff, (size_t)D * 4, st));
     hipLaunchKernelGGL(voc_quantise_kernel, dim3(ceil_div(D, 256)), dim3(256), 0, st,
                        reinterpret_cast<const float4*>(det_boxes), det_scores, det_classes, det_images, D, N, C,
-                       image_bits, bbq, mkey_a, rkey_a, iota, hdr);
+                       image_bits, w.bbq, w.mkey_a, w.rkey_a, w.iota, w.header);
     JTSM_CHECK_LAUNCH("voc quantise");
-    size_t cub_bytes = l.cub_bytes;
-    JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + l.cub, cub_bytes, mkey_a, mkey_b, iota, midx, D, 0,
+    size_t cub_bytes = w.cub_bytes;
+    JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, cub_bytes, w.mkey_a, w.mkey_b, w.iota, w.midx, D, 0,
                                                       kScoreBits + image_bits + class_bits, st));
-    cub_bytes = l.cub_bytes;
-    JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(ws + l.cub, cub_bytes, rkey_a, rkey_b, iota, ridx, D, 0,
+    cub_bytes = w.cub_bytes;
+    JTSM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, cub_bytes, w.rkey_a, w.rkey_b, w.iota, w.ridx, D, 0,
                                                       kScoreBits + class_bits, st));
   }
-  hipLaunchKernelGGL(voc_class_start_kernel, dim3(ceil_div(C + 1, 64)), dim3(64), 0, st, rkey_b, D, C, start);
+  hipLaunchKernelGGL(segment_starts_kernel, dim3(ceil_div(C + 1, 64)), dim3(64), 0, st, w.rkey_b, D, C, kScoreBits,
+                     w.start);
   JTSM_CHECK_LAUNCH("voc class start");
   if (D > 0) {
-    hipLaunchKernelGGL(voc_match_kernel, dim3(ceil_div(D, 4)), dim3(256), 0, st, mkey_b, midx, D, N, C, image_bits, bbq,
-                       reinterpret_cast<const int4*>(gt_boxes), gt_difficult, gt_offsets, claimed, corloc_cnt, tp, fp);
+    hipLaunchKernelGGL(voc_match_kernel, dim3(ceil_div(D, 4)), dim3(256), 0, st, w.mkey_b, w.midx, D, N, C, image_bits,
+                       w.bbq, reinterpret_cast<const int4*>(gt_boxes), gt_difficult, gt_offsets, w.claimed, w.corloc_cnt,
+                       tp, fp);
     JTSM_CHECK_LAUNCH("voc match");
   }
-  hipLaunchKernelGGL(voc_ap_kernel, dim3(C, kThr), dim3(kApChunk), 0, st, ridx, start, tp, fp, counts, corloc_cnt, C, D,
-                     use_07_metric, hdr, ap, corloc, stats, order);
+  hipLaunchKernelGGL(voc_ap_kernel, dim3(C, kThr), dim3(kApChunk), 0, st, w.ridx, w.start, tp, fp, counts,
+                     w.corloc_cnt, C, D, use_07_metric, w.header, ap, corloc, stats, order);
   JTSM_CHECK_LAUNCH("voc ap");
   return JTSM_OK;
 }

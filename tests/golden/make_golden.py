@@ -23,6 +23,9 @@ Sources of truth
     configs[4] steps on the GPU), the convolution tests' shapes and a grid around the rule boundaries.  Needs only the
     built library: `python tests/golden/make_golden.py conv_plan_table`.  It pins the rules as they are; re-record it
     in the pull request that changes one on purpose.
+  * workspace_sizes.npz: what the workspace queries of the device-side sorters answer (tests/test_capi.py:
+    WORKSPACE_SIZE_CASES), recorded before their layouts moved onto csrc/workspace.h.  Needs only the built library:
+    `python tests/golden/make_golden.py workspace_size_table`.
   * roi_align_fresh_ref.json: SHA-256 digests of the REFERENCE's compiled ROIAlign / ROIAlignRotated results on the
     seeded inputs of tests/test_oracle_pooling.py: fresh_calls().
 """
@@ -228,8 +231,23 @@ def conv_plan_table():
     print(CONV_PLAN_TABLE, shapes.shape, answers.shape, os.path.getsize(CONV_PLAN_TABLE))
 
 
+def workspace_size_table():
+    sys.path.insert(0, os.path.dirname(HERE))
+    from jtsm_amd import _lib
+    from test_capi import WORKSPACE_SIZE_CASES, WORKSPACE_SIZE_TABLE, workspace_size_answers
+
+    out = {}
+    for name, cases in WORKSPACE_SIZE_CASES.items():
+        out[name + "_args"] = np.array(cases, dtype=np.int64)
+        out[name + "_bytes"] = np.array(workspace_size_answers(_lib.lib(), name), dtype=np.int64)
+    np.savez_compressed(WORKSPACE_SIZE_TABLE, **out)
+    print(WORKSPACE_SIZE_TABLE, {k: v.tolist() for k, v in out.items() if k.endswith("_bytes")})
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["conv_plan_table"]:
         conv_plan_table()
+    elif sys.argv[1:] == ["workspace_size_table"]:
+        workspace_size_table()
     else:
         main()

@@ -183,6 +183,76 @@ def test_conv_planning_answers_match_the_recorded_table():
         len(bad), shapes[bad[0][0]].tolist(), bad[0][1], got[tuple(bad[0])], want[tuple(bad[0])])
 
 
+WORKSPACE_SIZE_TABLE = os.path.join(ROOT, "tests", "golden", "workspace_sizes.npz")
+
+# The argument sets of the recorded workspace-size table, per `jtsm_<name>_workspace_bytes` query: the empty cases, sizes
+# one below / at / above a multiple of 64 and a mid-sized case each.  Every sorted array (D, n, R * K) holds at most 1024 items.
+WORKSPACE_SIZE_CASES = {
+    "voc_eval": [(0, 0, 1), (1, 1, 1), (0, 5, 3), (5, 0, 3), (63, 63, 20), (64, 64, 20), (65, 65, 20), (257, 70, 20),
+                 (127, 128, 129), (1000, 300, 80), (1024, 2000, 200)],                               # D, G, C
+    "coco_image": [(0, 0, 1, 0, 0, 100), (1, 1, 1, 0, 0, 100), (0, 3, 2, 0, 0, 1), (63, 64, 80, 0, 0, 100),
+                   (64, 63, 80, 0, 0, 100), (65, 65, 80, 0, 0, 100), (100, 30, 80, 0, 0, 128), (5, 4, 3, 17, 13, 100),
+                   (64, 65, 80, 64, 64, 100), (100, 20, 80, 480, 640, 100), (10, 10, 5, 0, 0, 129),
+                   (300, 130, 80, 0, 0, 100)],                                                       # n, G, K, H, W, max_det
+    "coco_accumulate": [(0, 1), (1, 1), (63, 1), (64, 80), (65, 80), (127, 64), (128, 63), (129, 65), (1000, 80),
+                        (1024, 91)],                                                                 # D, K
+    "pq_accumulate": [(0, 0, 1), (1, 1, 1), (0, 31, 1), (31, 0, 5), (32, 32, 10), (63, 63, 133), (64, 64, 133),
+                      (65, 65, 133), (20, 30, 133), (200, 2000, 133), (1023, 1024, 133)],            # G, P, C
+    "batched_nms": [(0, 1, 0), (5, 0, 5), (1, 1, 0), (1, 1, 1), (63, 1, 63), (64, 1, 64), (65, 1, 65), (130, 65, 2),
+                    (128, 80, 64), (1000, 80, 100), (1024, 80, 1024)],                               # n, K, max_per_class
+    "fast_rcnn_inference": [(0, 1), (1, 0), (1, 1), (63, 1), (64, 1), (65, 1), (1, 80), (50, 20), (12, 80), (16, 64),
+                            (15, 65)],                                                               # R, K
+    "mine_top_p": [(0, 0, 0), (1, 0, 5), (1, 1, 1), (1, 1, 63), (1, 1, 64), (1, 1, 65), (2, 20, 63), (2, 20, 100),
+                   (8, 80, 300)],                                                                    # B, G, t_max
+    "roi_merge": [(0, 0), (1, 0), (1, 1), (1, 63), (1, 64), (1, 65), (63, 100), (64, 100), (65, 100), (2, 1000),
+                  (8, 4000)],                                                                        # B, R
+}
+WORKSPACE_SIZE_CASES["batched_nms_rotated"] = WORKSPACE_SIZE_CASES["batched_nms"]
+
+
+def workspace_size_answers(lib, name):
+    query = {"voc_eval": lambda D, G, K: lib.jtsm_voc_eval_workspace_bytes(D, G, K),
+             "coco_image": lambda n, G, K, H, W, m: lib.jtsm_coco_image_workspace_bytes(n, G, K, H, W, m),
+             "coco_accumulate": lambda D, K: lib.jtsm_coco_accumulate_workspace_bytes(D, K),
+             "pq_accumulate": lambda G, P, K: lib.jtsm_pq_accumulate_workspace_bytes(G, P, K),
+             "batched_nms": lambda n, K, m: lib.jtsm_batched_nms_workspace_bytes(n, K, m),
+             "batched_nms_rotated": lambda n, K, m: lib.jtsm_batched_nms_rotated_workspace_bytes(n, K, m),
+             "fast_rcnn_inference": lambda R, K: lib.jtsm_fast_rcnn_inference_workspace_bytes(R, K),
+             "mine_top_p": lambda B, G, t: lib.jtsm_mine_top_p_workspace_bytes(B, G, t),
+             "roi_merge": lambda B, R: lib.jtsm_roi_merge_workspace_bytes(B, R)}[name]
+    return [query(*args) for args in WORKSPACE_SIZE_CASES[name]]
+
+
+def test_workspace_sizes_match_the_recorded_table():
+    """tests/golden/workspace_sizes.npz (tests/golden/make_golden.py: workspace_size_table) holds what the workspace
+    queries of the device-side sorters answered for WORKSPACE_SIZE_CASES before their layouts moved onto the one arena
+    of csrc/workspace.h: every buffer, its alignment and the empty-buffer rule of each entry point show here as bytes.
+    Every case keeps each sorted array at 1024 items or fewer (so below the 4096 from which the radix sort's size query
+    fails on a host without a device and the answer lacks the sort's scratch — csrc/sorted_segments.h:
+    sort_pairs_temp_bytes): up to 1024 items rocPRIM sorts in one block and answers a fixed 256 bytes before it asks
+    for the device, above that its answer is the device's tuning (4095 items: 256 bytes without a device, 48 KiB on
+    gfx950) — so the table replays identically with and without a device."""
+    import numpy as np
+
+    from jtsm_amd import _lib
+
+    lib = _lib.lib()
+    assert lib.jtsm_voc_eval_workspace_bytes(0, 0, 1) == 3840
+    assert lib.jtsm_voc_eval_workspace_bytes(1, 1, 1) == 3840
+    assert lib.jtsm_voc_eval_workspace_bytes(257, 70, 20) == 25088
+    radix_sorted = {"voc_eval": lambda D, G, C_: D, "coco_accumulate": lambda D, K: D,      # items of the radix sorts
+                    "batched_nms": lambda n, K, m: n, "batched_nms_rotated": lambda n, K, m: n,
+                    "fast_rcnn_inference": lambda R, K: R * K}
+    table = np.load(WORKSPACE_SIZE_TABLE)
+    assert sorted(k[:-5] for k in table.files if k.endswith("_args")) == sorted(WORKSPACE_SIZE_CASES)
+    for name, cases in WORKSPACE_SIZE_CASES.items():
+        assert table[name + "_args"].tolist() == [list(c) for c in cases], name
+        if name in radix_sorted:
+            assert max(radix_sorted[name](*c) for c in cases) <= 1024, name
+        got, want = workspace_size_answers(lib, name), table[name + "_bytes"].tolist()
+        assert got == want, "%s: %s" % (name, [(c, g, w) for c, g, w in zip(cases, got, want) if g != w])
+
+
 def test_integration_doc_maps_every_declared_symbol():
     """INTEGRATION.md's symbol <-> reference-interface table names every entry point include/jtsm_hip.h declares
     (brace lists and trailing-* families expanded)."""
