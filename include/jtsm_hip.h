@@ -1185,6 +1185,40 @@ int jtsm_coco_accumulate(const int64_t* records, int D, int K, int N, const int6
                          int R, const int32_t* max_dets, int M, double* precision, double* scores, double* recall,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Deformable convolution v1 / v2: the sampling kernels of detectron2/layers/csrc/deformable/deform_conv_cuda_kernel.cu
+ * (deformable_im2col / modulated_deformable_im2col, *_col2im_coord, *_col2im) around this library's own contraction.
+ * Semantics and the reasons for the gather form: DESIGN.md §4j.  All tensors float32 and channels-last:
+ *   x (N, H, W, C); offset (N, Ho, Wo, G * 2 * K) and mask (N, Ho, Wo, G * K) — logical (N, channels, Ho, Wo) with the
+ *   reference's channel meaning: inside deformable group g, channel 2 k is dy and 2 k + 1 is dx of tap k = i * kw + j;
+ *   mask == NULL: v1 (no modulation).  K = kh * kw, G = deformable_groups, C / G a multiple of 4; stride, pad and
+ *   dil are square; Ho = (H + 2 pad - dil (kh - 1) - 1) / stride + 1, Wo likewise.
+ *   cols / dcols (N * Ho * Wo, K, C): tap-major, channel-minor rows — a channels-last (O, C, kh, kw) weight viewed as
+ *   (O, K * C) contracts them with no repacking.
+ *
+ * jtsm_deform_columns_f32 — cols <- mask * bilinear(x, p), p = ((float)(oy stride - pad + i dil) + dy, ... + dx); a
+ *   sample counts only inside (-1, H) x (-1, W), a corner only inside the map; w1 v1 + w2 v2 + w3 v3 + w4 v4 summed
+ *   left to right, the mask multiplied last (bit-defined: the file is built without floating-point contraction).
+ * jtsm_deform_offset_mask_grad_f32 — d_offset (offset's layout) <- sum over the group's channels of dcols * mask *
+ *   coordinate weight; d_mask (mask's layout; NULL with mask == NULL) <- sum of dcols * bilinear(x).  A fixed-shape
+ *   reduction per (pixel, tap, group): no atomics, every element written.
+ * jtsm_deform_input_grad_f32 — dx (N, H, W, C) <- the transposed sampling of dcols, as a deterministic gather: one
+ *   64-bit key per (sample, corner) with the destination in the high bits, a stable radix sort, one workgroup per
+ *   destination walking its list in order.  EVERY element of dx is written (destinations nothing reaches get zero): the
+ *   caller does not clear it.  workspace: jtsm_deform_input_grad_workspace_bytes(...), 256-byte aligned.  4 N Ho Wo K G
+ *   and N H W G must stay below 2^31, else JTSM_EINVAL (the caller loops over groups of images).
+ * Nothing is allocated or synchronised.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int jtsm_deform_columns_f32(const float* x, const float* offset, const float* mask, float* cols, int N, int H, int W,
+                            int C, int G, int kh, int kw, int stride, int pad, int dil, void* stream);
+int jtsm_deform_offset_mask_grad_f32(const float* dcols, const float* x, const float* offset, const float* mask,
+                                     float* d_offset, float* d_mask, int N, int H, int W, int C, int G, int kh, int kw,
+                                     int stride, int pad, int dil, void* stream);
+size_t jtsm_deform_input_grad_workspace_bytes(int N, int H, int W, int G, int kh, int kw, int stride, int pad, int dil);
+int jtsm_deform_input_grad_f32(const float* dcols, const float* offset, const float* mask, float* dx, int N, int H,
+                               int W, int C, int G, int kh, int kw, int stride, int pad, int dil, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 /* Model input boundary: GeneralizedMCNNWSL.preprocess_image
  * (projects/WSL/wsl/modeling/meta_arch/mcnn.py:303-318) + ImageList.from_tensors
  * (detectron2/structures/image_list.py:71-125) in one launch: images[b] is the mapper's uint8 (C, h_b, w_b) planar

@@ -2,6 +2,7 @@
 ``detectron2.layers`` / ``wsl.layers`` (detectron2/layers/__init__.py:1-13,
 projects/WSL/wsl/layers/__init__.py:1-11) that lie on the path."""
 from .cmil import ROILabel, ROIMerge, roi_label, roi_merge
+from .deform_conv import DeformConv, ModulatedDeformConv, deform_conv, modulated_deform_conv
 from .mist import mine_top_p
 from .moi_pool import MOIPool, moi_pool
 from .nms import batched_nms, batched_nms_rotated, nms_rotated

@@ -84,6 +84,38 @@ class Conv2d(nn.Conv2d):
         return y
 
 
+def _zero_padded_rows(weight, bias, multiple):
+    extra = -weight.shape[0] % multiple
+    if extra == 0:
+        return weight, bias
+    return (torch.cat([weight, weight.new_zeros((extra,) + tuple(weight.shape[1:]))]),
+            torch.cat([bias, bias.new_zeros(extra)]))
+
+
+def conv2d_padded(conv, x, multiple=8):
+    """conv(x) for a plain biased `Conv2d` (no norm, no activation) whose output-channel count is no multiple of 8,
+    computed with the channels zero-padded up to one and sliced off again.  The weight gradient of a layer narrower
+    than that is not eligible for the plane kernels and falls to the fp32 kernel, which adds its K slices with atomics:
+    two runs then differ in the last bits.  The parameters keep their shapes; the padding's gradient is dropped."""
+    assert conv.norm is None and conv.activation is None and conv.bias is not None
+    o = conv.out_channels
+    if o % multiple == 0:
+        return conv(x)
+    w, b = _zero_padded_rows(conv.weight, conv.bias, multiple)
+    y = conv2d_fused(x, w.contiguous(memory_format=CL), None, b, None, conv.stride[0], conv.padding[0],
+                     conv.dilation[0], False, True, emit_planes=False)
+    return y[:, :o]
+
+
+def linear_padded(linear, x, multiple=8):
+    """The same for a biased `Linear`."""
+    o = linear.out_features
+    if o % multiple == 0:
+        return linear(x)
+    w, b = _zero_padded_rows(linear.weight, linear.bias, multiple)
+    return linear_fused(x, w, b, False, True)[:, :o]
+
+
 class Linear(nn.Linear):
     """nn.Linear on the MFMA GEMM; `relu=True` folds the following ReLU into the epilogue."""
 

@@ -1,5 +1,6 @@
 """ResNet bottom-up behind the reference's names — API surface of detectron2/modeling/backbone/resnet.py
-(:26-98 BasicBlock, :101-211 BottleneckBlock, :331-359 BasicStem, :362-479 ResNet, :562-648 build_resnet_backbone):
+(:26-98 BasicBlock, :101-211 BottleneckBlock, :214-328 DeformBottleneckBlock, :331-359 BasicStem, :362-479 ResNet,
+:562-648 build_resnet_backbone):
 same class names, constructor keywords, module names (stem.conv1, resN.K.convM / shortcut) and therefore the same
 state_dict keys; everything else is this repo's own construction.
 
@@ -15,10 +16,11 @@ from torch import nn
 from ...layers.grad_fan import fan_out
 from ...layers.batch_norm import FrozenBatchNorm2d, get_norm
 from ...layers.blocks import CNNBlockBase
+from ...layers.deform_conv import DeformConv, ModulatedDeformConv
 from ...layers.elementwise import max_pool_3x3_s2
 from ...layers import fused_blocks
 from ...layers.fused_blocks import bottleneck_fused
-from ...layers.wrappers import Conv2d
+from ...layers.wrappers import Conv2d, conv2d_padded
 from .backbone import Backbone
 from .build import BACKBONE_REGISTRY
 
@@ -94,6 +96,51 @@ class BottleneckBlock(CNNBlockBase):
                 self.conv2.padding[0], self.conv2.dilation[0], sc.stride[0] if sc is not None else 1)
         skip = x if self.shortcut is None else self.shortcut(x)
         return self.conv3(self.conv2(self.conv1(x)), residual=skip)   # relu(bn(conv3(.)) + skip)
+
+
+class DeformBottleneckBlock(CNNBlockBase):
+    """BottleneckBlock with a deformable 3x3 (resnet.py:214-328): `conv2_offset`, an ordinary zero-initialised 3x3
+    convolution with bias, predicts 18 (v1) or 27 (v2: offsets and mask logits) channels per deformable group from
+    conv1's output, and `conv2` samples by them.  Not a BottleneckBlock: the fused block nodes and the identity chains
+    (ResNet._run_stage, layers/fused_blocks.py) key on that type; this block runs layer by layer."""
+
+    def __init__(self, in_channels, out_channels, *, bottleneck_channels, stride=1, num_groups=1, norm="BN",
+                 stride_in_1x1=False, dilation=1, deform_modulated=False, deform_num_groups=1):
+        super().__init__(in_channels, out_channels, stride)
+        self.deform_modulated = deform_modulated
+        s1, s3 = (stride, 1) if stride_in_1x1 else (1, stride)
+        mid = bottleneck_channels
+        self.shortcut = None
+        if in_channels != out_channels:
+            self.shortcut = conv_norm(in_channels, out_channels, 1, norm, stride=stride)
+        self.conv1 = conv_norm(in_channels, mid, 1, norm, stride=s1, relu=True)
+        op, offset_channels = (ModulatedDeformConv, 27) if deform_modulated else (DeformConv, 18)
+        self.conv2_offset = Conv2d(mid, offset_channels * deform_num_groups, kernel_size=3, stride=s3,
+                                   padding=1 * dilation, dilation=dilation)
+        self.conv2 = op(mid, mid, kernel_size=3, stride=s3, padding=1 * dilation, bias=False, groups=num_groups,
+                        dilation=dilation, deformable_groups=deform_num_groups, norm=get_norm(norm, mid),
+                        activation=F.relu)
+        _msra(self.conv2)
+        self.conv3 = conv_norm(mid, out_channels, 1, norm, relu=True)           # ReLU after the shortcut add
+        nn.init.constant_(self.conv2_offset.weight, 0)
+        nn.init.constant_(self.conv2_offset.bias, 0)
+
+    def _offsets(self, x):
+        """conv2_offset(x) through conv2d_padded: its 18 G / 27 G output channels are no multiple of 8, and a deformable
+        stage must train to the same bits twice."""
+        return conv2d_padded(self.conv2_offset, x)
+
+    def forward(self, x):
+        out = self.conv1(x)
+        if self.deform_modulated:
+            offset_mask = self._offsets(out)
+            offset_x, offset_y, mask = torch.chunk(offset_mask, 3, dim=1)
+            offset = torch.cat((offset_x, offset_y), dim=1)
+            out = self.conv2(out, offset, mask.sigmoid())
+        else:
+            out = self.conv2(out, self._offsets(out))
+        skip = x if self.shortcut is None else self.shortcut(x)
+        return self.conv3(out, residual=skip)   # relu(bn(conv3(.)) + skip)
 
 
 class BasicStem(CNNBlockBase):
@@ -217,11 +264,10 @@ def resnet_cfg(cfg):
     r = cfg.MODEL.RESNETS
     if r.DEPTH not in BLOCKS_PER_STAGE:
         raise ValueError("MODEL.RESNETS.DEPTH must be one of %s, got %r" % (sorted(BLOCKS_PER_STAGE), r.DEPTH))
-    if any(r.DEFORM_ON_PER_STAGE):
-        raise NotImplementedError("deformable conv is outside the JTSM path (SURVEY 2.1)")
     assert r.RES5_DILATION in {1, 2}, "res5_dilation cannot be {}.".format(r.RES5_DILATION)
     if r.DEPTH in (18, 34):
         assert r.RES2_OUT_CHANNELS == 64, "Must set MODEL.RESNETS.RES2_OUT_CHANNELS = 64 for R18/R34"
+        assert not any(r.DEFORM_ON_PER_STAGE), "MODEL.RESNETS.DEFORM_ON_PER_STAGE unsupported for R18/R34"
         assert r.NUM_GROUPS == 1, "Must set MODEL.RESNETS.NUM_GROUPS = 1 for R18/R34"
     last = max(_STAGE_NUMBER[f] for f in r.OUT_FEATURES if f != "stem")
     return r, BLOCKS_PER_STAGE[r.DEPTH][:last - 1]
@@ -244,9 +290,13 @@ def build_resnet_backbone(cfg, input_shape):
         if basic:
             stage = ResNet.make_stage(BasicBlock, n, first_stride, in_channels=cin, out_channels=cout, norm=r.NORM)
         else:
-            stage = ResNet.make_stage(BottleneckBlock, n, first_stride, in_channels=cin, out_channels=cout,
+            block, deform = BottleneckBlock, {}
+            if r.DEFORM_ON_PER_STAGE[number - 2]:
+                block = DeformBottleneckBlock
+                deform = {"deform_modulated": r.DEFORM_MODULATED, "deform_num_groups": r.DEFORM_NUM_GROUPS}
+            stage = ResNet.make_stage(block, n, first_stride, in_channels=cin, out_channels=cout,
                                       norm=r.NORM, bottleneck_channels=mid, stride_in_1x1=r.STRIDE_IN_1X1,
-                                      dilation=2 if dilated else 1, num_groups=r.NUM_GROUPS)
+                                      dilation=2 if dilated else 1, num_groups=r.NUM_GROUPS, **deform)
         stages.append(stage)
         cin, cout, mid = cout, cout * 2, mid * 2
     return ResNet(stem, stages, out_features=r.OUT_FEATURES).freeze(cfg.MODEL.BACKBONE.FREEZE_AT)

@@ -107,6 +107,8 @@ def _build_wsl(cfg, input_shape, pooled_stages, pool_output):
     with stride 2 unless RES5_DILATION is 2, in which case res4 and res5 dilate their 3x3s instead and that pool runs
     at stride 1 (the DC5 configs: stride-8 output).  No convolution of these networks is strided."""
     r, counts = resnet_cfg(cfg)
+    if any(r.DEFORM_ON_PER_STAGE):
+        raise NotImplementedError("deformable conv is outside the JTSM path (SURVEY 2.1)")
     basic = r.DEPTH in (18, 34)
     stem = ThreeConvStem(in_channels=input_shape.channels, out_channels=r.STEM_OUT_CHANNELS, norm=r.NORM)
     cin, cout, mid = r.STEM_OUT_CHANNELS, r.RES2_OUT_CHANNELS, r.NUM_GROUPS * r.WIDTH_PER_GROUP

@@ -9,7 +9,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ...layers.shape_spec import ShapeSpec
-from ...layers.wrappers import Conv2d, cat
+from ...layers.wrappers import Conv2d, cat, conv2d_padded
 from ...structures import Boxes, ImageList, Instances, pairwise_iou
 from ...utils.registry import Registry
 from ..anchor_generator import build_anchor_generator
@@ -53,8 +53,10 @@ class StandardRPNHead(nn.Module):
         logits, deltas = [], []
         for x in features:
             t = self.conv(x)
-            logits.append(self.objectness_logits(t))
-            deltas.append(self.anchor_deltas(t))
+            # (A and A * box_dim output channels are rarely multiples of 8: padded, so that the head's weight gradients
+            # repeat bit for bit — layers/wrappers.py: conv2d_padded)
+            logits.append(conv2d_padded(self.objectness_logits, t))
+            deltas.append(conv2d_padded(self.anchor_deltas, t))
         return logits, deltas
 
 

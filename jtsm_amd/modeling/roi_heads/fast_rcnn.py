@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ...layers.wrappers import Linear, cat
+from ...layers.wrappers import Linear, cat, linear_padded
 from ...structures import Instances
 from ..box_regression import Box2BoxTransform
 from .fast_rcnn_oicr import fast_rcnn_inference
@@ -40,7 +40,8 @@ class FastRCNNOutputLayers(nn.Module):
     def forward(self, x):
         if x.dim() > 2:
             x = x.reshape(x.shape[0], -1)
-        return self.cls_score(x), self.bbox_pred(x)
+        # (num_classes + 1 is rarely a multiple of 8: padded, so that the weight gradient repeats bit for bit — layers/wrappers.py)
+        return linear_padded(self.cls_score, x), linear_padded(self.bbox_pred, x)
 
     def losses(self, predictions, proposals: List[Instances]):
         scores, deltas = predictions
