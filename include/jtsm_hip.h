@@ -317,7 +317,7 @@ int jtsm_conv2d_backward_weight_f32(const float* dy, const float* x, float* dw,
  *                                   elements behind it; `planes` holds 2*rows*k elements.  One K stage of a contraction
  *                                   (32 k of both planes) is then ONE whole 128-byte line per row instead of half a line
  *                                   of each of two arrays.  The WEIGHT operand (w_hi, w_lo / wt_hi, wt_lo) of every
- *                                   bf16x3 forward / backward-data entry point may be given in this layout: it is
+ *                                   forward / backward-data plane entry point may be given in this layout (bf16x3): it is
  *                                   recognised by w_lo == w_hi + 32 elements (separate planes are at least a whole plane
  *                                   apart; keep them more than 32 elements apart).  jtsm_split_bf16_transposed_f32 and the
  *                                   records of jtsm_split_bf16_multi_f32 write paired planes when given such a pair
@@ -342,54 +342,102 @@ int jtsm_conv_bf16x3_eligible(const jtsm_conv_shape* s, int role);
  * 3x3 kernel igemm_x3_halo_kernel<role,TH,WM,WN,TN,HP16> (TH = 8 * WM / 2 patch rows, HP16 = 12 or 21). */
 int jtsm_conv_bf16x3_plan(const jtsm_conv_shape* s, int role, int* wm, int* wn, int* tm, int* tn, int* nbuf,
                           int* splits);
-/* y_hi / y_lo (both or neither; needs out_c % 4 == 0): the planes of the finished output y, written by the
- * epilogue for a following bf16x3 contraction — saves that layer's jtsm_split_bf16_f32 pass. */
-int jtsm_conv2d_forward_bf16x3(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t* w_hi,
-                               const uint16_t* w_lo, float* y, uint16_t* y_hi, uint16_t* y_lo,
-                               const jtsm_conv_shape* s, const float* scale, const float* bias,
-                               const float* residual, int relu, void* workspace, size_t workspace_bytes,
-                               void* stream);
-/* dx_hi / dx_lo (both or neither): planes of the finished dx (after accumulate / relu_mask) — with relu_mask =
- * the previous layer's ReLU output this IS that layer's gated gradient, ready for its own two contractions. */
-int jtsm_conv2d_backward_data_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* wt_hi,
-                                     const uint16_t* wt_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
-                                     const jtsm_conv_shape* s, const float* accumulate,
-                                     const float* relu_mask, void* workspace, size_t workspace_bytes,
-                                     void* stream);
-/* role 2 (backward-weight) is eligible when in_c and out_c are multiples of 8; dy / x planes as above.
- * Unlike the fp32 kernel this one is DETERMINISTIC: each pixel slice writes a partial tile into the
- * workspace (jtsm_conv_bf16x3_wgrad_workspace_bytes, 16-byte aligned) and a fixed-order pass adds them;
- * zero_dw == 0 adds the result to what dw holds. */
-size_t jtsm_conv_bf16x3_wgrad_workspace_bytes(const jtsm_conv_shape* s);
-int jtsm_conv2d_backward_weight_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* x_hi,
-                                       const uint16_t* x_lo, float* dw, const jtsm_conv_shape* s,
-                                       const float* row_scale, int zero_dw, void* workspace,
-                                       size_t workspace_bytes, void* stream);
 
 /* fp16 contractions (BASELINE.json configs[4]: "fp16 MFMA path" — fp16 operands, fp32 accumulate, fp32 results and
  * losses; the reference reaches fp16 through torch autocast, detectron2/engine/train_loop.py AMPTrainer).  Same
- * shapes, epilogue, workspace, eligibility and split-K rules as the bf16x3 entry points, but every operand is ONE
+ * shapes, epilogue, workspace, eligibility and split-K rules as bf16x3, but every operand is ONE
  * plane of IEEE binary16 bit patterns (uint16_t, 16-byte aligned) and a product is one v_mfma_f32_32x32x16_f16.
  *   jtsm_split_f16_f32              h[i] <- fp16(src[i] * 2^shift), same layout
  *   jtsm_split_f16_transposed_f32   as jtsm_split_bf16_transposed_f32, one plane
  *   jtsm_split_bf16_multi_f32       with a record's `lo` word 0 writes that record's fp16 plane into `hi`
- * Gradient planes carry a power-of-two factor 2^grad_shift (exact; keeps small gradients out of fp16's subnormal
- * range — the per-contraction equivalent of loss scaling): the caller splits dy with shift = grad_shift, the kernels
- * multiply the accumulator by 2^-grad_shift before the epilogue (dx, dw come out unscaled, fp32) and write the dx
- * plane (dx_h, nullable) with the factor applied again.  y_h (nullable) is the plain fp16 plane of y. */
+ * Activation and weight planes are plain fp16; gradient planes carry a power-of-two factor (grad_shift below). */
 int jtsm_split_f16_f32(const float* src, uint16_t* h, long n, int shift, void* stream);
 int jtsm_split_f16_transposed_f32(const float* w, const float* row_scale, uint16_t* h, int out_c, int taps, int in_c,
                                   void* stream);
-int jtsm_conv2d_forward_f16(const uint16_t* x_h, const uint16_t* w_h, float* y, uint16_t* y_h,
-                            const jtsm_conv_shape* s, const float* scale, const float* bias,
-                            const float* residual, int relu, void* workspace, size_t workspace_bytes,
-                            void* stream);
-int jtsm_conv2d_backward_data_f16(const uint16_t* dy_h, const uint16_t* wt_h, float* dx, uint16_t* dx_h,
-                                  const jtsm_conv_shape* s, const float* accumulate, const float* relu_mask,
-                                  int grad_shift, void* workspace, size_t workspace_bytes, void* stream);
-int jtsm_conv2d_backward_weight_f16(const uint16_t* dy_h, const uint16_t* x_h, float* dw, const jtsm_conv_shape* s,
-                                    const float* row_scale, int zero_dw, int grad_shift, void* workspace,
-                                    size_t workspace_bytes, void* stream);
+
+/* ---- The plane entry points: ONE function per contraction role, for both plane arithmetics.
+ * They compute what the _f32 entry points above compute (same shapes, epilogue, workspace and split-K rules;
+ * eligibility: jtsm_conv_bf16x3_eligible) from operand planes.  The ARITHMETIC is told by the two input lo planes:
+ * both given = bf16x3 (hi + lo per operand); both null = fp16, the *_hi arguments being the single fp16 planes.  One
+ * given and one not is refused, and so is an option used against its line below ("fp16 only", "not together with",
+ * "need"): JTSM_EINVAL with a jtsm_last_error text, nothing launched.  Every option is a nullable argument; null (0 for
+ * grad_shift) = not wanted.
+ *   output planes  y_hi, y_lo / dx_hi, dx_lo: planes of the FINISHED result (after the whole epilogue), written for a
+ *                  following contraction — saves that layer's split pass; with a gate the dx planes ARE the layer
+ *                  below's gated gradient, ready for its own two contractions.  bf16x3: both or neither.  fp16: the one
+ *                  plane goes in *_hi and *_lo must be null; y's plane is plain, dx's carries 2^grad_shift again.  Need
+ *                  the result's channel count % 4 == 0 and 16-byte aligned tensors; the strided 1x1 scatter form of the
+ *                  data gradient produces none.
+ *   fp32 result    y / dx may be NULL when its planes are requested: the fp32 copy is then never written (a chain that
+ *                  keeps its activations as planes only: the mask heads' tower, layers/fused_blocks.py).
+ *   gate_plane     the ReLU gate of relu_mask read from the gated activation's hi (bf16) or only (fp16) plane instead of
+ *                  its fp32 copy (16-byte aligned, same layout as the result): the result is kept where the 16-bit pattern
+ *                  is a positive number — the same gate (both formats round a positive fp32 to a positive value) at half
+ *                  the bytes.
+ *   row_scale      backward-data: one factor per result ROW (pixel or roi), applied first — the data gradient of a layer
+ *                  whose input rows were rescaled, e.g. the per-roi factor in front of the box head
+ *                  (projects/WSL/wsl/modeling/roi_heads/roi_heads_jtsm.py:607-633); needs in_c % 4 == 0.
+ *                  backward-weight: one factor per out_c, as in jtsm_conv2d_backward_weight_f32.
+ *   residual_h /   fp16 only (the reference's AMP step keeps activations and their gradients in fp16,
+ *   accumulate_h   detectron2/engine/train_loop.py:289-336): the residual / the accumulate term read from an fp16 plane
+ *                  — a block input that has no fp32 copy: y = relu?(conv * scale + bias + half(residual_h)); the shortcut
+ *                  path's gradient, carrying 2^grad_shift: dx = conv^T(dy) + accumulate_h * 2^-grad_shift, then row
+ *                  scale / gate_plane.  Not together with the fp32 twin (residual / accumulate); accumulate_h not with
+ *                  relu_mask or colsum either.  Need out_c (in_c) % 4 == 0; not the strided 1x1 scatter.
+ *   colsum         backward-data (also the transposed convolution's): ALSO leave the column sums of the finished, gated
+ *                  result: rows x in_c floats, rows = jtsm_conv_bf16x3_colsum_rows(s, role) (role 0 for the transposed
+ *                  convolution's conv shape, 1 for a data gradient; 0 rows: not available for this shape), one partial
+ *                  sum per row tile of the launch, which the caller adds up in order (jtsm_colsum_fold_f32) — the bias
+ *                  gradient of the layer below (ATen convolution_backward's grad_bias, detectron2/layers/wrappers.py:
+ *                  76-78), taken where that layer's output gradient is written instead of by a pass over it (sums of the
+ *                  fp32 values: no plane shift in them).  16-byte aligned.
+ *   db             backward-weight: ALSO the bias gradient db[out_c] = sum over output pixels of dy (ATen
+ *                  convolution_backward's third result / nn.Linear's bias gradient) in the same contraction: the
+ *                  workgroups of the first column tile run one extra matrix instruction per dy fragment against an
+ *                  all-ones fragment, so dy is not read a second time.  db comes from the same planes as dW.  Workspace:
+ *                  jtsm_conv_bf16x3_wgrad_bias_workspace_bytes (the slabs of jtsm_conv_bf16x3_wgrad_workspace_bytes + the
+ *                  bias partials).
+ *   grad_shift     fp16 only (0 under bf16x3), 0..24: GRADIENT planes (dy, g, accumulate_h and the dx plane written) carry
+ *                  the power-of-two factor 2^grad_shift (exact; keeps small gradients out of fp16's subnormal range — the
+ *                  per-contraction equivalent of loss scaling): the caller splits dy with shift = grad_shift, the kernels
+ *                  multiply the accumulator by 2^-grad_shift before the epilogue, so dx, dw and db come out unscaled, fp32.
+ * backward-weight is eligible (role 2) when in_c and out_c are multiples of 8.  Unlike the fp32 kernel it is
+ * DETERMINISTIC: each pixel slice writes a partial tile into the workspace (jtsm_conv_bf16x3_wgrad_workspace_bytes,
+ * 16-byte aligned) and a fixed-order pass adds them; zero_dw == 0 adds the result to what dw holds. */
+int jtsm_conv2d_forward_planes(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t* w_hi,
+                               const uint16_t* w_lo, float* y, uint16_t* y_hi, uint16_t* y_lo,
+                               const jtsm_conv_shape* s, const float* scale, const float* bias,
+                               const float* residual, const uint16_t* residual_h, int relu, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int jtsm_conv2d_backward_data_planes(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* wt_hi,
+                                     const uint16_t* wt_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
+                                     const jtsm_conv_shape* s, const float* row_scale, const float* accumulate,
+                                     const uint16_t* accumulate_h, const float* relu_mask, const uint16_t* gate_plane,
+                                     int grad_shift, float* colsum, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+int jtsm_conv_bf16x3_colsum_rows(const jtsm_conv_shape* s, int role);
+size_t jtsm_conv_bf16x3_wgrad_workspace_bytes(const jtsm_conv_shape* s);
+size_t jtsm_conv_bf16x3_wgrad_bias_workspace_bytes(const jtsm_conv_shape* s);
+int jtsm_conv2d_backward_weight_planes(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* x_hi,
+                                       const uint16_t* x_lo, float* dw, float* db, const jtsm_conv_shape* s,
+                                       const float* row_scale, int zero_dw, int grad_shift, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+/* Up to 8 weight gradients of ONE shape in a single launch (+ one finishing launch): member i is
+ * dw[i] = row_scale[i][out] * sum_pixels dy_i (x) x_i (fresh results; row_scale may be NULL, or hold NULL members).
+ * dy_hi .. x_lo are HOST arrays of n device pointers; the arithmetic is told by the two lo ARRAYS (both null: fp16).
+ * For the layers a network repeats (the bottleneck blocks of a ResNet stage: same ATen convolution_backward, weight
+ * output only, as jtsm_conv2d_backward_weight_planes): the K (pixel) axis of the whole group is cut into as many slices
+ * as ONE launch needs to fill the chip — a sixth of the slabs six separate launches write and fold.  Deterministic (slabs
+ * folded in slice order); results are bit-identical for a given (shape, n), not to the single-layer entry (different
+ * slicing).  Workspace: jtsm_conv_bf16x3_wgrad_group_workspace_bytes(s, n); jtsm_conv_bf16x3_wgrad_group_plan reports
+ * the kernel (tile: 0 = the 3x3 LDS-halo kernel, 128, 256) and the slice count. */
+size_t jtsm_conv_bf16x3_wgrad_group_workspace_bytes(const jtsm_conv_shape* s, int n);
+int jtsm_conv_bf16x3_wgrad_group_plan(const jtsm_conv_shape* s, int n, int* tile, int* splits);
+int jtsm_conv2d_backward_weight_group_planes(int n, const uint16_t* const* dy_hi, const uint16_t* const* dy_lo,
+                                             const uint16_t* const* x_hi, const uint16_t* const* x_lo,
+                                             float* const* dw, const float* const* row_scale,
+                                             const jtsm_conv_shape* s, int grad_shift, void* workspace,
+                                             size_t workspace_bytes, void* stream);
 /* ---- ConvTranspose2d(kernel 2, stride 2, padding 0, bias) — the mask heads' upsampler
  * (detectron2/modeling/roi_heads/mask_head.py:245-252 `deconv`; projects/WSL/wsl/modeling/roi_heads/mask_head.py:303-305;
  * ATen conv_transpose2d behind detectron2/layers/wrappers.py `ConvTranspose2d = torch.nn.ConvTranspose2d`).
@@ -397,95 +445,24 @@ int jtsm_conv2d_backward_weight_f16(const uint16_t* dy_h, const uint16_t* x_h, f
  * in channels_last memory order [in_c][dy][dx][out_c].  in_c % 32 == 0, out_c % 32 == 0.
  *   forward        y[b,2i+dy,2j+dx,o] = relu?(bias[o] + sum_c x[b,i,j,c] W[c][dy][dx][o]) — one GEMM whose epilogue
  *                  writes straight to the four output pixels.  wt_* = planes of W^T as
- *                  jtsm_split_bf16_transposed_f32(W, null, .., out_c = in_c, taps = 1, in_c = 4*out_c) makes them;
- *                  y_hi / y_lo (nullable pair): planes of y for the next contraction.
+ *                  jtsm_split_bf16_transposed_f32(W, null, .., out_c = in_c, taps = 1, in_c = 4*out_c) makes them.
  *   backward_data  dx[b,i,j,c] = sum_{dy,dx,o} g[b,2i+dy,2j+dx,o] W[c][dy][dx][o], kept where relu_mask > 0 (nullable:
  *                  the ReLU output x came from) — the forward role of the 2x2/stride-2 convolution whose OHWI weight is
- *                  the same memory: w_* = plain planes of W (jtsm_split_bf16_f32); dx_hi / dx_lo nullable pair;
- *                  gate_plane: the gate as a plane (see "planes only" below), nullable;
+ *                  the same memory: w_* = plain planes of W (jtsm_split_bf16_f32);
  *                  workspace: jtsm_conv_transpose2x2_workspace_bytes (may be null: no K split).
- *   backward_weight: jtsm_conv2d_backward_weight_bf16x3 with shape {batch, 2h, 2w, in_c = out_c, out_c = in_c, 2, 2,
+ *   backward_weight: jtsm_conv2d_backward_weight_planes with shape {batch, 2h, 2w, in_c = out_c, out_c = in_c, 2, 2,
  *                  stride 2, pad 0}, dy planes = x's, x planes = g's: dW comes out in the parameter's memory order.
- * The _f16 forms take one fp16 plane per operand; g's plane carries 2^grad_shift as in jtsm_conv2d_backward_data_f16. */
-int jtsm_conv_transpose2x2_forward_bf16x3(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t* wt_hi,
+ * Arithmetic, output planes (y_hi, y_lo / dx_hi, dx_lo), null fp32 result, gate_plane, colsum and grad_shift (g's
+ * planes carry it) as described for the plane entry points above. */
+int jtsm_conv_transpose2x2_forward_planes(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t* wt_hi,
                                           const uint16_t* wt_lo, float* y, uint16_t* y_hi, uint16_t* y_lo, int batch,
                                           int h, int w, int in_c, int out_c, const float* bias, int relu, void* stream);
-int jtsm_conv_transpose2x2_forward_f16(const uint16_t* x_h, const uint16_t* wt_h, float* y, uint16_t* y_h, int batch,
-                                       int h, int w, int in_c, int out_c, const float* bias, int relu, void* stream);
 size_t jtsm_conv_transpose2x2_workspace_bytes(int batch, int h, int w, int in_c, int out_c);
-int jtsm_conv_transpose2x2_backward_data_bf16x3(const uint16_t* g_hi, const uint16_t* g_lo, const uint16_t* w_hi,
+int jtsm_conv_transpose2x2_backward_data_planes(const uint16_t* g_hi, const uint16_t* g_lo, const uint16_t* w_hi,
                                                 const uint16_t* w_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
                                                 int batch, int h, int w, int in_c, int out_c, const float* relu_mask,
-                                                const uint16_t* gate_plane, void* workspace, size_t workspace_bytes,
-                                                void* stream);
-int jtsm_conv_transpose2x2_backward_data_f16(const uint16_t* g_h, const uint16_t* w_h, float* dx, uint16_t* dx_h,
-                                             int batch, int h, int w, int in_c, int out_c, const float* relu_mask,
-                                             const uint16_t* gate_plane, int grad_shift, void* workspace,
-                                             size_t workspace_bytes, void* stream);
-/* ---- Chains that keep their activations as PLANES only (the mask heads' tower, layers/fused_blocks.py).
- * In every plane-arithmetic entry point the fp32 result pointer (y / dx) may be NULL when its planes (y_hi.. / dx_hi..)
- * are requested: the fp32 copy is then never written.  A ReLU gate can be read from the gated activation's hi (bf16)
- * or only (fp16) plane instead of its fp32 copy: `gate_plane` (nullable, 16-byte aligned, same layout as the result)
- * keeps the result where the 16-bit pattern is a positive number — the same gate (both formats round a positive fp32
- * to a positive value) at half the bytes.  jtsm_conv2d_backward_data_ex_* = jtsm_conv2d_backward_data_* with every
- * epilogue option: row_scale (nullable, one factor per result row — pixel or roi — applied first: the data gradient
- * of a layer whose input rows were rescaled, e.g. the per-roi factor in front of the box head,
- * projects/WSL/wsl/modeling/roi_heads/roi_heads_jtsm.py:607-633), accumulate, relu_mask (fp32 gate) and gate_plane;
- * jtsm_channel_sum_planes = the bias gradient (jtsm_channel_sum_ws_f32) of a gradient held as
- * planes: out[c] = sum_r (hi + lo)[r][c] (lo null: the fp16 plane times 2^-shift); C % 8 == 0; workspace of
- * 1024 * C floats. */
-int jtsm_conv2d_backward_data_ex_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* wt_hi,
-                                        const uint16_t* wt_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
-                                        const jtsm_conv_shape* s, const float* row_scale, const float* accumulate,
-                                        const float* relu_mask, const uint16_t* gate_plane, void* workspace,
-                                        size_t workspace_bytes, void* stream);
-int jtsm_conv2d_backward_data_ex_f16(const uint16_t* dy_h, const uint16_t* wt_h, float* dx, uint16_t* dx_h,
-                                     const jtsm_conv_shape* s, const float* row_scale, const float* accumulate,
-                                     const float* relu_mask, const uint16_t* gate_plane, int grad_shift, void* workspace,
-                                     size_t workspace_bytes, void* stream);
-
-/* fp16-ONLY activations (BASELINE configs[4]; the reference's AMP step keeps activations and their gradients in fp16,
- * detectron2/engine/train_loop.py:289-336): a chain of layers whose activations exist as their fp16 operand plane alone.
- *   forward_res16:        jtsm_conv2d_forward_f16 with the RESIDUAL read from an fp16 plane (a block input that has no
- *                         fp32 copy): y = relu?(conv * scale + bias + half(residual_h)); y may be NULL (plane only).
- *   backward_data_acc16:  jtsm_conv2d_backward_data_ex_f16 with the ACCUMULATE term read from an fp16 gradient plane
- *                         carrying 2^grad_shift (the shortcut path's gradient): dx = conv^T(dy) + accumulate_h * 2^-shift,
- *                         then row scale / gate as in the _ex form; dx may be NULL (plane only).
- * Both need out_c (in_c) % 4 == 0 and 16-byte aligned planes; not the strided 1x1 scatter. */
-int jtsm_conv2d_forward_res16_f16(const uint16_t* x_h, const uint16_t* w_h, float* y, uint16_t* y_h,
-                                  const jtsm_conv_shape* s, const float* scale, const float* bias,
-                                  const uint16_t* residual_h, int relu, void* workspace, size_t workspace_bytes,
-                                  void* stream);
-int jtsm_conv2d_backward_data_acc16_f16(const uint16_t* dy_h, const uint16_t* wt_h, float* dx, uint16_t* dx_h,
-                                        const jtsm_conv_shape* s, const float* row_scale, const uint16_t* accumulate_h,
-                                        const uint16_t* gate_plane, int grad_shift, void* workspace,
-                                        size_t workspace_bytes, void* stream);
-
-/* The same data gradients (and the transposed convolution's), also leaving the COLUMN SUMS of the finished, gated
- * result: colsum (rows x in_c floats, rows = jtsm_conv_bf16x3_colsum_rows(s, role); role 0 for the transposed
- * convolution's conv shape, 1 for a data gradient; 0 rows: not available for this shape) holds one partial sum per row
- * tile of the launch, which the caller adds up in order (jtsm_colsum_fold_f32) — the bias gradient of the layer below
- * (ATen convolution_backward's grad_bias, detectron2/layers/wrappers.py:76-78), taken where that layer's output
- * gradient is written instead of by a pass over it (sums of the fp32 values: no plane shift in them). */
-int jtsm_conv_bf16x3_colsum_rows(const jtsm_conv_shape* s, int role);
-int jtsm_conv2d_backward_data_colsum_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* wt_hi,
-                                            const uint16_t* wt_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
-                                            const jtsm_conv_shape* s, const float* row_scale, const float* accumulate,
-                                            const float* relu_mask, const uint16_t* gate_plane, float* colsum,
-                                            void* workspace, size_t workspace_bytes, void* stream);
-int jtsm_conv2d_backward_data_colsum_f16(const uint16_t* dy_h, const uint16_t* wt_h, float* dx, uint16_t* dx_h,
-                                         const jtsm_conv_shape* s, const float* row_scale, const float* accumulate,
-                                         const float* relu_mask, const uint16_t* gate_plane, int grad_shift, float* colsum,
-                                         void* workspace, size_t workspace_bytes, void* stream);
-int jtsm_conv_transpose2x2_backward_data_colsum_bf16x3(const uint16_t* g_hi, const uint16_t* g_lo, const uint16_t* w_hi,
-                                                       const uint16_t* w_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
-                                                       int batch, int h, int w, int in_c, int out_c,
-                                                       const float* relu_mask, const uint16_t* gate_plane, float* colsum,
-                                                       void* workspace, size_t workspace_bytes, void* stream);
-int jtsm_conv_transpose2x2_backward_data_colsum_f16(const uint16_t* g_h, const uint16_t* w_h, float* dx, uint16_t* dx_h,
-                                                    int batch, int h, int w, int in_c, int out_c, const float* relu_mask,
-                                                    const uint16_t* gate_plane, int grad_shift, float* colsum,
-                                                    void* workspace, size_t workspace_bytes, void* stream);
+                                                const uint16_t* gate_plane, int grad_shift, float* colsum,
+                                                void* workspace, size_t workspace_bytes, void* stream);
 /* Streaming passes that end in operand planes (hi + lo bf16, or lo == NULL: one fp16 plane of v * 2^shift; all
  * pointers 16-byte aligned, element counts multiples of 8):
  *   jtsm_relu_backward_split_scaled_f32  g = y > 0 ? dy * scale : 0 (+ planes of g): the backward of ReLU followed by
@@ -495,7 +472,10 @@ int jtsm_conv_transpose2x2_backward_data_colsum_f16(const uint16_t* g_h, const u
  *   jtsm_split_rowscale_f32              planes of src[r][c] * row_scale[r] (nothing else is written): the per-roi
  *       rescale in front of the box head (roi_heads_jtsm.py:607-633) folded into the plane split;
  *   jtsm_dropout_split_f32               y = keep(i) ? x / (1 - p) : 0 (y may alias x) + planes of y (y_hi nullable);
- *       keep(i) is a counter-based hash of (seed, i), so no mask is stored. */
+ *       keep(i) is a counter-based hash of (seed, i), so no mask is stored;
+ *   jtsm_channel_sum_planes              the bias gradient (jtsm_channel_sum_ws_f32) of a gradient held as planes:
+ *       out[c] = sum_r (hi + lo)[r][c] (lo null: the fp16 plane times 2^-shift); C % 8 == 0; workspace of 1024 * C
+ *       floats. */
 int jtsm_relu_backward_split_scaled_f32(const float* dy, const float* y, float scale, float* g, uint16_t* g_hi,
                                         uint16_t* g_lo, long n, int shift, void* stream);
 int jtsm_split_rowscale_f32(const float* src, const float* row_scale, long rows, int cols, uint16_t* hi, uint16_t* lo,
@@ -509,37 +489,6 @@ int jtsm_channel_sum_planes(const uint16_t* hi, const uint16_t* lo, float* out, 
 int jtsm_channel_sum_planes_multi(const uint16_t* const* hi, const uint16_t* const* lo, float* const* outs,
                                   const long* rows, int count, int C, int shift, void* workspace,
                                   size_t workspace_bytes, void* stream);
-/* The weight gradient AND the bias gradient db[out_c] = sum over output pixels of dy (ATen convolution_backward's
- * third result / nn.Linear's bias gradient) in one contraction: the workgroups of the first column tile run one extra
- * matrix instruction per dy fragment against an all-ones fragment, so dy is not read a second time.  db comes from the
- * same planes as dW (hi + lo, or the fp16 plane times 2^-grad_shift).  Workspace:
- * jtsm_conv_bf16x3_wgrad_bias_workspace_bytes (the slabs of jtsm_conv_bf16x3_wgrad_workspace_bytes + the bias partials). */
-size_t jtsm_conv_bf16x3_wgrad_bias_workspace_bytes(const jtsm_conv_shape* s);
-int jtsm_conv2d_backward_weight_bias_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* x_hi,
-                                            const uint16_t* x_lo, float* dw, float* db, const jtsm_conv_shape* s,
-                                            const float* row_scale, int zero_dw, void* workspace,
-                                            size_t workspace_bytes, void* stream);
-int jtsm_conv2d_backward_weight_bias_f16(const uint16_t* dy_h, const uint16_t* x_h, float* dw, float* db,
-                                         const jtsm_conv_shape* s, const float* row_scale, int zero_dw, int grad_shift,
-                                         void* workspace, size_t workspace_bytes, void* stream);
-/* Up to 8 weight gradients of ONE shape in a single launch (+ one finishing launch): member i is
- * dw[i] = row_scale[i][out] * sum_pixels dy_i (x) x_i (fresh results; row_scale may be NULL, or hold NULL members).
- * For the layers a network repeats (the bottleneck blocks of a ResNet stage: same ATen convolution_backward, weight
- * output only, as jtsm_conv2d_backward_weight_bf16x3): the K (pixel) axis of the whole group is cut into as many slices
- * as ONE launch needs to fill the chip — a sixth of the slabs six separate launches write and fold.  Deterministic (slabs
- * folded in slice order); results are bit-identical for a given (shape, n), not to the single-layer entry (different
- * slicing).  Workspace: jtsm_conv_bf16x3_wgrad_group_workspace_bytes(s, n); jtsm_conv_bf16x3_wgrad_group_plan reports
- * the kernel (tile: 0 = the 3x3 LDS-halo kernel, 128, 256) and the slice count. */
-size_t jtsm_conv_bf16x3_wgrad_group_workspace_bytes(const jtsm_conv_shape* s, int n);
-int jtsm_conv_bf16x3_wgrad_group_plan(const jtsm_conv_shape* s, int n, int* tile, int* splits);
-int jtsm_conv2d_backward_weight_group_bf16x3(int n, const uint16_t* const* dy_hi, const uint16_t* const* dy_lo,
-                                             const uint16_t* const* x_hi, const uint16_t* const* x_lo,
-                                             float* const* dw, const float* const* row_scale,
-                                             const jtsm_conv_shape* s, void* workspace, size_t workspace_bytes,
-                                             void* stream);
-int jtsm_conv2d_backward_weight_group_f16(int n, const uint16_t* const* dy_h, const uint16_t* const* x_h,
-                                          float* const* dw, const float* const* row_scale, const jtsm_conv_shape* s,
-                                          int grad_shift, void* workspace, size_t workspace_bytes, void* stream);
 /* g = dy where y > 0 else 0 (fp32), and g's fp16 plane times 2^shift (n % 8 == 0) in the same pass. */
 int jtsm_relu_backward_split_f16(const float* dy, const float* y, float* g, uint16_t* g_h, long n, int shift,
                                  void* stream);
@@ -556,7 +505,7 @@ int jtsm_relu_backward_f32(const float* dy, const float* y, float* g, long n, vo
 /* out[c] = sum_r g[r*C + c]  — bias gradient of a conv / linear layer. */
 int jtsm_channel_sum_f32(const float* g, float* out, long rows, int C, void* stream);
 /* The same for n <= 16 small (rows[b] x width) matrices in one launch, rows added in order: out (n, width) — folds the
- * per-row-tile column sums of jtsm_conv2d_backward_data_colsum_* of several layers at once. */
+ * per-row-tile column sums (`colsum` of the plane entry points' data gradients) of several layers at once. */
 int jtsm_colsum_fold_f32(const float* const* parts, const int* rows, int n, int width, float* out, void* stream);
 /* The same without atomics (bitwise reproducible) and ~4x faster on large inputs: row slabs are summed into
  * `workspace` (jtsm_channel_sum_workspace_bytes, 16-byte aligned) and folded in slab order, for any C and any

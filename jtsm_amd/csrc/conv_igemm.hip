@@ -1763,7 +1763,7 @@ static int x3_forward(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t
                       const uint16_t* w_lo, float* y, uint16_t* y_hi, uint16_t* y_lo,
                       const jtsm_conv_shape* s, const float* scale, const float* bias,
                       const float* residual, int relu, void* workspace, size_t workspace_bytes,
-                      void* stream, const FwdExtras& ex = FwdExtras()) {
+                      void* stream, const FwdExtras& ex) {
   Params p = {};
   int rc = map_gemm(s, FWD, false, p);
   if (rc) return rc;
@@ -1808,8 +1808,8 @@ static int x3_backward_data(const uint16_t* dy_hi, const uint16_t* dy_lo, const 
                             const uint16_t* wt_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
                             const jtsm_conv_shape* s, const float* accumulate, const float* relu_mask, int grad_shift,
                             void* workspace, size_t workspace_bytes, void* stream,
-                            const uint16_t* gate_plane = nullptr, const float* row_scale = nullptr,
-                            float* colsum = nullptr, const uint16_t* accumulate_h = nullptr) {
+                            const uint16_t* gate_plane, const float* row_scale, float* colsum,
+                            const uint16_t* accumulate_h) {
   Params p = {};
   int rc = map_gemm(s, DGRAD, false, p);
   if (rc) return rc;
@@ -1972,7 +1972,7 @@ template <int NP>
 static int x3_backward_weight(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* x_hi,
                               const uint16_t* x_lo, float* dw, const jtsm_conv_shape* s,
                               const float* row_scale, int zero_dw, int grad_shift, void* workspace,
-                              size_t workspace_bytes, void* stream, float* bias_grad = nullptr) {
+                              size_t workspace_bytes, void* stream, float* bias_grad) {
   Params p = {};
   int rc = map_gemm(s, WGRAD, false, p);
   if (rc) return rc;
@@ -2108,71 +2108,69 @@ int jtsm_conv_bf16x3_wgrad_group_plan(const jtsm_conv_shape* s, int n, int* tile
   return JTSM_OK;
 }
 
-int jtsm_conv2d_backward_weight_group_bf16x3(int n, const uint16_t* const* dy_hi, const uint16_t* const* dy_lo,
+// ---- the plane entry points: one per contraction role, every epilogue option a nullable argument -----------------
+// The arithmetic is told by the two INPUT lo planes: both given = split-bf16 (the NP = 2 templates), both null = one
+// fp16 plane per operand (NP = 1).  What only one arithmetic can express is refused here, before anything is launched:
+// an output lo plane under fp16, a gradient shift on split-bf16 planes (which carry none).
+static int planes_arith(const char* what, const void* a_lo, const void* b_lo, const void* out_lo, int grad_shift,
+                        int* np) {
+  JTSM_REQUIRE((a_lo == nullptr) == (b_lo == nullptr),
+               "%s: give both input lo planes (split-bf16) or neither (one fp16 plane per operand)", what);
+  *np = a_lo ? 2 : 1;
+  JTSM_REQUIRE(*np == 2 || !out_lo, "%s: the fp16 arithmetic writes one output plane (the output lo plane must be null)", what);
+  JTSM_REQUIRE(*np == 1 || grad_shift == 0, "%s: grad_shift belongs to the fp16 arithmetic (split-bf16 planes carry no factor)", what);
+  return JTSM_OK;
+}
+#define JTSM_BY_PLANES(np, fn, ...) ((np) == 2 ? fn<2>(__VA_ARGS__) : fn<1>(__VA_ARGS__))
+
+int jtsm_conv2d_backward_weight_group_planes(int n, const uint16_t* const* dy_hi, const uint16_t* const* dy_lo,
                                              const uint16_t* const* x_hi, const uint16_t* const* x_lo,
                                              float* const* dw, const float* const* row_scale,
-                                             const jtsm_conv_shape* s, void* workspace, size_t workspace_bytes,
-                                             void* stream) {
-  return x3_backward_weight_group<2>(n, dy_hi, dy_lo, x_hi, x_lo, dw, row_scale, s, 0, workspace, workspace_bytes, stream);
+                                             const jtsm_conv_shape* s, int grad_shift, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  int np = 0;
+  if (int rc = planes_arith("conv backward-weight group", dy_lo, x_lo, nullptr, grad_shift, &np)) return rc;
+  return JTSM_BY_PLANES(np, x3_backward_weight_group, n, dy_hi, dy_lo, x_hi, x_lo, dw, row_scale, s, grad_shift,
+                        workspace, workspace_bytes, stream);
 }
 
-int jtsm_conv2d_backward_weight_group_f16(int n, const uint16_t* const* dy_h, const uint16_t* const* x_h,
-                                          float* const* dw, const float* const* row_scale, const jtsm_conv_shape* s,
-                                          int grad_shift, void* workspace, size_t workspace_bytes, void* stream) {
-  return x3_backward_weight_group<1>(n, dy_h, nullptr, x_h, nullptr, dw, row_scale, s, grad_shift, workspace,
-                                     workspace_bytes, stream);
-}
-
-int jtsm_conv2d_forward_bf16x3(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t* w_hi,
+int jtsm_conv2d_forward_planes(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t* w_hi,
                                const uint16_t* w_lo, float* y, uint16_t* y_hi, uint16_t* y_lo,
                                const jtsm_conv_shape* s, const float* scale, const float* bias,
-                               const float* residual, int relu, void* workspace, size_t workspace_bytes,
-                               void* stream) {
-  return x3_forward<2>(x_hi, x_lo, w_hi, w_lo, y, y_hi, y_lo, s, scale, bias, residual, relu, workspace,
-                       workspace_bytes, stream);
-}
-
-int jtsm_conv2d_backward_data_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* wt_hi,
-                                     const uint16_t* wt_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
-                                     const jtsm_conv_shape* s, const float* accumulate, const float* relu_mask,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
-  return x3_backward_data<2>(dy_hi, dy_lo, wt_hi, wt_lo, dx, dx_hi, dx_lo, s, accumulate, relu_mask, 0, workspace,
-                             workspace_bytes, stream);
-}
-
-int jtsm_conv2d_backward_weight_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* x_hi,
-                                       const uint16_t* x_lo, float* dw, const jtsm_conv_shape* s,
-                                       const float* row_scale, int zero_dw, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
-  return x3_backward_weight<2>(dy_hi, dy_lo, x_hi, x_lo, dw, s, row_scale, zero_dw, 0, workspace, workspace_bytes,
-                               stream);
-}
-
-/* ---- fp16 path (BASELINE configs[4]): ONE IEEE fp16 plane per operand, fp32 accumulate, fp32 results ---- */
-int jtsm_conv2d_forward_f16(const uint16_t* x_h, const uint16_t* w_h, float* y, uint16_t* y_h,
-                            const jtsm_conv_shape* s, const float* scale, const float* bias,
-                            const float* residual, int relu, void* workspace, size_t workspace_bytes,
-                            void* stream) {
-  return x3_forward<1>(x_h, nullptr, w_h, nullptr, y, y_h, nullptr, s, scale, bias, residual, relu, workspace,
-                       workspace_bytes, stream);
-}
-
-/* ---- fp16-only activations: the residual / accumulate operand as an fp16 plane (include/jtsm_hip.h) ---- */
-int jtsm_conv2d_forward_res16_f16(const uint16_t* x_h, const uint16_t* w_h, float* y, uint16_t* y_h,
-                                  const jtsm_conv_shape* s, const float* scale, const float* bias,
-                                  const uint16_t* residual_h, int relu, void* workspace, size_t workspace_bytes,
-                                  void* stream) {
+                               const float* residual, const uint16_t* residual_h, int relu, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  int np = 0;
+  if (int rc = planes_arith("conv forward", x_lo, w_lo, y_lo, 0, &np)) return rc;
   FwdExtras ex;
   ex.residual_h = residual_h;
-  return x3_forward<1>(x_h, nullptr, w_h, nullptr, y, y_h, nullptr, s, scale, bias, nullptr, relu, workspace,
-                       workspace_bytes, stream, ex);
+  return JTSM_BY_PLANES(np, x3_forward, x_hi, x_lo, w_hi, w_lo, y, y_hi, y_lo, s, scale, bias, residual, relu,
+                        workspace, workspace_bytes, stream, ex);
 }
-int jtsm_conv2d_backward_data_acc16_f16(const uint16_t* dy_h, const uint16_t* wt_h, float* dx, uint16_t* dx_h,
-                                        const jtsm_conv_shape* s, const float* row_scale, const uint16_t* accumulate_h,
-                                        const uint16_t* gate_plane, int grad_shift, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-  return x3_backward_data<1>(dy_h, nullptr, wt_h, nullptr, dx, dx_h, nullptr, s, nullptr, nullptr, grad_shift,
-                             workspace, workspace_bytes, stream, gate_plane, row_scale, nullptr, accumulate_h);
+
+int jtsm_conv2d_backward_data_planes(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* wt_hi,
+                                     const uint16_t* wt_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
+                                     const jtsm_conv_shape* s, const float* row_scale, const float* accumulate,
+                                     const uint16_t* accumulate_h, const float* relu_mask, const uint16_t* gate_plane,
+                                     int grad_shift, float* colsum, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  int np = 0;
+  if (int rc = planes_arith("conv backward-data", dy_lo, wt_lo, dx_lo, grad_shift, &np)) return rc;
+  JTSM_REQUIRE(!accumulate_h || (!relu_mask && !colsum),
+               "conv backward-data: an fp16 accumulate plane goes with neither an fp32 gate (relu_mask) nor column sums");
+  return JTSM_BY_PLANES(np, x3_backward_data, dy_hi, dy_lo, wt_hi, wt_lo, dx, dx_hi, dx_lo, s, accumulate, relu_mask,
+                        grad_shift, workspace, workspace_bytes, stream, gate_plane, row_scale, colsum, accumulate_h);
+}
+
+// db (nullable): dW and db in one contraction (conv_x3.h: x3_bias_mma): db[out_c] = sum over pixels of dy, from the
+// same planes.
+int jtsm_conv2d_backward_weight_planes(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* x_hi,
+                                       const uint16_t* x_lo, float* dw, float* db, const jtsm_conv_shape* s,
+                                       const float* row_scale, int zero_dw, int grad_shift, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  int np = 0;
+  if (int rc = planes_arith("conv backward-weight", dy_lo, x_lo, nullptr, grad_shift, &np)) return rc;
+  return JTSM_BY_PLANES(np, x3_backward_weight, dy_hi, dy_lo, x_hi, x_lo, dw, s, row_scale, zero_dw, grad_shift,
+                        workspace, workspace_bytes, stream, db);
 }
 
 // ---- ConvTranspose2d(kernel 2, stride 2, padding 0): the mask heads' upsampler -----------------------------------
@@ -2197,22 +2195,16 @@ static jtsm_conv_shape ct_conv_shape(int batch, int h, int w, int in_c, int out_
                (long)batch * h * w * 4 * (long)(in_c > out_c ? in_c : out_c) < (1L << 31),                       \
                what ": needs in_c %% 32 == 0, out_c %% 32 == 0 and fewer than 2^31 elements per tensor")
 
-int jtsm_conv_transpose2x2_forward_bf16x3(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t* wt_hi,
+int jtsm_conv_transpose2x2_forward_planes(const uint16_t* x_hi, const uint16_t* x_lo, const uint16_t* wt_hi,
                                           const uint16_t* wt_lo, float* y, uint16_t* y_hi, uint16_t* y_lo, int batch,
                                           int h, int w, int in_c, int out_c, const float* bias, int relu, void* stream) {
   JTSM_CT_DIMS_OK("conv_transpose2x2 forward");
+  int np = 0;
+  if (int rc = planes_arith("conv_transpose2x2 forward", x_lo, wt_lo, y_lo, 0, &np)) return rc;
   const jtsm_conv_shape g = ct_gemm_shape(batch, h, w, in_c, out_c);
   FwdExtras ex; ex.shuffle_c = out_c; ex.shuffle_h = h; ex.shuffle_w = w;
-  return x3_forward<2>(x_hi, x_lo, wt_hi, wt_lo, y, y_hi, y_lo, &g, nullptr, bias, nullptr, relu, nullptr, 0, stream, ex);
-}
-
-int jtsm_conv_transpose2x2_forward_f16(const uint16_t* x_h, const uint16_t* wt_h, float* y, uint16_t* y_h, int batch,
-                                       int h, int w, int in_c, int out_c, const float* bias, int relu, void* stream) {
-  JTSM_CT_DIMS_OK("conv_transpose2x2 forward");
-  const jtsm_conv_shape g = ct_gemm_shape(batch, h, w, in_c, out_c);
-  FwdExtras ex; ex.shuffle_c = out_c; ex.shuffle_h = h; ex.shuffle_w = w;
-  return x3_forward<1>(x_h, nullptr, wt_h, nullptr, y, y_h, nullptr, &g, nullptr, bias, nullptr, relu, nullptr, 0, stream,
-                       ex);
+  return JTSM_BY_PLANES(np, x3_forward, x_hi, x_lo, wt_hi, wt_lo, y, y_hi, y_lo, &g, nullptr, bias, nullptr, relu,
+                        nullptr, 0, stream, ex);
 }
 
 size_t jtsm_conv_transpose2x2_workspace_bytes(int batch, int h, int w, int in_c, int out_c) {
@@ -2221,52 +2213,28 @@ size_t jtsm_conv_transpose2x2_workspace_bytes(int batch, int h, int w, int in_c,
   return jtsm_conv_workspace_bytes(&g, 0);
 }
 
-int jtsm_conv_transpose2x2_backward_data_bf16x3(const uint16_t* g_hi, const uint16_t* g_lo, const uint16_t* w_hi,
+// relu_mask / gate_plane: the ReLU gate as fp32 values or read from the gated activation's hi / fp16 PLANE
+// (Params::mask_plane); dx may be null when only the planes of the gated gradient are wanted (a chain that keeps
+// activations as planes).  colsum (nullable): see jtsm_conv_bf16x3_colsum_rows below.
+int jtsm_conv_transpose2x2_backward_data_planes(const uint16_t* g_hi, const uint16_t* g_lo, const uint16_t* w_hi,
                                                 const uint16_t* w_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
                                                 int batch, int h, int w, int in_c, int out_c, const float* relu_mask,
-                                                const uint16_t* gate_plane, void* workspace, size_t workspace_bytes,
-                                                void* stream) {
+                                                const uint16_t* gate_plane, int grad_shift, float* colsum,
+                                                void* workspace, size_t workspace_bytes, void* stream) {
   JTSM_CT_DIMS_OK("conv_transpose2x2 backward-data");
-  const jtsm_conv_shape g = ct_conv_shape(batch, h, w, in_c, out_c);
-  FwdExtras ex; ex.mask = relu_mask; ex.mask_plane = gate_plane;
-  return x3_forward<2>(g_hi, g_lo, w_hi, w_lo, dx, dx_hi, dx_lo, &g, nullptr, nullptr, nullptr, 0, workspace,
-                       workspace_bytes, stream, ex);
-}
-
-int jtsm_conv_transpose2x2_backward_data_f16(const uint16_t* g_h, const uint16_t* w_h, float* dx, uint16_t* dx_h,
-                                             int batch, int h, int w, int in_c, int out_c, const float* relu_mask,
-                                             const uint16_t* gate_plane, int grad_shift, void* workspace,
-                                             size_t workspace_bytes, void* stream) {
-  JTSM_CT_DIMS_OK("conv_transpose2x2 backward-data");
+  int np = 0;
+  if (int rc = planes_arith("conv_transpose2x2 backward-data", g_lo, w_lo, dx_lo, grad_shift, &np)) return rc;
   JTSM_REQUIRE(grad_shift >= 0 && grad_shift <= 24, "conv_transpose2x2 backward-data f16: grad_shift must be in 0..24");
   const jtsm_conv_shape g = ct_conv_shape(batch, h, w, in_c, out_c);
   FwdExtras ex; ex.mask = relu_mask; ex.mask_plane = gate_plane; ex.in_shift = grad_shift; ex.out_shift = grad_shift;
-  return x3_forward<1>(g_h, nullptr, w_h, nullptr, dx, dx_h, nullptr, &g, nullptr, nullptr, nullptr, 0, workspace,
-                       workspace_bytes, stream, ex);
+  ex.colsum = colsum;
+  return JTSM_BY_PLANES(np, x3_forward, g_hi, g_lo, w_hi, w_lo, dx, dx_hi, dx_lo, &g, nullptr, nullptr, nullptr, 0,
+                        workspace, workspace_bytes, stream, ex);
 }
 
-// The data gradient with its ReLU gate read from the gated activation's hi / fp16 PLANE (Params::mask_plane); dx may
-// be null when only the planes of the gated gradient are wanted (a chain that keeps activations as planes).
-int jtsm_conv2d_backward_data_ex_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* wt_hi,
-                                        const uint16_t* wt_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
-                                        const jtsm_conv_shape* s, const float* row_scale, const float* accumulate,
-                                        const float* relu_mask, const uint16_t* gate_plane, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-  return x3_backward_data<2>(dy_hi, dy_lo, wt_hi, wt_lo, dx, dx_hi, dx_lo, s, accumulate, relu_mask, 0, workspace,
-                             workspace_bytes, stream, gate_plane, row_scale);
-}
-
-int jtsm_conv2d_backward_data_ex_f16(const uint16_t* dy_h, const uint16_t* wt_h, float* dx, uint16_t* dx_h,
-                                     const jtsm_conv_shape* s, const float* row_scale, const float* accumulate,
-                                     const float* relu_mask, const uint16_t* gate_plane, int grad_shift, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-  return x3_backward_data<1>(dy_h, nullptr, wt_h, nullptr, dx, dx_h, nullptr, s, accumulate, relu_mask, grad_shift,
-                             workspace, workspace_bytes, stream, gate_plane, row_scale);
-}
-
-// The same data gradients, also leaving the column sums of the finished (gated) result per row tile: the bias gradient
-// of the layer below, taken where its output gradient is written.  colsum: jtsm_conv_bf16x3_colsum_rows(s, role) x in_c
-// floats; the caller adds the rows up (jtsm_channel_sum_f32) in order.
+// Column sums of a data gradient's (or the transposed convolution's) finished, gated result, one row per row tile: the
+// bias gradient of the layer below, taken where its output gradient is written.  colsum:
+// jtsm_conv_bf16x3_colsum_rows(s, role) x in_c floats; the caller adds the rows up (jtsm_colsum_fold_f32) in order.
 int jtsm_conv_bf16x3_colsum_rows(const jtsm_conv_shape* s, int role) {
   Params p = {};
   if ((role != FWD && role != DGRAD) || map_gemm(s, role, false, p) || !x3_eligible(role, p.s)) return 0;
@@ -2274,79 +2242,6 @@ int jtsm_conv_bf16x3_colsum_rows(const jtsm_conv_shape* s, int role) {
   if (p.M <= 0 || p.N % 4) return 0;
   const X3Plan pl = plan_x3(role, p, 0, true);   // (column sums: one row per row tile of the generic kernel)
   return ceil_div(p.M, 32 * pl.wm * pl.tm);
-}
-int jtsm_conv2d_backward_data_colsum_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* wt_hi,
-                                            const uint16_t* wt_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
-                                            const jtsm_conv_shape* s, const float* row_scale, const float* accumulate,
-                                            const float* relu_mask, const uint16_t* gate_plane, float* colsum,
-                                            void* workspace, size_t workspace_bytes, void* stream) {
-  JTSM_REQUIRE(colsum, "conv backward-data colsum: null colsum");
-  return x3_backward_data<2>(dy_hi, dy_lo, wt_hi, wt_lo, dx, dx_hi, dx_lo, s, accumulate, relu_mask, 0, workspace,
-                             workspace_bytes, stream, gate_plane, row_scale, colsum);
-}
-int jtsm_conv2d_backward_data_colsum_f16(const uint16_t* dy_h, const uint16_t* wt_h, float* dx, uint16_t* dx_h,
-                                         const jtsm_conv_shape* s, const float* row_scale, const float* accumulate,
-                                         const float* relu_mask, const uint16_t* gate_plane, int grad_shift, float* colsum,
-                                         void* workspace, size_t workspace_bytes, void* stream) {
-  JTSM_REQUIRE(colsum, "conv backward-data colsum: null colsum");
-  return x3_backward_data<1>(dy_h, nullptr, wt_h, nullptr, dx, dx_h, nullptr, s, accumulate, relu_mask, grad_shift,
-                             workspace, workspace_bytes, stream, gate_plane, row_scale, colsum);
-}
-int jtsm_conv_transpose2x2_backward_data_colsum_bf16x3(const uint16_t* g_hi, const uint16_t* g_lo, const uint16_t* w_hi,
-                                                       const uint16_t* w_lo, float* dx, uint16_t* dx_hi, uint16_t* dx_lo,
-                                                       int batch, int h, int w, int in_c, int out_c,
-                                                       const float* relu_mask, const uint16_t* gate_plane, float* colsum,
-                                                       void* workspace, size_t workspace_bytes, void* stream) {
-  JTSM_CT_DIMS_OK("conv_transpose2x2 backward-data");
-  JTSM_REQUIRE(colsum, "conv_transpose2x2 backward-data colsum: null colsum");
-  const jtsm_conv_shape g = ct_conv_shape(batch, h, w, in_c, out_c);
-  FwdExtras ex; ex.mask = relu_mask; ex.mask_plane = gate_plane; ex.colsum = colsum;
-  return x3_forward<2>(g_hi, g_lo, w_hi, w_lo, dx, dx_hi, dx_lo, &g, nullptr, nullptr, nullptr, 0, workspace,
-                       workspace_bytes, stream, ex);
-}
-int jtsm_conv_transpose2x2_backward_data_colsum_f16(const uint16_t* g_h, const uint16_t* w_h, float* dx, uint16_t* dx_h,
-                                                    int batch, int h, int w, int in_c, int out_c, const float* relu_mask,
-                                                    const uint16_t* gate_plane, int grad_shift, float* colsum,
-                                                    void* workspace, size_t workspace_bytes, void* stream) {
-  JTSM_CT_DIMS_OK("conv_transpose2x2 backward-data");
-  JTSM_REQUIRE(colsum && grad_shift >= 0 && grad_shift <= 24, "conv_transpose2x2 backward-data colsum f16: null colsum / bad grad_shift");
-  const jtsm_conv_shape g = ct_conv_shape(batch, h, w, in_c, out_c);
-  FwdExtras ex; ex.mask = relu_mask; ex.mask_plane = gate_plane; ex.in_shift = grad_shift; ex.out_shift = grad_shift;
-  ex.colsum = colsum;
-  return x3_forward<1>(g_h, nullptr, w_h, nullptr, dx, dx_h, nullptr, &g, nullptr, nullptr, nullptr, 0, workspace,
-                       workspace_bytes, stream, ex);
-}
-
-// dW and db in one contraction (conv_x3.h: x3_bias_mma): db[out_c] = sum over pixels of dy, from the same planes.
-int jtsm_conv2d_backward_weight_bias_bf16x3(const uint16_t* dy_hi, const uint16_t* dy_lo, const uint16_t* x_hi,
-                                            const uint16_t* x_lo, float* dw, float* db, const jtsm_conv_shape* s,
-                                            const float* row_scale, int zero_dw, void* workspace,
-                                            size_t workspace_bytes, void* stream) {
-  JTSM_REQUIRE(db, "conv backward-weight+bias: null db");
-  return x3_backward_weight<2>(dy_hi, dy_lo, x_hi, x_lo, dw, s, row_scale, zero_dw, 0, workspace, workspace_bytes,
-                               stream, db);
-}
-
-int jtsm_conv2d_backward_weight_bias_f16(const uint16_t* dy_h, const uint16_t* x_h, float* dw, float* db,
-                                         const jtsm_conv_shape* s, const float* row_scale, int zero_dw, int grad_shift,
-                                         void* workspace, size_t workspace_bytes, void* stream) {
-  JTSM_REQUIRE(db, "conv backward-weight+bias: null db");
-  return x3_backward_weight<1>(dy_h, nullptr, x_h, nullptr, dw, s, row_scale, zero_dw, grad_shift, workspace,
-                               workspace_bytes, stream, db);
-}
-
-int jtsm_conv2d_backward_data_f16(const uint16_t* dy_h, const uint16_t* wt_h, float* dx, uint16_t* dx_h,
-                                  const jtsm_conv_shape* s, const float* accumulate, const float* relu_mask,
-                                  int grad_shift, void* workspace, size_t workspace_bytes, void* stream) {
-  return x3_backward_data<1>(dy_h, nullptr, wt_h, nullptr, dx, dx_h, nullptr, s, accumulate, relu_mask, grad_shift,
-                             workspace, workspace_bytes, stream);
-}
-
-int jtsm_conv2d_backward_weight_f16(const uint16_t* dy_h, const uint16_t* x_h, float* dw, const jtsm_conv_shape* s,
-                                    const float* row_scale, int zero_dw, int grad_shift, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-  return x3_backward_weight<1>(dy_h, nullptr, x_h, nullptr, dw, s, row_scale, zero_dw, grad_shift, workspace,
-                               workspace_bytes, stream);
 }
 
 int jtsm_split_f16_f32(const float* src, uint16_t* h, long n, int shift, void* stream) {

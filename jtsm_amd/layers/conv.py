@@ -539,23 +539,15 @@ def _launch_forward(pl, x, w, y, yp, scale=None, bias=None, residual=None, relu=
     relu = int(bool(relu))
     nbytes = pl.ws[0]
     ws = _scratch(nbytes, x.device)
+    rh = _hl(residual_plane)[0]
     lib = L.lib()
-    if residual_plane is not None:
-        assert MATH == "f16" and residual is None
-        rh = _hl(residual_plane)[0]
-        name, call = "conv2d_forward_res16_f16", lambda: lib.jtsm_conv2d_forward_res16_f16(
-            xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), rh, relu, L.ptr(ws), nbytes, L.stream())
-    elif MATH == "f16":
-        name, call = "conv2d_forward_f16", lambda: lib.jtsm_conv2d_forward_f16(
-            xh, wh, L.ptr(y), yh, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), relu, L.ptr(ws), nbytes,
-            L.stream())
-    else:
-        name, call = "conv2d_forward_bf16x3", lambda: lib.jtsm_conv2d_forward_bf16x3(
-            xh, xl, wh, wl, L.ptr(y), yh, yl, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), relu, L.ptr(ws),
-            nbytes, L.stream())
+    call = lambda: lib.jtsm_conv2d_forward_planes(      # noqa: E731
+        xh, xl, wh, wl, L.ptr(y), yh, yl, pl.ref, L.ptr(scale), L.ptr(bias), L.ptr(residual), rh, relu, L.ptr(ws),
+        nbytes, L.stream())
     n_out = pl.s.batch * pl.s.out_c * pl.oh * pl.ow
     extra = _numel(residual) + (0.5 * n_out if residual_plane is not None else 0)    # (an fp16 plane: 2 B per element)
-    L.check(_timed(_x3_variant(pl.s, 0), pl.flops, call, pl.desc, extra, n_out, yp is not None, y is not None), name)
+    L.check(_timed(_x3_variant(pl.s, 0), pl.flops, call, pl.desc, extra, n_out, yp is not None, y is not None),
+            "conv2d_forward_planes")
 
 
 def _launch_backward_data(pl, g, wt, dx, dp, accumulate=None, relu_mask=None, row_scale=None, gate=None,
@@ -568,34 +560,19 @@ def _launch_backward_data(pl, g, wt, dx, dp, accumulate=None, relu_mask=None, ro
     wh, wl = _hl(wt)
     dh, dl = _hl(dp)
     gate_h = _hl(gate)[0]
+    ah = _hl(accumulate_plane)[0]
+    shift = GRAD_SHIFT if MATH == "f16" else 0
     nbytes = pl.ws[1]
     ws = _scratch(nbytes, g.device)
     lib = L.lib()
-    if accumulate_plane is not None:
-        assert MATH == "f16" and accumulate is None and relu_mask is None and colsum is None
-        ah = _hl(accumulate_plane)[0]
-        name, call = "conv2d_backward_data_acc16_f16", lambda: lib.jtsm_conv2d_backward_data_acc16_f16(
-            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), ah, gate_h, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream())
-    elif colsum is not None and MATH == "f16":
-        name, call = "conv2d_backward_data_colsum_f16", lambda: lib.jtsm_conv2d_backward_data_colsum_f16(
-            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), L.ptr(accumulate), L.ptr(relu_mask), gate_h, GRAD_SHIFT,
-            L.ptr(colsum), L.ptr(ws), nbytes, L.stream())
-    elif colsum is not None:
-        name, call = "conv2d_backward_data_colsum_bf16x3", lambda: lib.jtsm_conv2d_backward_data_colsum_bf16x3(
-            gh, gl, wh, wl, L.ptr(dx), dh, dl, pl.ref, L.ptr(row_scale), L.ptr(accumulate), L.ptr(relu_mask), gate_h,
-            L.ptr(colsum), L.ptr(ws), nbytes, L.stream())
-    elif MATH == "f16":     # (jtsm_conv2d_backward_data_* is the _ex_ entry point with row_scale and gate_plane null)
-        name, call = "conv2d_backward_data_ex_f16", lambda: lib.jtsm_conv2d_backward_data_ex_f16(
-            gh, wh, L.ptr(dx), dh, pl.ref, L.ptr(row_scale), L.ptr(accumulate), L.ptr(relu_mask), gate_h, GRAD_SHIFT,
-            L.ptr(ws), nbytes, L.stream())
-    else:
-        name, call = "conv2d_backward_data_ex_bf16x3", lambda: lib.jtsm_conv2d_backward_data_ex_bf16x3(
-            gh, gl, wh, wl, L.ptr(dx), dh, dl, pl.ref, L.ptr(row_scale), L.ptr(accumulate), L.ptr(relu_mask), gate_h,
-            L.ptr(ws), nbytes, L.stream())
+    call = lambda: lib.jtsm_conv2d_backward_data_planes(      # noqa: E731
+        gh, gl, wh, wl, L.ptr(dx), dh, dl, pl.ref, L.ptr(row_scale), L.ptr(accumulate), ah, L.ptr(relu_mask), gate_h,
+        shift, L.ptr(colsum), L.ptr(ws), nbytes, L.stream())
     n_in = pl.s.batch * pl.s.in_c * pl.s.in_h * pl.s.in_w
     half = (gate is not None) + (accumulate_plane is not None)     # (a gate / fp16 plane: 2 bytes per element)
     extra = _numel(accumulate) + _numel(relu_mask) + 0.5 * n_in * half
-    L.check(_timed(_x3_variant(pl.s, 1), pl.flops, call, pl.desc, extra, n_in, dp is not None, dx is not None), name)
+    L.check(_timed(_x3_variant(pl.s, 1), pl.flops, call, pl.desc, extra, n_in, dp is not None, dx is not None),
+            "conv2d_backward_data_planes")
 
 
 def _launch_backward_weight(pl, g, x, out, row_scale, fresh, bias_out=None):
@@ -606,21 +583,12 @@ def _launch_backward_weight(pl, g, x, out, row_scale, fresh, bias_out=None):
     fresh = int(fresh)
     nbytes = pl.ws[2] if bias_out is None else max(pl.ws[3], pl.ws[2])
     ws = _scratch(nbytes, x.device)
+    shift = GRAD_SHIFT if MATH == "f16" else 0
     lib = L.lib()
-    if bias_out is not None and MATH == "f16":
-        name, call = "conv2d_backward_weight_bias_f16", lambda: lib.jtsm_conv2d_backward_weight_bias_f16(
-            gh, xh, L.ptr(out), L.ptr(bias_out), pl.ref, L.ptr(row_scale), fresh, GRAD_SHIFT, L.ptr(ws), nbytes,
-            L.stream())
-    elif bias_out is not None:
-        name, call = "conv2d_backward_weight_bias_bf16x3", lambda: lib.jtsm_conv2d_backward_weight_bias_bf16x3(
-            gh, gl, xh, xl, L.ptr(out), L.ptr(bias_out), pl.ref, L.ptr(row_scale), fresh, L.ptr(ws), nbytes, L.stream())
-    elif MATH == "f16":
-        name, call = "conv2d_backward_weight_f16", lambda: lib.jtsm_conv2d_backward_weight_f16(
-            gh, xh, L.ptr(out), pl.ref, L.ptr(row_scale), fresh, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream())
-    else:
-        name, call = "conv2d_backward_weight_bf16x3", lambda: lib.jtsm_conv2d_backward_weight_bf16x3(
-            gh, gl, xh, xl, L.ptr(out), pl.ref, L.ptr(row_scale), fresh, L.ptr(ws), nbytes, L.stream())
-    L.check(_timed(_x3_variant(pl.s, 2), pl.flops, call, pl.desc, 0, out.numel()), name)
+    call = lambda: lib.jtsm_conv2d_backward_weight_planes(      # noqa: E731
+        gh, gl, xh, xl, L.ptr(out), L.ptr(bias_out), pl.ref, L.ptr(row_scale), fresh, shift, L.ptr(ws), nbytes,
+        L.stream())
+    L.check(_timed(_x3_variant(pl.s, 2), pl.flops, call, pl.desc, 0, out.numel()), "conv2d_backward_weight_planes")
 
 
 def _slot_view(w, w_shape):
@@ -754,14 +722,10 @@ def _launch_ct_forward(x, x_shape, w, y, yp, bias, relu):
     lib = L.lib()
     var = _x3_variant(_plan((n, i, h, wd), (4 * o, i, 1, 1), 1, 0, 1).s, 0)
     var = _Variant(str(var), 1) if var is not None else None      # (the pixel-shuffle epilogue never splits K)
-    if MATH == "f16":
-        name, call = "conv_transpose2x2_forward_f16", lambda: lib.jtsm_conv_transpose2x2_forward_f16(
-            xh, wth, L.ptr(y), yh, n, h, wd, i, o, L.ptr(bias), relu, L.stream())
-    else:
-        name, call = "conv_transpose2x2_forward_bf16x3", lambda: lib.jtsm_conv_transpose2x2_forward_bf16x3(
-            xh, xl, wth, wtl, L.ptr(y), yh, yl, n, h, wd, i, o, L.ptr(bias), relu, L.stream())
+    call = lambda: lib.jtsm_conv_transpose2x2_forward_planes(      # noqa: E731
+        xh, xl, wth, wtl, L.ptr(y), yh, yl, n, h, wd, i, o, L.ptr(bias), relu, L.stream())
     L.check(_timed(var, 2.0 * n * h * wd * i * 4 * o, call, _ct_desc(n, h, wd, i, o), 0, 4 * n * o * h * wd,
-                   yp is not None, y is not None), name)
+                   yp is not None, y is not None), "conv_transpose2x2_forward_planes")
 
 
 def _launch_ct_backward_data(pl, g, w, dx, dp, relu_mask=None, gate=None, colsum=None):
@@ -774,28 +738,17 @@ def _launch_ct_backward_data(pl, g, w, dx, dp, relu_mask=None, gate=None, colsum
     wh, wl = _hl(w)
     dh, dl = _hl(dp)
     gate_h = _hl(gate)[0]
+    shift = GRAD_SHIFT if MATH == "f16" else 0
     nbytes = pl.ws[0]
     ws = _scratch(nbytes, g.device)
     lib = L.lib()
-    if colsum is not None and MATH == "f16":
-        name = "conv_transpose2x2_backward_data_colsum_f16"
-        call = lambda: lib.jtsm_conv_transpose2x2_backward_data_colsum_f16(      # noqa: E731
-            gh, wh, L.ptr(dx), dh, n, h, wd, i, o, L.ptr(relu_mask), gate_h, GRAD_SHIFT, L.ptr(colsum), L.ptr(ws),
-            nbytes, L.stream())
-    elif colsum is not None:
-        name = "conv_transpose2x2_backward_data_colsum_bf16x3"
-        call = lambda: lib.jtsm_conv_transpose2x2_backward_data_colsum_bf16x3(   # noqa: E731
-            gh, gl, wh, wl, L.ptr(dx), dh, dl, n, h, wd, i, o, L.ptr(relu_mask), gate_h, L.ptr(colsum), L.ptr(ws),
-            nbytes, L.stream())
-    elif MATH == "f16":
-        name, call = "conv_transpose2x2_backward_data_f16", lambda: lib.jtsm_conv_transpose2x2_backward_data_f16(
-            gh, wh, L.ptr(dx), dh, n, h, wd, i, o, L.ptr(relu_mask), gate_h, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream())
-    else:
-        name, call = "conv_transpose2x2_backward_data_bf16x3", lambda: lib.jtsm_conv_transpose2x2_backward_data_bf16x3(
-            gh, gl, wh, wl, L.ptr(dx), dh, dl, n, h, wd, i, o, L.ptr(relu_mask), gate_h, L.ptr(ws), nbytes, L.stream())
+    call = lambda: lib.jtsm_conv_transpose2x2_backward_data_planes(      # noqa: E731
+        gh, gl, wh, wl, L.ptr(dx), dh, dl, n, h, wd, i, o, L.ptr(relu_mask), gate_h, shift, L.ptr(colsum), L.ptr(ws),
+        nbytes, L.stream())
     n_dx = n * i * h * wd
     extra = _numel(relu_mask) + 0.5 * n_dx * (gate is not None)     # (the gate plane: 2 bytes per element)
-    L.check(_timed(_x3_variant(s, 0), pl.flops, call, pl.desc, extra, n_dx, dp is not None, dx is not None), name)
+    L.check(_timed(_x3_variant(s, 0), pl.flops, call, pl.desc, extra, n_dx, dp is not None, dx is not None),
+            "conv_transpose2x2_backward_data_planes")
 
 
 def conv_transpose2x2_forward(x, w, bias=None, relu=False, emit_planes=False):
@@ -1008,7 +961,7 @@ def planes_backward_weight(g, x, w, stride=1, pad=0, dil=1, w_shape=None, row_sc
 # DEFER_WGRAD the fused bottleneck node only QUEUES its weight gradients (operand planes kept alive) and hands autograd
 # nothing; flush_deferred_weight_gradients() — called by the first block of every stage (the last of the stage to run
 # in a backward), by the gradient exchange before it closes its buckets, and at the end of the backward — launches the
-# queued layers of one shape as ONE group (jtsm_conv2d_backward_weight_group_*: a sixth of the slices, one finishing
+# queued layers of one shape as ONE group (jtsm_conv2d_backward_weight_group_planes: a sixth of the slices, one finishing
 # launch), stores the results as the parameters' .grad (accumulating into an existing one) and runs their
 # post-accumulate hooks, which is all AccumulateGrad would have done.
 # Only for leaf parameters reached through `.backward()`: `torch.autograd.grad(..., inputs=[weight])` must switch it off
@@ -1259,6 +1212,9 @@ def flush_deferred_weight_gradients():
             ptr_t = C.c_void_p * n
             gh, gl = zip(*[_hl(g.buf) for g, *_ in part])
             xh, xl = zip(*[_hl(x.buf) for _, x, *_ in part])
+            ghs, xhs = ptr_t(*gh), ptr_t(*xh)
+            gls, xls = (None, None) if MATH == "f16" else (ptr_t(*gl), ptr_t(*xl))    # (fp16: no lo planes at all)
+            shift = GRAD_SHIFT if MATH == "f16" else 0
             dws = ptr_t(*[o.data_ptr() for o in outs])
             scales = ptr_t(*[(it[6].data_ptr() if it[6] is not None else None) for it in part])
             nbytes = lib.jtsm_conv_bf16x3_wgrad_group_workspace_bytes(pl.ref, n)
@@ -1274,14 +1230,10 @@ def flush_deferred_weight_gradients():
                     base = "igemm_x3_wgrad_group_kernel<%s,2%s>" % ("4,2,2,4" if tile.value == 256 else "2,2,2,2", np_)
                 variant = _Variant(base, sp.value)
             desc = pl.desc[:-1] + (pl.desc[-1] * n,) if pl.desc is not None else None
-            if MATH == "f16":
-                call = lambda: lib.jtsm_conv2d_backward_weight_group_f16(      # noqa: E731
-                    n, ptr_t(*gh), ptr_t(*xh), dws, scales, pl.ref, GRAD_SHIFT, L.ptr(ws), nbytes, L.stream())
-            else:
-                call = lambda: lib.jtsm_conv2d_backward_weight_group_bf16x3(   # noqa: E731
-                    n, ptr_t(*gh), ptr_t(*gl), ptr_t(*xh), ptr_t(*xl), dws, scales, pl.ref, L.ptr(ws), nbytes,
-                    L.stream())
-            L.check(_timed(variant, pl.flops * n, call, desc, 0, outs[0].numel() * n), "conv2d_backward_weight_group")
+            call = lambda: lib.jtsm_conv2d_backward_weight_group_planes(      # noqa: E731
+                n, ghs, gls, xhs, xls, dws, scales, pl.ref, shift, L.ptr(ws), nbytes, L.stream())
+            L.check(_timed(variant, pl.flops * n, call, desc, 0, outs[0].numel() * n),
+                    "conv2d_backward_weight_group_planes")
             for (g, x, w, *_), o in zip(part, outs):
                 _deliver_grad(w, o)
 

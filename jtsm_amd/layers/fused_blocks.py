@@ -207,10 +207,10 @@ class _IdentityChain16Fn(Function):
     """fp16-ONLY activations (BASELINE configs[4]; the reference's AMP step keeps activations and their gradients in
     fp16, detectron2/engine/train_loop.py:289-336): the identity-shortcut blocks of a stage — every block after its
     first — as ONE autograd node in the fp16 arithmetic.  Inside it an activation exists as its fp16 operand plane and
-    nothing else: conv3's epilogue reads the residual from the block input's plane (jtsm_conv2d_forward_res16_f16) and
+    nothing else: conv3's epilogue reads the residual from the block input's plane (jtsm_conv2d_forward_planes: residual_h) and
     writes the block output's plane only; backward, the gradient stream between the blocks is an fp16 plane carrying
     2^GRAD_SHIFT — conv1's data-gradient epilogue adds the shortcut term from the previous plane
-    (jtsm_conv2d_backward_data_acc16_f16), gates by the block input's plane and emits the next one.  fp32 exists for the
+    (jtsm_conv2d_backward_data_planes: accumulate_h), gates by the block input's plane and emits the next one.  fp32 exists for the
     chain's input (the first block's output, whose plane is reused), its output (read by the FPN lateral and the next
     stage) and the two gradients at those ends.  Per inner block output that is 2 B written + 2 B read instead of
     4 + 2 B written + 4 B read.

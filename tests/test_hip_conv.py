@@ -121,7 +121,7 @@ def test_conv_backward_data_and_weight(cuda, case):
     dw2 = K.conv2d_backward_weight(dyd, xd, tuple(w.shape), s, p, d, bias_out=db)
     close(db, dy.double().sum((0, 2, 3)), "bias gradient")
     close(dw2, w.grad / scale.view(-1, 1, 1, 1), "wgrad beside the bias gradient")
-    # row scale applied to the data gradient's rows (jtsm_conv2d_backward_data_ex_*) for the 1x1 cases
+    # row scale applied to the data gradient's rows (row_scale of jtsm_conv2d_backward_data_planes) for the 1x1 cases
     # accumulate + relu gate epilogue of dgrad
     acc = torch.randn(x.shape, generator=g)
     gate = torch.randn(x.shape, generator=g)
@@ -817,7 +817,7 @@ def test_block_output_gate_rides_in_the_next_blocks_epilogue(cuda, monkeypatch, 
 @pytest.mark.parametrize("math", ["bf16x3", "f16"])
 def test_deferred_weight_gradients_are_grouped_and_match_the_single_launches(cuda, math):
     """layers/conv.py: with DEFER_WGRAD the fused bottleneck node queues its weight gradients and the same-shape layers
-    of a stage go out as ONE grouped launch (jtsm_conv2d_backward_weight_group_*).  A stage of one projection block +
+    of a stage go out as ONE grouped launch (jtsm_conv2d_backward_weight_group_planes).  A stage of one projection block +
     four identity blocks: the data gradient is the same bits either way; every weight gradient agrees with the
     single-launch result to summation order (different K slicing: 1e-5 of the tensor's magnitude; fp16 planes round the
     same operands the same way, so the bar is the same), twice in a row gives the same bits, and the launch log shows
@@ -886,3 +886,175 @@ def test_deferred_weight_gradients_are_grouped_and_match_the_single_launches(cud
     finally:
         K.defer_weight_gradients(True)
         K.set_math(old)
+
+
+def test_plane_entry_points_refuse_what_neither_arithmetic_expresses(cuda):
+    """The six jtsm_*_planes entry points (include/jtsm_hip.h) take both plane arithmetics and every epilogue option as
+    nullable arguments; the combinations no arithmetic has must come back as JTSM_EINVAL with a jtsm_last_error text and
+    launch nothing.  Each case is a call on real device buffers of the right sizes (batch 1, 8x8, 32 -> 32 channels,
+    1x1; the matching 2x2 transposed pair) that is valid except for ONE combination: it is refused, the result buffers
+    still hold their fill value after a synchronise, and the same call without the offending argument returns JTSM_OK.
+    (Independent of the module's arithmetic fixture: the calls name their arithmetic by their lo planes.)"""
+    import ctypes as C
+
+    from jtsm_amd import _lib as L
+
+    lib, EINVAL, FILL = L.lib(), -1, {torch.float32: 7.0, torch.int16: 0x1234}
+    declared = L.declarations()
+    gen = torch.Generator().manual_seed(31)
+    shift = K.GRAD_SHIFT
+
+    def planes(rows, cols):      # one random matrix as (bf16 hi, bf16 lo, fp16) planes
+        v = (torch.randn(rows, cols, generator=gen) * 0.1).to(cuda)
+        hi = v.bfloat16()
+        return hi.view(torch.int16), (v - hi.float()).bfloat16().view(torch.int16), v.half().view(torch.int16)
+
+    def f32(n):
+        return torch.randn(n, generator=gen).to(cuda)
+
+    def result(n, dtype=torch.float32):
+        return torch.full((n,), FILL[dtype], dtype=dtype, device=cuda)
+
+    def scratch(nbytes):
+        return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=cuda)
+
+    def raw(args):
+        return [a.data_ptr() if torch.is_tensor(a) else a for a in args.values()]
+
+    def check(fn, results, valid, offending, word):
+        """`fn`: (entry point's name, call); `valid`: the arguments of a call that is fine, by name and in order;
+        `offending`: what turns it into the refused combination."""
+        name, call = fn
+        assert len(valid) == len(declared[name][1]), name
+        assert call(raw(dict(valid, **offending))) == EINVAL, (name, sorted(offending))
+        msg = lib.jtsm_last_error().decode()
+        assert msg and word in msg, (name, sorted(offending), msg)
+        torch.cuda.synchronize()
+        for r in results:
+            assert bool((r == FILL[r.dtype]).all()), (name, sorted(offending), "something was launched")
+        assert call(raw(valid)) == 0, (name, lib.jtsm_last_error())
+        torch.cuda.synchronize()
+        for r in results:
+            r.fill_(FILL[r.dtype])
+
+    def arith(np_, hi, lo, h16):     # (hi, lo) arguments of one operand in the split-bf16 (2) / fp16 (1) arithmetic
+        return (hi, lo) if np_ == 2 else (h16, None)
+
+    s = K.ConvShape(1, 8, 8, 32, 32, 1, 1, 1, 0, 1)
+    ref, st = C.byref(s), L.stream()
+    px, cin, cout = 64, 32, 32
+    x, w, wt, dy = planes(px, cin), planes(cout, cin), planes(cin, cout), planes(px, cout)
+    half_res, half_acc, gate = planes(px, cout)[2], planes(px, cin)[2], planes(px, cin)[2]
+    scale, bias, ch_scale = f32(cout), f32(cout), f32(cout)
+    res, acc, mask = f32(px * cout), f32(px * cin), f32(px * cin)
+
+    # ---- forward
+    y, y_hi, y_lo = result(px * cout), result(px * cout, torch.int16), result(px * cout, torch.int16)
+    nb = lib.jtsm_conv_workspace_bytes(ref, 0)
+    ws = scratch(nb)
+
+    def fwd(np_, **over):
+        (xh, xl), (wh, wl) = arith(np_, *x), arith(np_, *w)
+        return dict(dict(x_hi=xh, x_lo=xl, w_hi=wh, w_lo=wl, y=y, y_hi=y_hi, y_lo=y_lo if np_ == 2 else None, s=ref,
+                         scale=scale, bias=bias, residual=None, residual_h=None, relu=1, ws=ws, nbytes=nb, stream=st),
+                    **over)
+    fn = ("jtsm_conv2d_forward_planes", lambda a: lib.jtsm_conv2d_forward_planes(*a))
+    outs = (y, y_hi, y_lo)
+    check(fn, outs, fwd(1), dict(x_lo=x[1]), "lo plane")
+    check(fn, outs, fwd(1), dict(w_lo=w[1]), "lo plane")
+    check(fn, outs, fwd(1), dict(y_lo=y_lo), "lo plane")
+    check(fn, outs, fwd(2), dict(residual_h=half_res), "residual")
+    check(fn, outs, fwd(1, residual=res), dict(residual_h=half_res), "residual")
+
+    # ---- backward-data
+    dx, dx_hi, dx_lo = result(px * cin), result(px * cin, torch.int16), result(px * cin, torch.int16)
+    rows = lib.jtsm_conv_bf16x3_colsum_rows(ref, 1)
+    assert rows > 0
+    colsum = result(rows * cin)
+    nb1 = lib.jtsm_conv_workspace_bytes(ref, 1)
+    ws1 = scratch(nb1)
+
+    def bwd(np_, **over):
+        (gh, gl), (wh, wl) = arith(np_, *dy), arith(np_, *wt)
+        return dict(dict(dy_hi=gh, dy_lo=gl, wt_hi=wh, wt_lo=wl, dx=dx, dx_hi=dx_hi, dx_lo=dx_lo if np_ == 2 else None,
+                         s=ref, row_scale=None, accumulate=None, accumulate_h=None, relu_mask=None, gate_plane=gate,
+                         grad_shift=shift if np_ == 1 else 0, colsum=None, ws=ws1, nbytes=nb1, stream=st), **over)
+    fn = ("jtsm_conv2d_backward_data_planes", lambda a: lib.jtsm_conv2d_backward_data_planes(*a))
+    outs = (dx, dx_hi, dx_lo, colsum)
+    check(fn, outs, bwd(1), dict(dy_lo=dy[1]), "lo plane")
+    check(fn, outs, bwd(1), dict(wt_lo=wt[1]), "lo plane")
+    check(fn, outs, bwd(1), dict(dx_lo=dx_lo), "lo plane")
+    check(fn, outs, bwd(2, colsum=colsum), dict(grad_shift=shift), "grad_shift")
+    check(fn, outs, bwd(2), dict(accumulate_h=half_acc), "accumulate")
+    check(fn, outs, bwd(1, accumulate=acc), dict(accumulate_h=half_acc), "accumulate")
+    check(fn, outs, bwd(1, accumulate_h=half_acc), dict(relu_mask=mask), "accumulate")
+    check(fn, outs, bwd(1, accumulate_h=half_acc), dict(colsum=colsum), "accumulate")
+
+    # ---- backward-weight, single and grouped
+    dw, db = result(cout * cin), result(cout)
+    nb2 = lib.jtsm_conv_bf16x3_wgrad_bias_workspace_bytes(ref)
+    ws2 = scratch(nb2)
+
+    def wgrad(np_, **over):
+        (gh, gl), (xh, xl) = arith(np_, *dy), arith(np_, *x)
+        return dict(dict(dy_hi=gh, dy_lo=gl, x_hi=xh, x_lo=xl, dw=dw, db=db, s=ref, row_scale=ch_scale, zero_dw=1,
+                         grad_shift=shift if np_ == 1 else 0, ws=ws2, nbytes=nb2, stream=st), **over)
+    fn = ("jtsm_conv2d_backward_weight_planes", lambda a: lib.jtsm_conv2d_backward_weight_planes(*a))
+    outs = (dw, db)
+    check(fn, outs, wgrad(1), dict(dy_lo=dy[1]), "lo plane")
+    check(fn, outs, wgrad(1), dict(x_lo=x[1]), "lo plane")
+    check(fn, outs, wgrad(2), dict(grad_shift=shift), "grad_shift")
+
+    x2, dy2 = planes(px, cin), planes(px, cout)
+    dws = (dw, result(cout * cin))
+    nb3 = lib.jtsm_conv_bf16x3_wgrad_group_workspace_bytes(ref, 2)
+    ws3 = scratch(nb3)
+
+    def table(*ts):
+        return (C.c_void_p * len(ts))(*[t.data_ptr() if t is not None else None for t in ts])
+
+    def group(np_, **over):
+        i, j = (0, 1) if np_ == 2 else (2, None)
+        return dict(dict(n=2, dy_hi=table(dy[i], dy2[i]), dy_lo=table(dy[j], dy2[j]) if j else None,
+                         x_hi=table(x[i], x2[i]), x_lo=table(x[j], x2[j]) if j else None, dw=table(*dws),
+                         row_scale=table(ch_scale, None), s=ref, grad_shift=shift if np_ == 1 else 0, ws=ws3, nbytes=nb3,
+                         stream=st), **over)
+    fn = ("jtsm_conv2d_backward_weight_group_planes", lambda a: lib.jtsm_conv2d_backward_weight_group_planes(*a))
+    check(fn, dws, group(1), dict(dy_lo=table(dy[1], dy2[1])), "lo plane")
+    check(fn, dws, group(1), dict(x_lo=table(x[1], x2[1])), "lo plane")
+    check(fn, dws, group(2), dict(grad_shift=shift), "grad_shift")
+
+    # ---- the transposed 2x2 pair: x (1, 8, 8, 32) -> y (1, 16, 16, 32)
+    n, h, wd, ci, co = 1, 8, 8, 32, 32
+    w_t, w_plain, g = planes(4 * co, ci), planes(ci, 4 * co), planes(4 * px, co)
+    ty, ty_hi, ty_lo = result(4 * px * co), result(4 * px * co, torch.int16), result(4 * px * co, torch.int16)
+
+    def ct_fwd(np_, **over):
+        (xh, xl), (wh, wl) = arith(np_, *x), arith(np_, *w_t)
+        return dict(dict(x_hi=xh, x_lo=xl, wt_hi=wh, wt_lo=wl, y=ty, y_hi=ty_hi, y_lo=ty_lo if np_ == 2 else None, batch=n,
+                         h=h, w=wd, in_c=ci, out_c=co, bias=bias, relu=1, stream=st), **over)
+    fn = ("jtsm_conv_transpose2x2_forward_planes", lambda a: lib.jtsm_conv_transpose2x2_forward_planes(*a))
+    outs = (ty, ty_hi, ty_lo)
+    check(fn, outs, ct_fwd(1), dict(x_lo=x[1]), "lo plane")
+    check(fn, outs, ct_fwd(1), dict(wt_lo=w_t[1]), "lo plane")
+    check(fn, outs, ct_fwd(1), dict(y_lo=ty_lo), "lo plane")
+
+    ct_shape = K.ConvShape(n, 2 * h, 2 * wd, co, ci, 2, 2, 2, 0, 1)      # the convolution it transposes
+    rows = lib.jtsm_conv_bf16x3_colsum_rows(C.byref(ct_shape), 0)
+    assert rows > 0
+    ct_colsum = result(rows * ci)
+    nb4 = lib.jtsm_conv_transpose2x2_workspace_bytes(n, h, wd, ci, co)
+    ws4 = scratch(nb4)
+
+    def ct_bwd(np_, **over):
+        (gh, gl), (wh, wl) = arith(np_, *g), arith(np_, *w_plain)
+        return dict(dict(g_hi=gh, g_lo=gl, w_hi=wh, w_lo=wl, dx=dx, dx_hi=dx_hi, dx_lo=dx_lo if np_ == 2 else None,
+                         batch=n, h=h, w=wd, in_c=ci, out_c=co, relu_mask=None, gate_plane=gate,
+                         grad_shift=shift if np_ == 1 else 0, colsum=ct_colsum, ws=ws4, nbytes=nb4, stream=st), **over)
+    fn = ("jtsm_conv_transpose2x2_backward_data_planes", lambda a: lib.jtsm_conv_transpose2x2_backward_data_planes(*a))
+    outs = (dx, dx_hi, dx_lo, ct_colsum)
+    check(fn, outs, ct_bwd(1), dict(g_lo=g[1]), "lo plane")
+    check(fn, outs, ct_bwd(1), dict(w_lo=w_plain[1]), "lo plane")
+    check(fn, outs, ct_bwd(1), dict(dx_lo=dx_lo), "lo plane")
+    check(fn, outs, ct_bwd(2), dict(grad_shift=shift), "grad_shift")
+    torch.cuda.synchronize()

@@ -619,7 +619,7 @@ def test_r101_rectangular_fp16_losses_within_stated_tolerance(cuda):
 def test_fp16_only_identity_chain_matches_the_per_block_nodes(cuda):
     """fp16-only activations.  A stage's identity blocks as ONE node whose activations and gradient
     stream are fp16 planes alone (layers/fused_blocks.py: _IdentityChain16Fn; residual / shortcut gradient read from
-    planes: jtsm_conv2d_forward_res16_f16 / jtsm_conv2d_backward_data_acc16_f16) against (1) the per-block nodes of the
+    planes: residual_h / accumulate_h of jtsm_conv2d_{forward,backward_data}_planes) against (1) the per-block nodes of the
     same fp16 arithmetic, which keep an fp32 residual stream, and (2) the same stage in exact fp32: output, input
     gradient and every weight gradient within the fp16 leg's stated bars (operands round at 2^-11 per layer either
     way; the chain also rounds the residual stream once per block, as the reference's AMP step does)."""
