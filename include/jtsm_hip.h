@@ -1168,6 +1168,47 @@ int jtsm_deform_input_grad_f32(const float* dcols, const float* offset, const fl
                                int W, int C, int G, int kh, int kw, int stride, int pad, int dil, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Keypoint R-CNN.  Logits / heatmaps are float32, plain contiguous (R, K, S, S): one (roi, keypoint)
+ * map is one row of S * S floats, S <= 64.  rois (R, 4) are x1, y1, x2, y2.  Built without floating-point contraction.
+ *
+ * jtsm_keypoint_targets_f32 — `_keypoints_to_heatmap`, detectron2/structures/keypoints.py:84-140, in its fp32
+ *   arithmetic: scale = (1 / (x2 - x1)) * S, as torch evaluates the reference's `S / (x2 - x1)`; cell = floor((x - x1) * scale); x == x2 -> S - 1; valid = inside and v > 0;
+ *   targets (N, K) int32 = (cy * S + cx) * valid; valid (N, K) uint8.  keypoints (N, K, 3) = x, y, v.
+ * jtsm_keypoint_loss_forward_f32 / _backward_f32 — `keypoint_rcnn_loss`, detectron2/modeling/roi_heads/
+ *   keypoint_head.py:40-96: loss <- sum over valid rows of lse(row) - row[target], divided by `normalizer`, or by the
+ *   number of valid rows when normalizer <= 0 (the reference's None); no valid row: 0.  One workgroup per row, the
+ *   row in registers, a fixed-order sum over the rows: two runs give the same bits.  workspace:
+ *   jtsm_keypoint_loss_workspace_bytes(N, K), 256-byte aligned, carried from the forward to the backward (each row's
+ *   lse and the divisor).  Backward: grad_logits <- (exp(x - lse) - onehot) * *grad_loss / divisor on valid rows, 0
+ *   on the others; EVERY element is written.  grad_loss is a device scalar.
+ * jtsm_keypoint_decode_f32 — `heatmaps_to_keypoints`, detectron2/structures/keypoints.py:143-217: out (R, K, 4) =
+ *   x, y, logit, score.  One workgroup per map, the map in LDS; the bicubic value (A = -0.75, align_corners = False,
+ *   taps clamped to the border, horizontal sums first) of every pixel of the ceil(w) x ceil(h) up-sampling is
+ *   computed on the fly under a running arg-max whose ties go to the lowest flat index; score = 1 / sum exp(map - max)
+ *   over the S x S map.  A box side beyond 16384 px is walked up to 16384.  The maps are not modified.
+ * jtsm_keypoint_upsample_forward_f32 / _backward_f32 — the tail of `KRCNNConvDeconvUpsampleHead.layers`,
+ *   keypoint_head.py:247-272: z (R, H, W, Cp) channels-last is the 3x3 convolution form of ConvTranspose2d(C, K, 4,
+ *   stride 2, padding 1), channel (py * 2 + px) * K + k = output pixel (2 i + py, 2 j + px) of keypoint k, Cp >= 4 K
+ *   (padding channels ignored); logits (R, K, 4 H, 4 W) <- F.interpolate(scale_factor=2, "bilinear",
+ *   align_corners=False) of the shuffled map, one pass.  Backward: grad_z (R, H, W, Cp) <- the exact adjoint as a
+ *   gather per element, zeros in the padding channels; no atomics.
+ * Nothing is allocated or synchronised; R = 0 / N = 0 launch nothing (the loss forward still writes loss = 0).
+ * ------------------------------------------------------------------------------------------------------------------ */
+int jtsm_keypoint_targets_f32(const float* keypoints, const float* rois, int N, int K, int S, int32_t* targets,
+                              uint8_t* valid, void* stream);
+size_t jtsm_keypoint_loss_workspace_bytes(int N, int K);
+int jtsm_keypoint_loss_forward_f32(const float* logits, const int32_t* targets, const uint8_t* valid, int N, int K,
+                                   int S, float normalizer, float* loss, void* workspace, void* stream);
+int jtsm_keypoint_loss_backward_f32(const float* logits, const int32_t* targets, const uint8_t* valid, int N, int K,
+                                    int S, const float* grad_loss, const void* workspace, float* grad_logits,
+                                    void* stream);
+int jtsm_keypoint_decode_f32(const float* maps, const float* rois, int R, int K, int S, float* out, void* stream);
+int jtsm_keypoint_upsample_forward_f32(const float* z, int R, int K, int H, int W, int Cp, float* logits,
+                                       void* stream);
+int jtsm_keypoint_upsample_backward_f32(const float* grad_logits, int R, int K, int H, int W, int Cp, float* grad_z,
+                                        void* stream);
+
 /* Model input boundary: GeneralizedMCNNWSL.preprocess_image
  * (projects/WSL/wsl/modeling/meta_arch/mcnn.py:303-318) + ImageList.from_tensors
  * (detectron2/structures/image_list.py:71-125) in one launch: images[b] is the mapper's uint8 (C, h_b, w_b) planar

@@ -34,7 +34,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # cmil.hip likewise: ROIMerge's clique means are `sum += C[n] / IC`, each quotient and each sum rounded.
 # rotated_boxes.hip likewise: the IoU is box_iou_rotated_utils.h with every product and sum rounded, as tests/rotated_ref.py.
 # deform_conv.hip likewise: the bilinear sample is `w1*v1 + w2*v2 + w3*v3 + w4*v4` product by product, as tests/deform_conv_ref.py.
+# keypoint.hip likewise: target cells are `floor((x - x1) * scale)` and decoded points `(i + 0.5) * corr + x1` as the reference rounds them.
 FILE_FLAGS = {"semseg_ops.hip": ["-fno-slp-vectorize"], "voc_eval.hip": ["-ffp-contract=off"],
+              "keypoint.hip": ["-ffp-contract=off"],
               "coco_eval.hip": ["-ffp-contract=off"], "cmil.hip": ["-ffp-contract=off"],
               "rotated_boxes.hip": ["-ffp-contract=off"], "deform_conv.hip": ["-ffp-contract=off"]}
 

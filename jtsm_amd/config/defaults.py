@@ -12,7 +12,7 @@ _DEFAULTS = {
     "INPUT": {"FORMAT": "BGR", "MASK_FORMAT": "polygon", "MIN_SIZE_TRAIN": (800,), "MIN_SIZE_TRAIN_SAMPLING": "choice",
               "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333},
     "DATASETS": {"PRECOMPUTED_PROPOSAL_TOPK_TRAIN": 2000, "PRECOMPUTED_PROPOSAL_TOPK_TEST": 1000},
-    "TEST": {"DETECTIONS_PER_IMAGE": 100,
+    "TEST": {"DETECTIONS_PER_IMAGE": 100, "KEYPOINT_OKS_SIGMAS": [],
              "AUG": {"ENABLED": False, "MIN_SIZES": (400, 500, 600, 700, 800, 900, 1000, 1100, 1200), "MAX_SIZE": 4000,
                      "FLIP": True}},
     "SOLVER": {"MAX_ITER": 40000, "BASE_LR": 0.001, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.0001,
@@ -48,6 +48,12 @@ _DEFAULTS = {
         "ROI_MASK_HEAD": {"NAME": "MaskRCNNConvUpsampleHead", "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0,
                           "NUM_CONV": 0, "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_MASK": False,
                           "POOLER_TYPE": "ROIAlignV2"},
+        # detectron2/config/defaults.py:347-377 (and :584, TEST.KEYPOINT_OKS_SIGMAS)
+        "ROI_KEYPOINT_HEAD": {"NAME": "KRCNNConvDeconvUpsampleHead", "POOLER_RESOLUTION": 14,
+                              "POOLER_SAMPLING_RATIO": 0, "POOLER_TYPE": "ROIAlignV2",
+                              "CONV_DIMS": (512, 512, 512, 512, 512, 512, 512, 512), "NUM_KEYPOINTS": 17,
+                              "MIN_KEYPOINTS_PER_IMAGE": 1, "NORMALIZE_LOSS_BY_VISIBLE_KEYPOINTS": True,
+                              "LOSS_WEIGHT": 1.0},
         "SEM_SEG_HEAD": {"NAME": "SemSegFPNHead", "IN_FEATURES": ["p2", "p3", "p4", "p5"], "IGNORE_VALUE": 255,
                          "NUM_CLASSES": 54, "CONVS_DIM": 128, "COMMON_STRIDE": 4, "NORM": "GN", "LOSS_WEIGHT": 1.0},
         # detectron2/config/defaults.py:398-406 (combine_semantic_and_instance_outputs thresholds)

@@ -53,6 +53,35 @@ def unique_boxes(boxes: torch.Tensor, scale=1.0):
     return np.sort(index)
 
 
+def create_keypoint_hflip_indices(keypoint_names, keypoint_flip_map):
+    """int32 (K,): for every keypoint the index of its opposite-handed counterpart, itself where it has none
+    (detectron2/data/detection_utils.py:490-509, which reads the two lists from the dataset's metadata; this package
+    has no dataset catalog, so they are passed in: e.g. COCO's 17 names and its (left_x, right_x) pairs)."""
+    names = list(keypoint_names)
+    flip_map = dict(keypoint_flip_map)
+    flip_map.update({v: k for k, v in list(flip_map.items())})
+    return np.asarray([names.index(flip_map.get(n, n)) for n in names], dtype=np.int32)
+
+
+def transform_keypoint_annotations(keypoints, transforms, image_size, keypoint_hflip_indices=None):
+    """One instance's (K, 3) = x, y, visibility through the image's transforms (detectron2/data/
+    detection_utils.py:324-363): a point that leaves the (h, w) image becomes unlabelled (v = 0, and then x = y = 0 as
+    COCO has it); under an odd number of horizontal flips left and right keypoints swap by `keypoint_hflip_indices`."""
+    from .transforms import HFlipTransform
+
+    keypoints = np.asarray(keypoints, dtype="float64").reshape(-1, 3).copy()
+    keypoints_xy = transforms.apply_coords(keypoints[:, :2].copy())
+    inside = ((keypoints_xy >= np.array([0, 0])) & (keypoints_xy <= np.array(image_size[::-1]))).all(axis=1)
+    keypoints[:, :2] = keypoints_xy
+    keypoints[:, 2][~inside] = 0
+    parts = getattr(transforms, "transforms", [transforms])
+    if sum(isinstance(t, HFlipTransform) for t in parts) % 2 == 1:
+        assert keypoint_hflip_indices is not None
+        keypoints = keypoints[np.asarray(keypoint_hflip_indices), :]
+    keypoints[keypoints[:, 2] == 0] = 0
+    return keypoints
+
+
 def transform_proposals_seg(dataset_dict, image_shape, transforms, *, proposal_topk, min_box_size=0):
     """In place: `proposal_file` -> `proposals` (Instances: proposal_boxes, objectness_logits, oh_labels) and
     `superpixels` (H, W) int32, both in the transformed image's frame."""

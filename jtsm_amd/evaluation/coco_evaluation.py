@@ -6,7 +6,7 @@ detection on the device; evaluate() concatenates the records, makes one more cal
 precision / recall tables), reads the tables back once per task and summarises them with NumPy as pycocotools'
 _summarize does.  Semantics: DESIGN.md §4g.
 
-Not reproduced: keypoints, _eval_box_proposals (AR of proposals), comm.gather across ranks (one rank's images only), the
+Not reproduced: the keypoints task (OKS; the model side exists), _eval_box_proposals (AR of proposals), comm.gather across ranks (one rank's images only), the
 JSON / .pth dumps, LVIS, polygon rasterisation (ground-truth masks are bitmasks).  The AR lines of the summary are kept
 in `last_eval[task]["stats"]`; the reference does not report them either."""
 import json

@@ -17,6 +17,9 @@ def detector_postprocess(results: Instances, output_height: int, output_width: i
     if field is None:
         raise AssertionError("Predictions must contain boxes!")
     boxes = out.get(field)
+    if out.has("pred_keypoints"):     # x, y by the boxes' factors (postprocessing.py:70-72); the score stays
+        out.pred_keypoints = out.pred_keypoints * out.pred_keypoints.new_tensor(
+            [output_width / in_w, output_height / in_h, 1.0])
     boxes.scale(output_width / in_w, output_height / in_h)
     boxes.clip(out.image_size)
     out = out[boxes.nonempty()]

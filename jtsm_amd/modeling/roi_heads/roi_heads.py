@@ -27,6 +27,24 @@ def select_foreground_proposals(proposals: List[Instances], bg_label: int):
     return fg_proposals, fg_selection_masks
 
 
+def select_proposals_with_visible_keypoints(proposals: List[Instances]):
+    """detectron2/modeling/roi_heads/roi_heads.py:77-121: keep the proposals whose matched instance has at least one
+    labelled keypoint (v >= 1) inside the proposal box, edges included; the others would add nothing to the loss."""
+    ret = []
+    for proposals_per_image in proposals:
+        if len(proposals_per_image) == 0 or not proposals_per_image.has("gt_keypoints"):
+            ret.append(proposals_per_image)
+            continue
+        gt_keypoints = proposals_per_image.gt_keypoints.tensor
+        vis_mask = gt_keypoints[:, :, 2] >= 1
+        xs, ys = gt_keypoints[:, :, 0], gt_keypoints[:, :, 1]
+        box = proposals_per_image.proposal_boxes.tensor.unsqueeze(dim=1)     # (#proposals, 1, 4)
+        kp_in_box = (xs >= box[:, :, 0]) & (xs <= box[:, :, 2]) & (ys >= box[:, :, 1]) & (ys <= box[:, :, 3])
+        selection = (kp_in_box & vis_mask).any(dim=1)
+        ret.append(proposals_per_image[selection.nonzero().squeeze(1)])
+    return ret
+
+
 @torch.no_grad()
 def get_image_level_gt(targets, num_classes):
     """Per image: sorted unique thing classes (float/int64 copies) and their one-hot (B,num_classes)."""
@@ -139,6 +157,16 @@ class StandardROIHeads(torch.nn.Module):
                                          sampling_ratio=m.POOLER_SAMPLING_RATIO, pooler_type=m.POOLER_TYPE)
             self.mask_head = build_mask_head(cfg, ShapeSpec(channels=c, width=m.POOLER_RESOLUTION,
                                                             height=m.POOLER_RESOLUTION))
+        self.keypoint_on = cfg.MODEL.KEYPOINT_ON
+        if self.keypoint_on:
+            # detectron2/modeling/roi_heads/roi_heads.py:669-697 (_init_keypoint_head); imported only here, so a model
+            # without keypoints never loads the keypoint modules
+            from .keypoint_head import build_keypoint_head
+            k = cfg.MODEL.ROI_KEYPOINT_HEAD
+            self.keypoint_pooler = ROIPooler(output_size=k.POOLER_RESOLUTION, scales=scales,
+                                             sampling_ratio=k.POOLER_SAMPLING_RATIO, pooler_type=k.POOLER_TYPE)
+            self.keypoint_head = build_keypoint_head(cfg, ShapeSpec(channels=c, width=k.POOLER_RESOLUTION,
+                                                                    height=k.POOLER_RESOLUTION))
 
     def _box_predictor(self, cfg, input_shape):
         from .fast_rcnn import FastRCNNOutputLayers
@@ -181,6 +209,8 @@ class StandardROIHeads(torch.nn.Module):
             losses = self._forward_box(features, proposals)
             if self.mask_on:
                 losses.update(self._forward_mask(features, proposals, targets))
+            if self.keypoint_on:
+                losses.update(self._forward_keypoint(features, proposals))
             return proposals, losses
         pred = self._forward_box(features, proposals)
         return self.forward_with_given_boxes(features, pred), {}
@@ -200,7 +230,22 @@ class StandardROIHeads(torch.nn.Module):
             feats = [features[f] for f in self.in_features]
             x = self.mask_pooler(feats, [i.pred_boxes for i in instances])
             mask_rcnn_inference(self.mask_head.layers(x)[0], instances)
+        if self.keypoint_on:
+            instances = self._forward_keypoint(features, instances)
         return instances
+
+    def _forward_keypoint(self, features, instances):
+        """detectron2/modeling/roi_heads/roi_heads.py:839-875.  Training: the foreground rois whose matched instance
+        has a labelled keypoint inside the roi -> {"loss_keypoint"}; inference: `pred_keypoints` and
+        `pred_keypoint_heatmaps` added to the detections."""
+        feats = [features[f] for f in self.in_features]
+        if self.training:
+            instances, _ = select_foreground_proposals(instances, self.num_classes)
+            instances = select_proposals_with_visible_keypoints(instances)
+            boxes = [x.proposal_boxes for x in instances]
+        else:
+            boxes = [x.pred_boxes for x in instances]
+        return self.keypoint_head(self.keypoint_pooler(feats, boxes), instances)
 
     def _forward_mask(self, features, proposals, targets):
         """Foreground rois only; the target of a roi is its matched instance's bitmask cropped to the roi at

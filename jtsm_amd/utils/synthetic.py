@@ -10,19 +10,24 @@ recipe scaled by width / size in x.  `cluster` > 0 replaces that fraction of the
 around regions: a mined pseudo-GT box that is one of those copies has O(cluster * R / objects) proposals above IoU 0.5,
 which is what gives the mask branch a realistic foreground count (uniform-random boxes almost never overlap that
 much).  With cluster = 1 every proposal belongs to a group, so the count no longer depends on WHICH proposal a
-randomly initialised detector happens to pick."""
+randomly initialised detector happens to pick.
+
+`keypoints` = K (default None: nothing added) gives every instance a ground-truth box (`gt_boxes`) and `gt_keypoints`
+(K points, x, y, v) inside it: most labelled (v = 1 or 2), every fourth not labelled (v = 0, x = y = 0), some exactly
+on the box's right or bottom edge — the cases Keypoints.to_heatmap treats apart."""
 import math
 
 import torch
 
-from ..structures import Boxes, Instances
+from ..structures import Boxes, Instances, Keypoints
 
 NUM_THINGS, NUM_STUFF = 80, 54
 
 
 def synthetic_inputs(seed, batch=2, size=1024, proposals=2000, sp_block=32, n_things=3, n_stuff=2, device="cpu",
-                     num_things=NUM_THINGS, num_stuff=NUM_STUFF, width=None, cluster=0.0, objects=None):
+                     num_things=NUM_THINGS, num_stuff=NUM_STUFF, width=None, cluster=0.0, objects=None, keypoints=None):
     g = torch.Generator().manual_seed(seed)
+    gk = torch.Generator().manual_seed(seed + 7919)
     width = size if width is None else width
     sx = width / float(size)
     gh, gw = size // sp_block, width // sp_block
@@ -69,9 +74,28 @@ def synthetic_inputs(seed, batch=2, size=1024, proposals=2000, sp_block=32, n_th
         for j, s in enumerate(stuff):
             sem[(j + 1) * band:(j + 2) * band] = s
         sem[:8] = 255
+        instances = Instances((size, width), gt_classes=things.to(device))
+        if keypoints is not None:
+            # (drawn from a generator of their own: every other tensor is the plain recipe's, bit for bit)
+            n = len(things)
+            bx = torch.rand(n, generator=gk) * width * 0.5
+            by = torch.rand(n, generator=gk) * size * 0.5
+            bw = (torch.rand(n, generator=gk) * 0.3 + 0.15) * width
+            bh = (torch.rand(n, generator=gk) * 0.3 + 0.15) * size
+            gt = torch.stack([bx, by, bx + bw, by + bh], 1)
+            kp = torch.rand(n, keypoints, 3, generator=gk)
+            kp[:, :, 0] = gt[:, None, 0] + kp[:, :, 0] * bw[:, None]
+            kp[:, :, 1] = gt[:, None, 1] + kp[:, :, 1] * bh[:, None]
+            kp[:, :, 2] = (kp[:, :, 2] * 2).floor() + 1                # labelled: v = 1 or 2
+            which = torch.arange(n)[:, None] + torch.arange(keypoints)[None, :]
+            kp[:, :, 0] = torch.where(which % 5 == 1, gt[:, None, 2].expand(n, keypoints), kp[:, :, 0])   # right edge
+            kp[:, :, 1] = torch.where(which % 5 == 2, gt[:, None, 3].expand(n, keypoints), kp[:, :, 1])   # bottom edge
+            kp[which % 4 == 3] = 0                                     # not labelled: v = 0 and x = y = 0
+            instances.gt_boxes = Boxes(gt.to(device))
+            instances.gt_keypoints = Keypoints(kp.to(device))
         d = {
             "image": image.to(device),
-            "instances": Instances((size, width), gt_classes=things.to(device)),
+            "instances": instances,
             "sem_seg": sem.to(device),
             "superpixels": ids.to(device),
             "proposals": Instances((size, width), proposal_boxes=Boxes(boxes.to(device)),
