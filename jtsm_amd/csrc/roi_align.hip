@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "roi_geometry.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
@@ -54,7 +55,81 @@ __device__ __forceinline__ void store_vec(T* p, const T (&v)[VEC]) {
   *reinterpret_cast<V*>(p) = x;
 }
 
+// ---------------------------------------------------------------- the sample walk of a (roi, bin) wavefront
+// Lane s computes sample s of the bin's gh x gw grid; the samples are then replayed in (iy, ix) order, the owner's taps
+// broadcast to the whole wavefront, and body(p, w) gets the four tap positions and weights of every sample inside the
+// map (a sample outside has p[0] < 0: wave-uniform, skipped by all lanes together).
+template <typename T, bool ROT, class F>
+__device__ __forceinline__ void for_each_sample(const RoiGeom<T>& g, int H, int W, int ph, int pw, int lane, F body) {
+#pragma clang fp contract(off)
+  const int S = (g.gh > 0 && g.gw > 0) ? g.gh * g.gw : 0;
+  for (int s0 = 0; s0 < S; s0 += 64) {
+    const int s = s0 + lane;
+    Tap<T> mine;
+    if (s < S) {
+      const int iy = s / g.gw;
+      mine = sample_tap<T, ROT>(g, H, W, ph, pw, iy, s - iy * g.gw);
+    } else {
+      mine.pos[0] = mine.pos[1] = mine.pos[2] = mine.pos[3] = -1;
+      mine.w[0] = mine.w[1] = mine.w[2] = mine.w[3] = (T)0;
+    }
+    const int cnt = (S - s0) < 64 ? (S - s0) : 64;
+    for (int j = 0; j < cnt; ++j) {
+      const int p0 = __shfl(mine.pos[0], j);
+      if (p0 < 0) continue;
+      const int p[4] = {p0, __shfl(mine.pos[1], j), __shfl(mine.pos[2], j), __shfl(mine.pos[3], j)};
+      const T w[4] = {__shfl(mine.w[0], j), __shfl(mine.w[1], j), __shfl(mine.w[2], j), __shfl(mine.w[3], j)};
+      body(p, w);
+    }
+  }
+}
+
+// The wavefront index of the (roi, bin) kernels below, four wavefronts to a workgroup.
+// (readfirstlane: the wavefront index is uniform, but the compiler cannot see that through threadIdx — with it
+// the roi / bin / address arithmetic of the kernel runs on the scalar unit instead of once per lane)
+__device__ __forceinline__ long wave_index() {
+  return (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+
 // ---------------------------------------------------------------- NHWC forward
+// One (roi, bin) of the forward.  The walk is re-run for every 64 * VEC channels (it stays inside the channel loop:
+// hoisting it changes the registers and the speed); the sum is divided by max(gh * gw, 1) as the reference does.
+template <typename T, int VEC, bool ROT>
+__device__ __forceinline__ void align_pool_wave(const T* __restrict__ in, const T* __restrict__ rois, T* __restrict__ out,
+                                                int C, int H, int W, T scale, int PH, int PW, int sr, int aligned, int n,
+                                                int bin, int lane) {
+#pragma clang fp contract(off)
+  const int nbins = PH * PW;
+  const int ph = bin / PW, pw = bin - ph * PW;
+  const RoiGeom<T> g = roi_geometry<T, ROT>(rois, n, scale, PH, PW, sr, aligned != 0);
+  const int cells = g.gh * g.gw;
+  const T count = (T)(cells > 1 ? cells : 1);
+  const T* __restrict__ plane = in + (size_t)g.b * H * W * C;
+  T* __restrict__ orow = out + ((size_t)n * nbins + bin) * C;
+  for (int cb = 0; cb < C; cb += 64 * VEC) {
+    const int c = cb + lane * VEC;
+    const bool live = c < C;
+    T acc[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = (T)0;
+    for_each_sample<T, ROT>(g, H, W, ph, pw, lane, [&](const int (&p)[4], const T (&w)[4]) {
+      if (!live) return;
+      T a[VEC], b[VEC], d[VEC], e[VEC];
+      load_vec<T, VEC>(plane + (size_t)p[0] * C + c, a);
+      load_vec<T, VEC>(plane + (size_t)p[1] * C + c, b);
+      load_vec<T, VEC>(plane + (size_t)p[2] * C + c, d);
+      load_vec<T, VEC>(plane + (size_t)p[3] * C + c, e);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) acc[v] += w[0] * a[v] + w[1] * b[v] + w[2] * d[v] + w[3] * e[v];
+    });
+    if (live) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) acc[v] /= count;
+      store_vec<T, VEC>(orow + c, acc);
+    }
+  }
+}
+
 template <typename T, int VEC, bool ROT>
 __global__ __launch_bounds__(256) void align_fwd_nhwc(const T* __restrict__ in,
                                                       const T* __restrict__ rois,
@@ -62,66 +137,13 @@ __global__ __launch_bounds__(256) void align_fwd_nhwc(const T* __restrict__ in,
                                                       int M, T scale, int PH, int PW, int sr,
                                                       int aligned,
                                                       const int* __restrict__ roi_level, int level) {
-#pragma clang fp contract(off)
-  const int lane = threadIdx.x & 63;
   const int nbins = PH * PW;
-  // (readfirstlane: the wavefront index is uniform, but the compiler cannot see that through threadIdx — with it
-  // the roi / bin / address arithmetic below runs on the scalar unit instead of once per lane)
-  const long wave = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long wave = wave_index();
   if (wave >= (long)M * nbins) return;
-  if (roi_level && roi_level[wave / nbins] != level) return;  // FPN: this roi lives on another level  // whole wave leaves together
+  if (roi_level && roi_level[wave / nbins] != level) return;  // FPN: this roi lives on another level (whole wave leaves)
   const int n = (int)(wave / nbins);
-  const int bin = (int)(wave - (long)n * nbins);
-  const int ph = bin / PW, pw = bin - ph * PW;
-
-  const RoiGeom<T> g = roi_geometry<T, ROT>(rois, n, scale, PH, PW, sr, aligned != 0);
-  const int S = (g.gh > 0 && g.gw > 0) ? g.gh * g.gw : 0;
-  const int cells = g.gh * g.gw;
-  const T count = (T)(cells > 1 ? cells : 1);
-  const T* __restrict__ plane = in + (size_t)g.b * H * W * C;
-  T* __restrict__ orow = out + ((size_t)n * nbins + bin) * C;
-
-  for (int cb = 0; cb < C; cb += 64 * VEC) {
-    const int c = cb + lane * VEC;
-    const bool live = c < C;
-    T acc[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[v] = (T)0;
-    for (int s0 = 0; s0 < S; s0 += 64) {
-      const int s = s0 + lane;
-      Tap<T> mine;
-      if (s < S) {
-        const int iy = s / g.gw;
-        mine = sample_tap<T, ROT>(g, H, W, ph, pw, iy, s - iy * g.gw);
-      } else {
-        mine.pos[0] = mine.pos[1] = mine.pos[2] = mine.pos[3] = -1;
-        mine.w[0] = mine.w[1] = mine.w[2] = mine.w[3] = (T)0;
-      }
-      const int cnt = (S - s0) < 64 ? (S - s0) : 64;
-      for (int j = 0; j < cnt; ++j) {
-        const int p0 = __shfl(mine.pos[0], j);
-        if (p0 < 0) continue;  // wave-uniform: the sample lies outside the map
-        const int p1 = __shfl(mine.pos[1], j), p2 = __shfl(mine.pos[2], j),
-                  p3 = __shfl(mine.pos[3], j);
-        const T w0 = __shfl(mine.w[0], j), w1 = __shfl(mine.w[1], j),
-                w2 = __shfl(mine.w[2], j), w3 = __shfl(mine.w[3], j);
-        if (live) {
-          T a[VEC], b[VEC], d[VEC], e[VEC];
-          load_vec<T, VEC>(plane + (size_t)p0 * C + c, a);
-          load_vec<T, VEC>(plane + (size_t)p1 * C + c, b);
-          load_vec<T, VEC>(plane + (size_t)p2 * C + c, d);
-          load_vec<T, VEC>(plane + (size_t)p3 * C + c, e);
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) acc[v] += w0 * a[v] + w1 * b[v] + w2 * d[v] + w3 * e[v];
-        }
-      }
-    }
-    if (live) {
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) acc[v] /= count;
-      store_vec<T, VEC>(orow + c, acc);
-    }
-  }
+  align_pool_wave<T, VEC, ROT>(in, rois, out, C, H, W, scale, PH, PW, sr, aligned, n, (int)(wave - (long)n * nbins),
+                               threadIdx.x & 63);
 }
 
 // The maps of the call: one level (jtsm_roi_align_backward_level_f32 / the plain entry) or all FPN levels at once
@@ -139,6 +161,37 @@ struct AlignLevels {
 };
 
 // ---------------------------------------------------------------- NHWC backward
+// One (roi, bin) of the scatter backward: divided by gh * gw, inside every atomic's operand, as the reference does.
+template <typename T, int VEC, bool ROT>
+__device__ __forceinline__ void align_scatter_wave(const T* __restrict__ grad, const T* __restrict__ rois,
+                                                   T* __restrict__ gin, int C, int H, int W, T scale, int PH, int PW,
+                                                   int sr, int aligned, int n, int bin, int lane) {
+#pragma clang fp contract(off)
+  const int nbins = PH * PW;
+  const int ph = bin / PW, pw = bin - ph * PW;
+  const RoiGeom<T> g = roi_geometry<T, ROT>(rois, n, scale, PH, PW, sr, aligned != 0);
+  const T count = (T)(g.gh * g.gw);
+  T* __restrict__ plane = gin + (size_t)g.b * H * W * C;
+  const T* __restrict__ grow = grad + ((size_t)n * nbins + bin) * C;
+  for (int cb = 0; cb < C; cb += 64 * VEC) {
+    const int c = cb + lane * VEC;
+    const bool live = c < C;
+    T go[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) go[v] = (T)0;
+    if (live) load_vec<T, VEC>(grow + c, go);
+    for_each_sample<T, ROT>(g, H, W, ph, pw, lane, [&](const int (&p)[4], const T (&w)[4]) {
+      if (!live) return;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        T* dst = plane + (size_t)p[q] * C + c;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) atomicAdd(dst + v, go[v] * w[q] / count);
+      }
+    });
+  }
+}
+
 template <typename T, int VEC, bool ROT>
 __global__ __launch_bounds__(256) void align_bwd_nhwc(const T* __restrict__ grad,
                                                       const T* __restrict__ rois,
@@ -147,60 +200,14 @@ __global__ __launch_bounds__(256) void align_bwd_nhwc(const T* __restrict__ grad
                                                       int aligned,
                                                       const int* __restrict__ roi_level, int level,
                                                       const int* __restrict__ census_max, int census_limit) {
-#pragma clang fp contract(off)
-  if (census_max && *census_max <= census_limit) return;   // the gather form (align_bwd_tiled) took this call
-  const int lane = threadIdx.x & 63;
+  if (census_max && *census_max <= census_limit) return;   // the gather form (align_bwd_gather) took this call
   const int nbins = PH * PW;
-  // (readfirstlane: the wavefront index is uniform, but the compiler cannot see that through threadIdx — with it
-  // the roi / bin / address arithmetic below runs on the scalar unit instead of once per lane)
-  const long wave = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long wave = wave_index();
   if (wave >= (long)M * nbins) return;
   if (roi_level && roi_level[wave / nbins] != level) return;  // FPN: this roi lives on another level
   const int n = (int)(wave / nbins);
-  const int bin = (int)(wave - (long)n * nbins);
-  const int ph = bin / PW, pw = bin - ph * PW;
-
-  const RoiGeom<T> g = roi_geometry<T, ROT>(rois, n, scale, PH, PW, sr, aligned != 0);
-  const int S = (g.gh > 0 && g.gw > 0) ? g.gh * g.gw : 0;
-  const T count = (T)(g.gh * g.gw);
-  T* __restrict__ plane = gin + (size_t)g.b * H * W * C;
-  const T* __restrict__ grow = grad + ((size_t)n * nbins + bin) * C;
-
-  for (int cb = 0; cb < C; cb += 64 * VEC) {
-    const int c = cb + lane * VEC;
-    const bool live = c < C;
-    T go[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) go[v] = (T)0;
-    if (live) load_vec<T, VEC>(grow + c, go);
-    for (int s0 = 0; s0 < S; s0 += 64) {
-      const int s = s0 + lane;
-      Tap<T> mine;
-      if (s < S) {
-        const int iy = s / g.gw;
-        mine = sample_tap<T, ROT>(g, H, W, ph, pw, iy, s - iy * g.gw);
-      } else {
-        mine.pos[0] = mine.pos[1] = mine.pos[2] = mine.pos[3] = -1;
-        mine.w[0] = mine.w[1] = mine.w[2] = mine.w[3] = (T)0;
-      }
-      const int cnt = (S - s0) < 64 ? (S - s0) : 64;
-      for (int j = 0; j < cnt; ++j) {
-        const int p0 = __shfl(mine.pos[0], j);
-        if (p0 < 0) continue;
-        int p[4] = {p0, __shfl(mine.pos[1], j), __shfl(mine.pos[2], j), __shfl(mine.pos[3], j)};
-        T w[4] = {__shfl(mine.w[0], j), __shfl(mine.w[1], j), __shfl(mine.w[2], j),
-                  __shfl(mine.w[3], j)};
-        if (live) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            T* dst = plane + (size_t)p[q] * C + c;
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) atomicAdd(dst + v, go[v] * w[q] / count);
-          }
-        }
-      }
-    }
-  }
+  align_scatter_wave<T, VEC, ROT>(grad, rois, gin, C, H, W, scale, PH, PW, sr, aligned, n,
+                                  (int)(wave - (long)n * nbins), threadIdx.x & 63);
 }
 
 // The scatter form over a level table in ONE launch (the census fallback of the gather form below: before, one launch
@@ -211,11 +218,9 @@ __global__ __launch_bounds__(256) void align_bwd_nhwc_levels(const float* __rest
                                                              const AlignLevels lv, int C, int M, int PH, int PW, int sr,
                                                              int aligned, const int* __restrict__ roi_level,
                                                              const int* __restrict__ census_max, int census_limit) {
-#pragma clang fp contract(off)
   if (census_max && *census_max <= census_limit) return;   // the gather form took this call
-  const int lane = threadIdx.x & 63;
   const int nbins = PH * PW;
-  const long wave = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long wave = wave_index();
   if (wave >= (long)M * nbins) return;
   const int n = (int)(wave / nbins);
   int l = 0;
@@ -224,56 +229,16 @@ __global__ __launch_bounds__(256) void align_bwd_nhwc_levels(const float* __rest
     for (l = 0; l < lv.n && lv.level_id[l] != id; ++l) {}
     if (l == lv.n) return;
   }
-  const int H = lv.H[l], W = lv.W[l];
-  const int bin = (int)(wave - (long)n * nbins);
-  const int ph = bin / PW, pw = bin - ph * PW;
-  const RoiGeom<float> g = roi_geometry<float, false>(rois, n, lv.scale[l], PH, PW, sr, aligned != 0);
-  const int S = (g.gh > 0 && g.gw > 0) ? g.gh * g.gw : 0;
-  const float count = (float)(g.gh * g.gw);
-  float* __restrict__ plane = lv.gin[l] + (size_t)g.b * H * W * C;
-  const float* __restrict__ grow = grad + ((size_t)n * nbins + bin) * C;
-  for (int cb = 0; cb < C; cb += 64 * VEC) {
-    const int c = cb + lane * VEC;
-    const bool live = c < C;
-    float go[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) go[v] = 0.f;
-    if (live) load_vec<float, VEC>(grow + c, go);
-    for (int s0 = 0; s0 < S; s0 += 64) {
-      const int s = s0 + lane;
-      Tap<float> mine;
-      if (s < S) {
-        const int iy = s / g.gw;
-        mine = sample_tap<float, false>(g, H, W, ph, pw, iy, s - iy * g.gw);
-      } else {
-        mine.pos[0] = mine.pos[1] = mine.pos[2] = mine.pos[3] = -1;
-        mine.w[0] = mine.w[1] = mine.w[2] = mine.w[3] = 0.f;
-      }
-      const int cnt = (S - s0) < 64 ? (S - s0) : 64;
-      for (int j = 0; j < cnt; ++j) {
-        const int p0 = __shfl(mine.pos[0], j);
-        if (p0 < 0) continue;
-        int p[4] = {p0, __shfl(mine.pos[1], j), __shfl(mine.pos[2], j), __shfl(mine.pos[3], j)};
-        float w[4] = {__shfl(mine.w[0], j), __shfl(mine.w[1], j), __shfl(mine.w[2], j), __shfl(mine.w[3], j)};
-        if (live) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float* dst = plane + (size_t)p[q] * C + c;
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) atomicAdd(dst + v, go[v] * w[q] / count);
-          }
-        }
-      }
-    }
-  }
+  align_scatter_wave<float, VEC, false>(grad, rois, lv.gin[l], C, lv.H[l], lv.W[l], lv.scale[l], PH, PW, sr, aligned, n,
+                                        (int)(wave - (long)n * nbins), threadIdx.x & 63);
 }
 
 // ---------------------------------------------------------------- NHWC backward as a gather
 // A workgroup owns an 8 x 8-cell tile of the gradient map x 64 channels, lists — from the roi geometry alone, in
 // (roi, bin) order — the bins whose bilinear taps can reach the tile, and adds their contributions in LDS.  The bin's
 // samples form a gh x gw grid and a sample's four weights are (hy | ly) x (hx | lx), so the sum over the grid
-// factorises into eight row weights times eight column weights of the tile (make_tap's clamping and out-of-range
-// rules, roi_geometry.h, are per axis too).  The four wavefronts take the listed bins round-robin, each into its OWN
+// factorises into eight row weights times eight column weights of the tile (the clamping and out-of-range rules are
+// per axis too: axis_outside / axis_tap in roi_geometry.h, which make_tap is built from).  The four wavefronts take the listed bins round-robin, each into its OWN
 // 64-cell x 64-channel accumulator (lane = channel), and the four are summed in a fixed order at the end: no
 // atomics, reproducible bit for bit, every map cell written exactly once (no zero fill).  2-5x faster than the scatter
 // form above on spread-out rois; a tile under a pile of rois is walked by one workgroup, so a census of the boxes
@@ -345,26 +310,23 @@ constexpr int kSubsets = 4;     // wavefronts that share a channel block's work 
 // workgroup walking roi after roi, 2-3 dependent load round trips each.  Measured and NOT kept: a 16-wavefront form for
 // the tiles under piles (4 x 4-cell quadrants x 256 channels, items over four wavefronts per channel block): the same
 // time as this form on the piled workload — its per-job listing and staging cost what the wider walk saved.
-template <int TILE, int NBLK>
-__global__ __launch_bounds__(256 * NBLK) void align_bwd_gather(
+__global__ __launch_bounds__(256) void align_bwd_gather(
     const float* __restrict__ grad, const float* __restrict__ rois, const AlignLevels lv, int C, int M, int PH, int PW,
     int sr, int aligned, const int* __restrict__ plan, int census_lim, int fan, const int4* __restrict__ reach_in,
     const int* __restrict__ meta_in, int accumulate) {
 #pragma clang fp contract(off)
   __shared__ int roi_list[256];
   __shared__ float roi_row[256][5];
-  constexpr int NW = 4 * NBLK, NT = 256 * NBLK, NCH = 64 * NBLK;
-  __shared__ int wave_count[NW];
-  __shared__ __attribute__((aligned(16))) float wts[kSub][2][kMaxBins][TILE];     // [roi][axis y|x][slot][line]
-  __shared__ __attribute__((aligned(16))) float copies[2][TILE * TILE][NCH];       // 32 KiB: two slots of the final sums
+  __shared__ int wave_count[kSubsets];
+  __shared__ __attribute__((aligned(16))) float wts[kSub][2][kMaxBins][kTile];    // [roi][axis y|x][slot][line]
+  __shared__ __attribute__((aligned(16))) float copies[2][kTile * kTile][64];      // 32 KiB: two slots of the final sums
   __shared__ int first_bin[kSub][2], nbin[kSub][2];
   __shared__ float inv_cnt[kSub];
   __shared__ unsigned char row_lo[kSub][kMaxBins], row_hi[kSub][kMaxBins];   // tile lines with a non-zero y weight
   __shared__ int item_base[kSub + 1];
   __shared__ unsigned short items[kSub * kMaxBins];                         // roi slot << 8 | bin-row slot
   if (plan[0] > census_lim) return;   // piled-up rois beyond what one workgroup should walk: the scatter form
-  const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int cblk = wv % NBLK, subset = wv / NBLK;
+  const int t = threadIdx.x, lane = t & 63, subset = __builtin_amdgcn_readfirstlane(t >> 6);
   const int nbins = PH * PW;
   const int njobs = plan[1];
 
@@ -384,28 +346,26 @@ __global__ __launch_bounds__(256 * NBLK) void align_bwd_gather(
     const int tx = rel % tiles_x; rel /= tiles_x;
     const int ty = rel % tiles_y;
     const int b = rel / tiles_y;
-    const int x0 = tx * TILE, y0 = ty * TILE, x1 = min(x0 + TILE, W) - 1, y1 = min(y0 + TILE, H) - 1;
+    const int x0 = tx * kTile, y0 = ty * kTile, x1 = min(x0 + kTile, W) - 1, y1 = min(y0 + kTile, H) - 1;
     float* __restrict__ out = lv.gin[lvl] + (size_t)b * H * W * C;
     {
-      const int cb0 = group * NCH;
-      const int nblk = min(NBLK, (C - cb0) >> 6);   // channel blocks present: wavefronts beyond them only keep step
-      const bool serving = cblk < nblk;
-      const int c = cb0 + cblk * 64 + lane;
-      float acc[TILE][TILE];
+      const int cb0 = group * 64;   // the job's 64 channels (C is a multiple of 64)
+      const int c = cb0 + lane;
+      float acc[kTile][kTile];
 #pragma unroll
-      for (int r = 0; r < TILE; ++r)
+      for (int r = 0; r < kTile; ++r)
 #pragma unroll
-        for (int q = 0; q < TILE; ++q) acc[r][q] = 0.f;
+        for (int q = 0; q < kTile; ++q) acc[r][q] = 0.f;
 
       for (int base = 0; base < M; base += 256) {
         const int n = base + t;
         bool hit = false;
-        if (t < 256 && n < M && meta_in[n] == (b | (lvl << 16))) {   // this level, this image, a box with samples
+        if (n < M && meta_in[n] == (b | (lvl << 16))) {   // this level, this image, a box with samples
           const int4 rc = reach_in[n];                               // (ya, yz, xa, xz)
           hit = rc.x <= y1 && rc.y >= y0 && rc.z <= x1 && rc.w >= x0;
         }
         int nroi;
-        const int slot = compact_wg<NW>(hit, wave_count, nroi);
+        const int slot = compact_wg<kSubsets>(hit, wave_count, nroi);
         if (hit) {
           roi_list[slot] = n;
 #pragma unroll
@@ -434,29 +394,26 @@ __global__ __launch_bounds__(256 * NBLK) void align_bwd_gather(
             if (axis == 0) inv_cnt[i] = 1.f / (float)(g.gh * g.gw);
           }
           __syncthreads();
-          for (int task = t; task < ns * 2 * kMaxBins; task += NT) {   // one (roi, axis, bin slot) per thread
+          for (int task = t; task < ns * 2 * kMaxBins; task += 256) {   // one (roi, axis, bin slot) per thread
             const int i = task / (2 * kMaxBins), axis = (task / kMaxBins) & 1, sl = task % kMaxBins;
             if (sl >= nbin[i][axis]) continue;
             const RoiGeom<float> g = geom_box<float>(roi_row[sub + i], scale, PH, PW, sr, aligned != 0);
             const float origin = axis ? g.x0 : g.y0, bin = axis ? g.bw : g.bh;
             const int grid = axis ? g.gw : g.gh, n_lines = axis ? W : H, t0 = axis ? x0 : y0;
             const int p = first_bin[i][axis] + sl;
-            float w[TILE];
+            float w[kTile];
 #pragma unroll
-            for (int r = 0; r < TILE; ++r) w[r] = 0.f;
-            for (int k = 0; k < grid; ++k) {
-              float y = origin + (float)p * bin + (float)((float)k + .5f) * bin / (float)grid;
-              if (y < -1.0f || y > (float)n_lines) continue;
-              if (y <= 0.f) y = 0.f;
-              int yl = (int)y, yh;
-              if (yl >= n_lines - 1) { yh = yl = n_lines - 1; y = (float)yl; } else { yh = yl + 1; }
-              const float ly = y - (float)yl, hy = 1.f - ly;
+            for (int r = 0; r < kTile; ++r) w[r] = 0.f;
+            for (int k = 0; k < grid; ++k) {   // sample_tap's coordinate and make_tap's rule, one axis at a time
+              const float y = origin + (float)p * bin + (float)((float)k + .5f) * bin / (float)grid;
+              if (axis_outside(n_lines, y)) continue;
+              const AxisTap<float> a = axis_tap<float, false>(n_lines, y);
 #pragma unroll
-              for (int r = 0; r < TILE; ++r) w[r] += (yl == t0 + r ? hy : 0.f) + (yh == t0 + r ? ly : 0.f);
+              for (int r = 0; r < kTile; ++r) w[r] += (a.lo == t0 + r ? a.w_lo : 0.f) + (a.hi == t0 + r ? a.w_hi : 0.f);
             }
-            int lo = TILE, hi = -1;
+            int lo = kTile, hi = -1;
 #pragma unroll
-            for (int r = 0; r < TILE; ++r) {
+            for (int r = 0; r < kTile; ++r) {
               wts[i][axis][sl][r] = w[r];
               if (w[r] != 0.f) { lo = min(lo, r); hi = r; }
             }
@@ -475,15 +432,15 @@ __global__ __launch_bounds__(256 * NBLK) void align_bwd_gather(
             if (t == ns - 1) item_base[ns] = inc;
           }
           __syncthreads();
-          for (int task = t; task < ns * kMaxBins; task += NT) {
+          for (int task = t; task < ns * kMaxBins; task += 256) {
             const int i = task / kMaxBins, a = task % kMaxBins;
             if (nbin[i][1] > 0 && a < nbin[i][0]) items[item_base[i] + a] = (unsigned short)(i << 8 | a);
           }
           __syncthreads();
-          // ---- walk: this wavefront takes items subset, subset + 4, ... for its channel block; the next item's
-          // gradient row is requested before this one is applied
+          // ---- walk: this wavefront takes items subset, subset + 4, ...; the next item's gradient row is requested
+          // before this one is applied
           {
-            const int nitems = serving ? item_base[ns] : 0;
+            const int nitems = item_base[ns];
             float gk[kMaxBins], gnext[kMaxBins];
             auto request = [&](int j, float (&g)[kMaxBins]) {
               const int it = __builtin_amdgcn_readfirstlane((int)items[j]);
@@ -504,23 +461,23 @@ __global__ __launch_bounds__(256 * NBLK) void align_bwd_gather(
               const int i = it >> 8, a = it & 255;
               const int npw = __builtin_amdgcn_readfirstlane(nbin[i][1]);
               const float inv = inv_cnt[i];
-              float v[TILE];
+              float v[kTile];
 #pragma unroll
-              for (int q = 0; q < TILE; ++q) v[q] = 0.f;
+              for (int q = 0; q < kTile; ++q) v[q] = 0.f;
 #pragma unroll
               for (int k = 0; k < kMaxBins; ++k) {
                 if (k >= npw) break;
                 const float gs = gk[k] * inv;
 #pragma unroll
-                for (int q = 0; q < TILE; ++q) v[q] += gs * wts[i][1][k][q];
+                for (int q = 0; q < kTile; ++q) v[q] += gs * wts[i][1][k][q];
               }
               const int rlo = __builtin_amdgcn_readfirstlane((int)row_lo[i][a]), rhi = __builtin_amdgcn_readfirstlane((int)row_hi[i][a]);
 #pragma unroll
-              for (int r = 0; r < TILE; ++r) {
+              for (int r = 0; r < kTile; ++r) {
                 if (r < rlo || r >= rhi) continue;      // (scalar test: lines this bin row has no weight on)
                 const float wy = wts[i][0][a][r];
 #pragma unroll
-                for (int q = 0; q < TILE; ++q) acc[r][q] += wy * v[q];
+                for (int q = 0; q < kTile; ++q) acc[r][q] += wy * v[q];
               }
             }
           }
@@ -528,18 +485,18 @@ __global__ __launch_bounds__(256 * NBLK) void align_bwd_gather(
         }
         __syncthreads();                    // before the next chunk overwrites roi_list / roi_row
       }
-      // the four register copies of every channel block, added in a fixed order through LDS: (a0 + a1) + (a2 + a3)
+      // the four register copies, added in a fixed order through LDS: (a0 + a1) + (a2 + a3)
       auto put = [&](int slot) {
 #pragma unroll
-        for (int r = 0; r < TILE; ++r)
+        for (int r = 0; r < kTile; ++r)
 #pragma unroll
-          for (int q = 0; q < TILE; ++q) copies[slot][r * TILE + q][cblk * 64 + lane] = acc[r][q];
+          for (int q = 0; q < kTile; ++q) copies[slot][r * kTile + q][lane] = acc[r][q];
       };
       auto take = [&](int slot) {
 #pragma unroll
-        for (int r = 0; r < TILE; ++r)
+        for (int r = 0; r < kTile; ++r)
 #pragma unroll
-          for (int q = 0; q < TILE; ++q) acc[r][q] += copies[slot][r * TILE + q][cblk * 64 + lane];
+          for (int q = 0; q < kTile; ++q) acc[r][q] += copies[slot][r * kTile + q][lane];
       };
       if (subset == 1) put(0);
       if (subset == 3) put(1);
@@ -551,10 +508,10 @@ __global__ __launch_bounds__(256 * NBLK) void align_bwd_gather(
       __syncthreads();
       if (subset == 0) { take(0); put(1); }
       __syncthreads();
-      for (int i = t; i < TILE * TILE * (NCH / 4); i += NT) {   // whole rows, 16 bytes per lane
-        const int cell = i / (NCH / 4), cc = (i % (NCH / 4)) * 4;
-        const int y = y0 + cell / TILE, x = x0 + cell % TILE;
-        if (y > y1 || x > x1 || cc >= nblk * 64) continue;
+      for (int i = t; i < kTile * kTile * 16; i += 256) {   // whole rows, 16 bytes per lane
+        const int cell = i / 16, cc = (i % 16) * 4;
+        const int y = y0 + cell / kTile, x = x0 + cell % kTile;
+        if (y > y1 || x > x1) continue;
         const float* src = &copies[1][cell][cc];
         float4* dst = reinterpret_cast<float4*>(out + ((size_t)y * W + x) * C + cb0 + cc);
         float4 v = make_float4(src[0], src[1], src[2], src[3]);
@@ -689,26 +646,18 @@ int launch_forward(const T* in, const T* rois, T* out, int B, int C, int H, int 
   return JTSM_OK;
 }
 
-// Gather form with the census guard over a level table: both forms are launched, the device-side census lets one of
-// them return at once.
-// census (one int per tile) + launch plan + per roi: reach + meta
-static size_t align_gather_head_bytes(int ntile, int C) {
-  return ((size_t)ntile * (1 + C / 64) * sizeof(int) + 4 * sizeof(int) + 15) & ~(size_t)15;
+// May the gather form take a backward call?  float32, not rotated, NHWC, whole 64-channel blocks, bins the staging
+// tables hold, and enough of them: a handful of rois — the mask branch's foreground set — is cheaper as memset + scatter
+// than as one workgroup per tile of the whole map, so the gather starts at 8192 bins.
+template <typename T, bool ROT>
+static bool gather_takes(int layout, int B, int C, int M, int PH, int PW, const void* grad, const void* rois) {
+  const long bins = (long)M * PH * PW;
+  return std::is_same<T, float>::value && !ROT && layout == JTSM_NHWC && B > 0 && C > 0 && C % 64 == 0 &&
+         PH <= kMaxBins && PW <= kMaxBins && bins >= 8192 && bins < (1L << 30) && grad && rois;
 }
-static size_t align_gather_bytes(int ntile, int C, int M) {
-  return align_gather_head_bytes(ntile, C) + (size_t)M * (sizeof(int4) + sizeof(int));
-}
-// stream-ordered scratch of a call whose entry point has no workspace argument (the reference-shaped ones): released on
-// every path out of the function
-struct AsyncScratch {
-  void* p = nullptr;
-  hipStream_t st = nullptr;
-  ~AsyncScratch() { if (p) (void)hipFreeAsync(p, st); }
-};
 
-static int align_backward_gather(const float* grad, const float* rois, AlignLevels& lv, int B, int C, int M, int PH,
-                                 int PW, int sr, int aligned, const int* roi_level, hipStream_t st, bool accumulate = false,
-                                 void* workspace = nullptr, size_t workspace_bytes = 0) {
+// The tiles of a level table (H, W and n set): tiles_x, tiles_y and first_tile filled in; returns the tile count.
+static int plan_tiles(AlignLevels& lv, int B) {
   int ntile = 0;
   for (int l = 0; l < lv.n; ++l) {
     lv.tiles_x[l] = ceil_div(lv.W[l], kTile);
@@ -717,7 +666,38 @@ static int align_backward_gather(const float* grad, const float* rois, AlignLeve
     ntile += B * lv.tiles_x[l] * lv.tiles_y[l];
   }
   lv.first_tile[lv.n] = ntile;
-  const size_t need = align_gather_bytes(ntile, C, M);
+  return ntile;
+}
+
+// The gather's workspace: the census (one int per tile), the launch plan (maximum, number of jobs, C / 64 (tile, channel
+// block) jobs per reachable tile), and per roi the cell reach and image | level entry << 16.
+struct GatherWs { int* census; int* plan; int4* reach; int* meta; };
+static GatherWs carve(Arena& a, int ntile, int C, int M) {
+  GatherWs k;
+  k.census = a.take<int>(ntile);
+  k.plan = a.take<int>(2 + (size_t)ntile * (C / 64));
+  k.reach = a.take<int4>(M);
+  k.meta = a.take<int>(M);
+  return k;
+}
+
+// stream-ordered scratch of a call whose entry point has no workspace argument (the reference-shaped ones): released on
+// every path out of the function
+struct AsyncScratch {
+  void* p = nullptr;
+  hipStream_t st = nullptr;
+  ~AsyncScratch() { if (p) (void)hipFreeAsync(p, st); }
+};
+
+// Gather form with the census guard over a level table: both forms are launched, the device-side census lets one of
+// them return at once.
+static int align_backward_gather(const float* grad, const float* rois, AlignLevels& lv, int B, int C, int M, int PH,
+                                 int PW, int sr, int aligned, const int* roi_level, hipStream_t st, bool accumulate = false,
+                                 void* workspace = nullptr, size_t workspace_bytes = 0) {
+  const int ntile = plan_tiles(lv, B);
+  Arena measure{nullptr};
+  carve(measure, ntile, C, M);
+  const size_t need = measure.off;
   AsyncScratch own;
   own.st = st;
   if (workspace) {
@@ -730,29 +710,24 @@ static int align_backward_gather(const float* grad, const float* rois, AlignLeve
   // (accumulate: the maps already hold a gradient — both forms add to it and nothing is cleared)
   for (int l = 0; l < lv.n && !accumulate; ++l)
     JTSM_CHECK_HIP(hipMemsetAsync(lv.gin[l], 0, (size_t)B * lv.H[l] * lv.W[l] * C * sizeof(float), st));
-  // census, then the launch plan (maximum, number of jobs, C / 64 (tile, channel block) jobs per reachable tile), then
-  // per roi: reach + meta
-  int* census = reinterpret_cast<int*>(workspace ? workspace : own.p);
+  Arena arena{static_cast<char*>(workspace ? workspace : own.p)};
+  const GatherWs k = carve(arena, ntile, C, M);
   const int fan = C / 64;
-  const size_t head = align_gather_head_bytes(ntile, C);
-  JTSM_CHECK_HIP(hipMemsetAsync(census, 0, (size_t)ntile * sizeof(int), st));
-  int* plan = census + ntile;
-  int4* reach = reinterpret_cast<int4*>(reinterpret_cast<char*>(census) + head);   // cell reach (16-byte aligned)
-  int* meta = reinterpret_cast<int*>(reach + M);                                    // image | level entry << 16
+  JTSM_CHECK_HIP(hipMemsetAsync(k.census, 0, (size_t)ntile * sizeof(int), st));
   hipLaunchKernelGGL(align_census_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, st, rois, M, PH, PW, sr, aligned,
-                     roi_level, lv, census, reach, meta);
-  hipLaunchKernelGGL(tile_plan_kernel, dim3(1), dim3(1024), 0, st, census, ntile, plan, 1, fan);
-  hipLaunchKernelGGL((align_bwd_gather<8, 1>), dim3(std::min(ntile * fan, 512)), dim3(256), 0, st, grad, rois, lv, C, M, PH,
-                     PW, sr, aligned, plan, census_limit(), fan, reach, meta, accumulate ? 1 : 0);
+                     roi_level, lv, k.census, k.reach, k.meta);
+  hipLaunchKernelGGL(tile_plan_kernel, dim3(1), dim3(1024), 0, st, k.census, ntile, k.plan, 1, fan);
+  hipLaunchKernelGGL(align_bwd_gather, dim3(std::min(ntile * fan, 512)), dim3(256), 0, st, grad, rois, lv, C, M, PH,
+                     PW, sr, aligned, k.plan, census_limit(), fan, k.reach, k.meta, accumulate ? 1 : 0);
   constexpr int V = WideVec<float>::value;
   const int blocks = ceil_div((long)M * PH * PW, 4);
   // the scatter form, all levels in one launch (returns at once unless the census says so)
   if (C % V == 0 && ((uintptr_t)grad % (V * sizeof(float))) == 0)
     hipLaunchKernelGGL((align_bwd_nhwc_levels<V>), dim3(blocks), dim3(256), 0, st, grad, rois, lv, C, M, PH, PW, sr, aligned,
-                       roi_level, plan, census_limit());
+                       roi_level, k.plan, census_limit());
   else
     hipLaunchKernelGGL((align_bwd_nhwc_levels<1>), dim3(blocks), dim3(256), 0, st, grad, rois, lv, C, M, PH, PW, sr, aligned,
-                       roi_level, plan, census_limit());
+                       roi_level, k.plan, census_limit());
   JTSM_CHECK_LAUNCH("roi_align backward (gather + census)");
   return JTSM_OK;      // (own scratch: released by AsyncScratch, also on the error returns above)
 }
@@ -768,10 +743,7 @@ int launch_backward(const T* grad, const T* rois, T* gin, int B, int C, int H, i
   const size_t in_elems = (size_t)B * C * H * W;
   if (in_elems == 0) return JTSM_OK;
   JTSM_REQUIRE(gin, "roi_align backward: null grad_input");
-  // (a handful of rois — the mask branch's foreground set — is cheaper as memset + scatter than as one workgroup per
-  // tile of the whole map: the gather starts at 8192 bins)
-  if (std::is_same<T, float>::value && !ROT && layout == JTSM_NHWC && C % 64 == 0 && grad && rois && PW <= kMaxBins && PH <= kMaxBins &&
-      (long)M * PH * PW >= 8192 && (long)M * PH * PW < (1L << 30)) {
+  if (gather_takes<T, ROT>(layout, B, C, M, PH, PW, grad, rois)) {
     AlignLevels lv = {};
     lv.n = 1;
     lv.gin[0] = reinterpret_cast<float*>(gin); lv.H[0] = H; lv.W[0] = W; lv.scale[0] = (float)scale;
@@ -848,7 +820,19 @@ __global__ __launch_bounds__(256) void rect_mask_targets_kernel(const float* __r
 // so the ORDER is kept and only the evaluation is spread.  A skipped sample contributes +0.f (x + 0.f == x for the
 // non-negative sums here), as do the lanes past the last sample.
 constexpr int CROP_BINS = 16;
+// One bin by one thread: the terms summed in (iy, ix) order, averaged, thresholded.  The per-roi kernels' small grids
+// and the thread-per-bin kernels (more rois or bins than a launch grid of rois holds) both end here.
 template <class F>   // term(ph, pw, iy, ix): t.w[0] * v0 + t.w[1] * v1 + t.w[2] * v2 + t.w[3] * v3, or 0.f when skipped
+__device__ __forceinline__ unsigned char crop_bin(int gh, int gw, int ph, int pw, F term) {
+#pragma clang fp contract(off)
+  const int cells = gh * gw;
+  const float count = (float)(cells > 1 ? cells : 1);
+  float acc = 0.f;
+  for (int iy = 0; iy < gh; ++iy)
+    for (int ix = 0; ix < gw; ++ix) acc += term(ph, pw, iy, ix);
+  return (acc / count) >= 0.5f ? 1 : 0;
+}
+template <class F>
 __device__ __forceinline__ void crop_bins(int side, int gh, int gw, unsigned char* __restrict__ out_roi,
                                           float (*buf)[64], F term) {
 #pragma clang fp contract(off)
@@ -856,13 +840,7 @@ __device__ __forceinline__ void crop_bins(int side, int gh, int gw, unsigned cha
   const float count = (float)(cells > 1 ? cells : 1);
   if (cells <= 16) {   // a thread per bin
     const int b = bin0 + (int)threadIdx.x;
-    if (threadIdx.x < CROP_BINS && b < nb) {
-      const int ph = b / side, pw = b - ph * side;
-      float acc = 0.f;
-      for (int iy = 0; iy < gh; ++iy)
-        for (int ix = 0; ix < gw; ++ix) acc += term(ph, pw, iy, ix);
-      out_roi[b] = (acc / count) >= 0.5f ? 1 : 0;
-    }
+    if (threadIdx.x < CROP_BINS && b < nb) out_roi[b] = crop_bin(gh, gw, b / side, b % side, term);
     return;
   }
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -896,6 +874,21 @@ __device__ __forceinline__ void crop_bins(int side, int gh, int gw, unsigned cha
 // marks — an image that is never rasterised here: pixel (y, x) of target t is oh_labels[t][superpixels[y][x]] != 0.
 // Thread (roi, ph, pw) runs the ROIAlign(1.0, sampling 0, aligned) arithmetic of BitMasks.crop_and_resize
 // (structures/masks.py:169-200) on that image and thresholds at 0.5.
+// One sample's term of that sum: the four taps' pixels looked up in the label row; 0.f for a sample outside the image.
+__device__ __forceinline__ float sp_mask_term(const RoiGeom<float>& g, int H, int W, const int* __restrict__ s,
+                                              const int* __restrict__ lab, int L, int ph, int pw, int iy, int ix) {
+#pragma clang fp contract(off)
+  const Tap<float> t = sample_tap<float, false>(g, H, W, ph, pw, iy, ix);
+  if (t.pos[0] < 0) return 0.f;
+  float v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int id = s[t.pos[k]];
+    v[k] = ((unsigned)id < (unsigned)L && lab[id] != 0) ? 1.f : 0.f;
+  }
+  return t.w[0] * v[0] + t.w[1] * v[1] + t.w[2] * v[2] + t.w[3] * v[3];
+}
+
 __global__ __launch_bounds__(256) void sp_mask_targets_kernel(const float* __restrict__ rois,        // (N,4) boxes
                                                               const int* __restrict__ oh_row,        // (N) label row
                                                               const int* __restrict__ img_of,        // (N) image
@@ -913,22 +906,9 @@ __global__ __launch_bounds__(256) void sp_mask_targets_kernel(const float* __res
     const RoiGeom<float> g = geom_box<float>(roi5, 1.0f, side, side, 0, true);
     const int* lab = oh_labels + (size_t)row * L;
     const int* s = sp + (size_t)img_of[n] * H * W;
-    const int cells = g.gh * g.gw;
-    const float count = (float)(cells > 1 ? cells : 1);
-    float acc = 0.f;
-    for (int iy = 0; iy < g.gh; ++iy)
-      for (int ix = 0; ix < g.gw; ++ix) {
-        const Tap<float> t = sample_tap<float, false>(g, H, W, ph, pw, iy, ix);
-        if (t.pos[0] < 0) continue;
-        float v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int id = s[t.pos[k]];
-          v[k] = ((unsigned)id < (unsigned)L && lab[id] != 0) ? 1.f : 0.f;
-        }
-        acc += t.w[0] * v[0] + t.w[1] * v[1] + t.w[2] * v[2] + t.w[3] * v[3];
-      }
-    out[idx] = (acc / count) >= 0.5f ? 1 : 0;
+    out[idx] = crop_bin(g.gh, g.gw, ph, pw, [&](int ph, int pw, int iy, int ix) -> float {
+      return sp_mask_term(g, H, W, s, lab, L, ph, pw, iy, ix);
+    });
   }
 }
 
@@ -952,15 +932,7 @@ __global__ __launch_bounds__(256) void sp_mask_targets_roi_kernel(const float* _
   const int* lab = oh_labels + (size_t)row * L;
   const int* s = sp + (size_t)img_of[n] * H * W;
   crop_bins(side, g.gh, g.gw, out_roi, buf, [&](int ph, int pw, int iy, int ix) -> float {
-    const Tap<float> t = sample_tap<float, false>(g, H, W, ph, pw, iy, ix);
-    if (t.pos[0] < 0) return 0.f;
-    float v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int id = s[t.pos[k]];
-      v[k] = ((unsigned)id < (unsigned)L && lab[id] != 0) ? 1.f : 0.f;
-    }
-    return t.w[0] * v[0] + t.w[1] * v[1] + t.w[2] * v[2] + t.w[3] * v[3];
+    return sp_mask_term(g, H, W, s, lab, L, ph, pw, iy, ix);
   });
 }
 
@@ -1021,6 +993,25 @@ __device__ __forceinline__ float pasted_bit_axes(const float* __restrict__ m, in
   return acc >= threshold ? 1.f : 0.f;
 }
 
+// One sample's term: the pasted image's bits at the four taps; 0.f for a sample outside the image.  box = (x0, y0, x1, y1).
+// (the kernels are bound by instruction issue: per tap the first form spent an integer division to recover (y, x)
+// and two float divisions + a floor per axis; a sample's four taps share two rows and two columns)
+__device__ __forceinline__ float paste_crop_term(const RoiGeom<float>& g, int H, int W, const float* __restrict__ m, int M,
+                                                 const float (&box)[4], float threshold, int ph, int pw, int iy, int ix) {
+#pragma clang fp contract(off)
+  const Tap<float> t = sample_tap<float, false>(g, H, W, ph, pw, iy, ix);
+  if (t.pos[0] < 0) return 0.f;
+  // make_tap: pos = {yl W + xl, yl W + xh, yh W + xl, yh W + xh} with yh in {yl, yl + 1}, xh in {xl, xl + 1}
+  const int yl = t.pos[0] / W, xl = t.pos[0] - yl * W;
+  const int xh = t.pos[1] - yl * W, yh = yl + (t.pos[2] != t.pos[0] ? 1 : 0);
+  const PasteAxis ayl = paste_axis(yl, box[1], box[3], M), axl = paste_axis(xl, box[0], box[2], M);
+  const PasteAxis ayh = yh == yl ? ayl : paste_axis(yh, box[1], box[3], M);
+  const PasteAxis axh = xh == xl ? axl : paste_axis(xh, box[0], box[2], M);
+  const float v0 = pasted_bit_axes(m, M, ayl, axl, threshold), v1 = pasted_bit_axes(m, M, ayl, axh, threshold);
+  const float v2 = pasted_bit_axes(m, M, ayh, axl, threshold), v3 = pasted_bit_axes(m, M, ayh, axh, threshold);
+  return t.w[0] * v0 + t.w[1] * v1 + t.w[2] * v2 + t.w[3] * v3;
+}
+
 __global__ __launch_bounds__(256) void paste_crop_targets_kernel(const float* __restrict__ probs,   // (N, M, M)
                                                                  const float* __restrict__ rois,    // (N, 4)
                                                                  unsigned char* __restrict__ out, long total, int M,
@@ -1029,30 +1020,13 @@ __global__ __launch_bounds__(256) void paste_crop_targets_kernel(const float* __
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int pw = (int)(idx % side), ph = (int)((idx / side) % side);
     const long n = idx / side / side;
-    const float x0 = rois[n * 4], y0 = rois[n * 4 + 1], x1 = rois[n * 4 + 2], y1 = rois[n * 4 + 3];
-    const float roi5[5] = {0.f, x0, y0, x1, y1};
+    const float box[4] = {rois[n * 4], rois[n * 4 + 1], rois[n * 4 + 2], rois[n * 4 + 3]};
+    const float roi5[5] = {0.f, box[0], box[1], box[2], box[3]};
     const RoiGeom<float> g = geom_box<float>(roi5, 1.0f, side, side, 0, true);
     const float* m = probs + (size_t)n * M * M;
-    const int cells = g.gh * g.gw;
-    const float count = (float)(cells > 1 ? cells : 1);
-    // (the kernel is bound by instruction issue: per tap the first form spent an integer division to recover (y, x)
-    // and two float divisions + a floor per axis; a sample's four taps share two rows and two columns)
-    float acc = 0.f;
-    for (int iy = 0; iy < g.gh; ++iy)
-      for (int ix = 0; ix < g.gw; ++ix) {
-        const Tap<float> t = sample_tap<float, false>(g, H, W, ph, pw, iy, ix);
-        if (t.pos[0] < 0) continue;
-        // make_tap: pos = {yl W + xl, yl W + xh, yh W + xl, yh W + xh} with yh in {yl, yl + 1}, xh in {xl, xl + 1}
-        const int yl = t.pos[0] / W, xl = t.pos[0] - yl * W;
-        const int xh = t.pos[1] - yl * W, yh = yl + (t.pos[2] != t.pos[0] ? 1 : 0);
-        const PasteAxis ayl = paste_axis(yl, y0, y1, M), axl = paste_axis(xl, x0, x1, M);
-        const PasteAxis ayh = yh == yl ? ayl : paste_axis(yh, y0, y1, M);
-        const PasteAxis axh = xh == xl ? axl : paste_axis(xh, x0, x1, M);
-        const float v0 = pasted_bit_axes(m, M, ayl, axl, threshold), v1 = pasted_bit_axes(m, M, ayl, axh, threshold);
-        const float v2 = pasted_bit_axes(m, M, ayh, axl, threshold), v3 = pasted_bit_axes(m, M, ayh, axh, threshold);
-        acc += t.w[0] * v0 + t.w[1] * v1 + t.w[2] * v2 + t.w[3] * v3;
-      }
-    out[idx] = (acc / count) >= 0.5f ? 1 : 0;
+    out[idx] = crop_bin(g.gh, g.gw, ph, pw, [&](int ph, int pw, int iy, int ix) -> float {
+      return paste_crop_term(g, H, W, m, M, box, threshold, ph, pw, iy, ix);
+    });
   }
 }
 
@@ -1062,21 +1036,12 @@ __global__ __launch_bounds__(256) void paste_crop_targets_roi_kernel(const float
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float buf[4][64];
   const long n = blockIdx.y;
-  const float x0 = rois[n * 4], y0 = rois[n * 4 + 1], x1 = rois[n * 4 + 2], y1 = rois[n * 4 + 3];
-  const float roi5[5] = {0.f, x0, y0, x1, y1};
+  const float box[4] = {rois[n * 4], rois[n * 4 + 1], rois[n * 4 + 2], rois[n * 4 + 3]};
+  const float roi5[5] = {0.f, box[0], box[1], box[2], box[3]};
   const RoiGeom<float> g = geom_box<float>(roi5, 1.0f, side, side, 0, true);
   const float* m = probs + (size_t)n * M * M;
   crop_bins(side, g.gh, g.gw, out + n * side * side, buf, [&](int ph, int pw, int iy, int ix) -> float {
-    const Tap<float> t = sample_tap<float, false>(g, H, W, ph, pw, iy, ix);
-    if (t.pos[0] < 0) return 0.f;
-    const int yl = t.pos[0] / W, xl = t.pos[0] - yl * W;
-    const int xh = t.pos[1] - yl * W, yh = yl + (t.pos[2] != t.pos[0] ? 1 : 0);
-    const PasteAxis ayl = paste_axis(yl, y0, y1, M), axl = paste_axis(xl, x0, x1, M);
-    const PasteAxis ayh = yh == yl ? ayl : paste_axis(yh, y0, y1, M);
-    const PasteAxis axh = xh == xl ? axl : paste_axis(xh, x0, x1, M);
-    const float v0 = pasted_bit_axes(m, M, ayl, axl, threshold), v1 = pasted_bit_axes(m, M, ayl, axh, threshold);
-    const float v2 = pasted_bit_axes(m, M, ayh, axl, threshold), v3 = pasted_bit_axes(m, M, ayh, axh, threshold);
-    return t.w[0] * v0 + t.w[1] * v1 + t.w[2] * v2 + t.w[3] * v3;
+    return paste_crop_term(g, H, W, m, M, box, threshold, ph, pw, iy, ix);
   });
 }
 
@@ -1184,10 +1149,13 @@ int jtsm_roi_align_rotated_backward_level_f32(const float* grad, const float* ro
 }
 
 size_t jtsm_roi_align_backward_levels_workspace_bytes(const int* H, const int* W, int nlevels, int B, int C, int M) {
-  if (!H || !W || nlevels <= 0 || B <= 0 || C <= 0 || M < 0) return 0;
-  long ntile = 0;
-  for (int l = 0; l < nlevels; ++l) ntile += (long)B * ceil_div(W[l], kTile) * ceil_div(H[l], kTile);
-  return align_gather_bytes((int)ntile, C, M);
+  if (!H || !W || nlevels <= 0 || nlevels > kAlignLevels || B <= 0 || C <= 0 || M < 0) return 0;
+  AlignLevels lv = {};
+  lv.n = nlevels;
+  for (int l = 0; l < nlevels; ++l) { lv.H[l] = H[l]; lv.W[l] = W[l]; }
+  Arena a{nullptr};
+  carve(a, plan_tiles(lv, B), C, M);
+  return a.off;
 }
 
 int jtsm_roi_align_backward_levels_f32(const float* grad, const float* rois, const int32_t* roi_level,
@@ -1200,9 +1168,7 @@ int jtsm_roi_align_backward_levels_f32(const float* grad, const float* rois, con
   JTSM_REQUIRE(B >= 0 && C >= 0 && M >= 0 && pooled_h > 0 && pooled_w > 0, "roi_align levels: negative size");
   JTSM_REQUIRE(roi_level || M == 0, "roi_align levels: null roi_level");
   hipStream_t st = as_stream(stream);
-  const bool gather = C % 64 == 0 && C > 0 && B > 0 && grad && rois && pooled_w <= kMaxBins && pooled_h <= kMaxBins &&
-                      (long)M * pooled_h * pooled_w >= 8192 && (long)M * pooled_h * pooled_w < (1L << 30);
-  if (gather) {
+  if (gather_takes<float, false>(JTSM_NHWC, B, C, M, pooled_h, pooled_w, grad, rois)) {
     AlignLevels lv = {};
     lv.n = 0;
     for (int l = 0; l < nlevels; ++l) {

@@ -81,36 +81,44 @@ __device__ __forceinline__ RoiGeom<T> geom_rbox(const T* __restrict__ roi, T sca
   return g;
 }
 
-// One bilinear sample.  STRICT selects the rotated variant's "y < 0" clamp test.
+// One axis of a bilinear sample on a line of n cells.  A coordinate outside [-1, n] drops the whole sample; inside, the
+// two cells and their weights: clamped at 0, the last line folded onto itself.  STRICT selects the rotated variant's
+// "y < 0" clamp test.  The one statement of the rule: make_tap takes two of these, the gather form of the backward
+// (roi_align.hip, align_bwd_gather) stages its per-axis weights from the same pair.  The range test stays a function
+// of its own, called BEFORE the clamp: folded into axis_tap as a sentinel it lengthened every kernel.
+template <typename T> __device__ __forceinline__ bool axis_outside(int n, T y) { return y < (T)-1.0 || y > (T)n; }
+template <typename T> struct AxisTap { int lo, hi; T w_lo, w_hi; };
+template <typename T, bool STRICT>
+__device__ __forceinline__ AxisTap<T> axis_tap(int n, T y) {
+#pragma clang fp contract(off)
+  AxisTap<T> a;
+  if (STRICT) { if (y < (T)0) y = (T)0; } else { if (y <= (T)0) y = (T)0; }
+  a.lo = (int)y;
+  if (a.lo >= n - 1) { a.hi = a.lo = n - 1; y = (T)a.lo; } else { a.hi = a.lo + 1; }
+  a.w_hi = y - (T)a.lo;
+  a.w_lo = (T)1 - a.w_hi;
+  return a;
+}
+
+// One bilinear sample: both axes in range, then four positions and four products.
 template <typename T, bool STRICT>
 __device__ __forceinline__ Tap<T> make_tap(int H, int W, T y, T x) {
 #pragma clang fp contract(off)
   Tap<T> t;
-  if (y < (T)-1.0 || y > (T)H || x < (T)-1.0 || x > (T)W) {
+  if (axis_outside(H, y) || axis_outside(W, x)) {
     t.pos[0] = t.pos[1] = t.pos[2] = t.pos[3] = -1;
     t.w[0] = t.w[1] = t.w[2] = t.w[3] = (T)0;
     return t;
   }
-  if (STRICT) {
-    if (y < (T)0) y = (T)0;
-    if (x < (T)0) x = (T)0;
-  } else {
-    if (y <= (T)0) y = (T)0;
-    if (x <= (T)0) x = (T)0;
-  }
-  int yl = (int)y, xl = (int)x, yh, xh;
-  if (yl >= H - 1) { yh = yl = H - 1; y = (T)yl; } else { yh = yl + 1; }
-  if (xl >= W - 1) { xh = xl = W - 1; x = (T)xl; } else { xh = xl + 1; }
-  const T ly = y - (T)yl, lx = x - (T)xl;
-  const T hy = (T)1 - ly, hx = (T)1 - lx;
-  t.pos[0] = yl * W + xl;
-  t.pos[1] = yl * W + xh;
-  t.pos[2] = yh * W + xl;
-  t.pos[3] = yh * W + xh;
-  t.w[0] = hy * hx;
-  t.w[1] = hy * lx;
-  t.w[2] = ly * hx;
-  t.w[3] = ly * lx;
+  const AxisTap<T> ay = axis_tap<T, STRICT>(H, y), ax = axis_tap<T, STRICT>(W, x);
+  t.pos[0] = ay.lo * W + ax.lo;
+  t.pos[1] = ay.lo * W + ax.hi;
+  t.pos[2] = ay.hi * W + ax.lo;
+  t.pos[3] = ay.hi * W + ax.hi;
+  t.w[0] = ay.w_lo * ax.w_lo;
+  t.w[1] = ay.w_lo * ax.w_hi;
+  t.w[2] = ay.w_hi * ax.w_lo;
+  t.w[3] = ay.w_hi * ax.w_hi;
   return t;
 }
 

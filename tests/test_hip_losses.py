@@ -355,3 +355,50 @@ def test_paste_crop_targets_bit_exact_vs_paste_then_roi_align(cuda):
     assert got.shape == want.shape and got.dtype == torch.bool
     assert torch.equal(got, want), int((got != want).sum())
     assert 0.2 < float(want.float().mean()) < 0.8
+
+
+def crop_target_forms_inputs(seed=5):
+    """65 540 small boxes in a 64 x 64 image — five more than a launch grid holds rois, so jtsm_sp_mask_targets_f32 and
+    jtsm_paste_crop_targets_f32 take their thread-per-bin forms — with what the two target families read: one image of
+    superpixels (8 x 8-pixel cells, 16 labels), eight evidence rows over L = 16 labels, 4 x 4 mask probabilities."""
+    g = torch.Generator().manual_seed(seed)
+    n, size = 65540, 64
+    wh = torch.rand(n, 2, generator=g) * 15 + 1                     # sides of 1 to 16 pixels
+    xy = torch.rand(n, 2, generator=g) * (size - wh)                # inside the image ...
+    boxes = torch.cat([xy, xy + wh], 1)
+    for i, b in ((0, [-3.0, 5.0, 9.5, 12.0]), (1, [50.0, -2.5, 63.0, 8.0]), (2, [55.5, 40.0, 67.0, 52.0]),
+                 (65536, [20.0, 57.0, 31.0, 66.5]), (65539, [-1.5, -1.5, 6.0, 4.0])):
+        boxes[i] = torch.tensor(b)                                  # ... but for a few across its border
+    sp = torch.randint(0, 16, (8, 8), generator=g).repeat_interleave(8, 0).repeat_interleave(8, 1)[None]
+    oh_labels = torch.randint(0, 2, (8, 16), generator=g)
+    oh_rows = torch.randint(-1, 8, (n,), generator=g)               # -1: no evidence row, an empty target
+    probs = torch.rand(n, 4, 4, generator=g)
+    return boxes, sp, oh_labels, oh_rows, probs
+
+
+def test_crop_targets_thread_per_bin_forms_equal_per_roi_forms(cuda):
+    """sp_mask_targets and paste_crop_targets have a per-roi form (a workgroup per 16 bins of one roi) and a
+    thread-per-bin form for more than 65 535 rois; both evaluate one definition of a sample's term (csrc/roi_align.hip:
+    sp_mask_term, paste_crop_term), the thread-per-bin form adding +0.f for a sample outside the image where the
+    reference skips the add.  One call with all 65 540 boxes (thread per bin) must equal, bit for bit, the per-roi
+    calls on rows [0, 65535) and on the last five rows.  side = 2: boxes of up to 16 pixels give sampling grids of up
+    to 8 x 8, so the per-roi form runs both its thread-per-bin (<= 16 samples) and wavefront-per-bin paths.  Between
+    10 % and 90 % of the target bits are set (checked for this seed against oracle.pooling.roi_align_forward on the
+    rasterised images of the first 300 and the last five boxes: 0.43 for sp_mask, 0.28 for paste_crop)."""
+    from jtsm_amd.layers.mining import paste_crop_targets, sp_mask_targets
+
+    boxes, sp, oh_labels, oh_rows, probs = (x.to(cuda) for x in crop_target_forms_inputs())
+    n, side, size = boxes.shape[0], 2, 64
+    img_of = torch.zeros(n, dtype=torch.int32, device=cuda)
+    head, tail = slice(0, 65535), slice(n - 5, n)
+    forms = {
+        "sp_mask": lambda s: sp_mask_targets(boxes[s], oh_rows[s], img_of[s], oh_labels, sp, side),
+        "paste_crop": lambda s: paste_crop_targets(probs[s], boxes[s], side, size, size, 0.5),
+    }
+    for name, fn in forms.items():
+        whole = fn(slice(0, n)).cpu()
+        assert whole.shape == (n, side, side) and whole.dtype == torch.bool
+        assert torch.equal(whole[head], fn(head).cpu()), name
+        assert torch.equal(whole[tail], fn(tail).cpu()), name
+        share = float(whole.float().mean())
+        assert 0.1 < share < 0.9, (name, share)

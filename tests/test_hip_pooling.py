@@ -495,7 +495,7 @@ def test_multilevel_moi_pool_backward_falls_back_when_rois_pile_up(cuda):
 
 def test_roi_align_backward_gather_reproducible_and_fallback(cuda):
     """NHWC float32 backward with a 64-multiple channel count runs as a tiled gather (csrc/roi_align.hip:
-    align_bwd_tiled): bitwise reproducible, equal to the oracle within rounding; with a pile of rois on one tile the
+    align_bwd_gather): bitwise reproducible, equal to the oracle within rounding; with a pile of rois on one tile the
     census sends the call to the float-atomic scatter — same gradients either way."""
     rng = np.random.default_rng(7)
     B, Cc, H, W = 2, 64, 64, 64
