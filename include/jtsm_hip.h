@@ -1095,8 +1095,9 @@ int jtsm_confusion_accumulate(const int64_t* pred, const void* gt, int gt_elem_b
 /* ------------------------------------------------------------------------------------------------------------------
  * COCO box / mask AP on the device: COCOEvaluator's bbox and segm tasks (detectron2/evaluation/coco_evaluation.py) as
  * COCOeval_opt computes them (evaluation/fast_eval_api.py; layers/csrc/cocoeval/cocoeval.cpp: EvaluateImages,
- * Accumulate) with pycocotools' default parameters.  Semantics: DESIGN.md §4g.  T = 10 IoU thresholds and A = 4 area
- * ranges are fixed; bit a * 10 + t of a record word belongs to (area range a, threshold t).
+ * Accumulate) with pycocotools' default parameters, and the keypoints task (OKS).  Semantics: DESIGN.md §4g.  T = 10
+ * IoU thresholds and A = 4 area ranges are fixed; bit a * 10 + t of a record word belongs to (area range a, threshold
+ * t).
  *
  * jtsm_coco_image — ONE image and ONE task per call: ranks, IoUs and matches of the image's detections, one 32-byte
  *   record each, and the image's non-ignored ground truth added into npos.
@@ -1116,6 +1117,16 @@ int jtsm_confusion_accumulate(const int64_t* pred, const void* gt, int gt_elem_b
  *   n <= 65535, G <= 4096 (one matched bit per 64 ground-truth rows in a lane's word), n G <= 2^28, else JTSM_EINVAL.
  *   workspace: jtsm_coco_image_workspace_bytes(n, G, K, H, W, max_det) (H = W = 0 for bbox), 256-byte aligned.
  *
+ * jtsm_coco_image_keypoints — the same for the keypoints task: the similarity is pycocotools' computeOks (OKS) in
+ *   place of the IoU.  det_keypoints (n, P, 3) float32 (x, y, score) as the model leaves them: x and y get
+ *   instances_to_coco_json's `- 0.5` in fp32 where they are read, the array is not written.  gt_keypoints (G, P, 3)
+ *   double (x, y, v) as the COCO JSON holds them, rows as gt_boxes; sigmas (P) double on the device.  gt_ignore (G)
+ *   uint8 is the annotation's ignore flag (iscrowd or num_keypoints == 0: never counted, a match to it is ignored),
+ *   gt_crowd (G) uint8 only says which objects may be matched more than once.  The detection's area is w * h of its
+ *   box, as for bbox.  area_rng keeps four rows: the keypoints task's three plus a spare that repeats one of them.
+ *   1 <= P <= 64 and jtsm_coco_image's limits, else JTSM_EINVAL.  ious_debug <- the OKS.
+ *   workspace: jtsm_coco_image_keypoints_workspace_bytes(n, G, K, P, max_det), 256-byte aligned.
+ *
  * jtsm_coco_accumulate — the precision / scores (10, R, K, 4, M) and recall (10, K, 4, M) double tables, -1 where a
  *   (category, area range) has no non-ignored ground truth, from the concatenated records (D, 4) of all images, in any
  *   order: image_index in [0, N) must rise with the image id.  rec_thrs (R <= 1024) double and max_dets (M <= 8) int32
@@ -1129,6 +1140,14 @@ int jtsm_coco_image(const float* det_boxes, const float* det_scores, const int32
                     int image_index, int max_det, const double* iou_thrs, const double* area_rng, int64_t* records,
                     int64_t* npos, int64_t* stats, double* ious_debug, int32_t* rank_debug, void* workspace,
                     size_t workspace_bytes, void* stream);
+size_t jtsm_coco_image_keypoints_workspace_bytes(int n, int G, int K, int P, int max_det);
+int jtsm_coco_image_keypoints(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                              const float* det_keypoints, int n, int P, const double* gt_boxes, const double* gt_area,
+                              const uint8_t* gt_crowd, const uint8_t* gt_ignore, const double* gt_keypoints,
+                              const int32_t* gt_cat_start, int G, int K, const double* sigmas, int image_index,
+                              int max_det, const double* iou_thrs, const double* area_rng, int64_t* records,
+                              int64_t* npos, int64_t* stats, double* ious_debug, int32_t* rank_debug, void* workspace,
+                              size_t workspace_bytes, void* stream);
 size_t jtsm_coco_accumulate_workspace_bytes(int D, int K);
 int jtsm_coco_accumulate(const int64_t* records, int D, int K, int N, const int64_t* npos, const double* rec_thrs,
                          int R, const int32_t* max_dets, int M, double* precision, double* scores, double* recall,

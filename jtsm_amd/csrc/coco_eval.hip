@@ -1,5 +1,6 @@
-// COCO box / mask AP on the device: what the reference's COCOEvaluator (detectron2/evaluation/coco_evaluation.py) gets
-// from COCOeval_opt (evaluation/fast_eval_api.py) — pycocotools' parameters and IoU, and the reference's own
+// COCO box / mask / keypoint AP on the device: what the reference's COCOEvaluator
+// (detectron2/evaluation/coco_evaluation.py) gets from COCOeval_opt (evaluation/fast_eval_api.py) — pycocotools'
+// parameters, IoU and OKS, and the reference's own
 // detectron2/layers/csrc/cocoeval/cocoeval.cpp for the matching (MatchDetectionsToGroundTruth :61-140) and the
 // precision / recall tables (BuildSortedDetectionList :223-273, ComputePrecisionRecallCurve :284-371).
 // Semantics: DESIGN.md §4g.
@@ -9,6 +10,7 @@
 //              its XYWH box and area in fp64 (w, h subtracted in fp32 first), its record;
 //     pack     segm: (n, H, W) bytes -> 64-bit words by wave ballot, areas by popcount (one integer atomic per wave);
 //     iou      bbox: one thread per (detection, ground truth) pair; segm: one workgroup per pair sums popcount(a & b);
+//              keypoints (jtsm_coco_image_keypoints): one thread per pair, pycocotools' computeOks;
 //              pairs of different categories and detections past max_det leave on a uniform branch;
 //     match    one wavefront per (category, area range, threshold): detections in rank order, lanes over the
 //              category's ground truth in chunks of 64, last-maximum arg-max in two phases (non-ignored, then ignored);
@@ -42,6 +44,7 @@ constexpr int kMaxM = 8;          // maxDets entries
 constexpr int kMaxR = 1024;       // recall thresholds
 constexpr int kChunk = 256;       // records per step of the precision / recall walk = threads of its workgroup
 constexpr int kMaxGtChunks = 64;  // ground truth of one category in one image: 64 chunks of 64 (a lane's matched word)
+constexpr int kMaxKeypoints = 64; // keypoints of an object (the OKS thread walks them twice)
 
 struct Record {                   // 32 bytes; the Python side holds them as (D, 4) int64
   int cat;                        // num_categories for a detection that is left out (past max_det, or a bad class)
@@ -204,11 +207,60 @@ __global__ __launch_bounds__(256) void coco_mask_iou_kernel(const u64* __restric
   }
 }
 
-// One wavefront per (category, area range, threshold); 4 per workgroup.
+// pycocotools' computeOks.  One thread per (d, g).  The detection's x and y get instances_to_coco_json's `- 0.5` in
+// fp32 where they are read; the sum runs in keypoint order.
+__global__ __launch_bounds__(256) void coco_oks_kernel(const float* __restrict__ dkp, const int* __restrict__ classes,
+                                                       const int* __restrict__ rank, int n,
+                                                       const double4* __restrict__ gbox,
+                                                       const double* __restrict__ garea,
+                                                       const double* __restrict__ gkp,
+                                                       const double* __restrict__ sigmas, int P,
+                                                       const int* __restrict__ cat_start, int K, int G,
+                                                       double* __restrict__ ious) {
+#pragma clang fp contract(off)
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long)n * G) return;
+  const int d = (int)(t / G), g = (int)(t % G);
+  double o = -1.0;
+  if (rank[d] >= 0 && gt_cat_of(cat_start, K, g) == classes[d]) {
+    const float* a = dkp + (long)d * P * 3;
+    const double* b = gkp + (long)g * P * 3;
+    int k1 = 0;
+    for (int p = 0; p < P; ++p) k1 += b[3 * p + 2] > 0 ? 1 : 0;
+    const double4 bb = gbox[g];
+    const double x0 = bb.x - bb.z, x1 = bb.x + bb.z * 2;
+    const double y0 = bb.y - bb.w, y1 = bb.y + bb.w * 2;
+    const double ar = garea[g] + 2.220446049250313e-16;                  // np.spacing(1)
+    double sum = 0.0;
+    for (int p = 0; p < P; ++p) {
+      if (k1 > 0 && !(b[3 * p + 2] > 0)) continue;
+      const double xd = (double)(a[3 * p] - 0.5f), yd = (double)(a[3 * p + 1] - 0.5f);
+      double dx, dy;
+      if (k1 > 0) {
+        dx = xd - b[3 * p];
+        dy = yd - b[3 * p + 1];
+      } else {                                                           // the distance to the doubled box
+        dx = fmax(0.0, x0 - xd) + fmax(0.0, xd - x1);
+        dy = fmax(0.0, y0 - yd) + fmax(0.0, yd - y1);
+      }
+      const double s2 = sigmas[p] * 2;
+      const double var = s2 * s2;
+      const double xx = dx * dx, yy = dy * dy;
+      const double e = (xx + yy) / var / ar / 2;
+      sum = sum + exp(-e);
+    }
+    o = sum / (double)(k1 > 0 ? k1 : P);
+  }
+  ious[t] = o;
+}
+
+// One wavefront per (category, area range, threshold); 4 per workgroup.  gignore: the annotation's ignore flag (never
+// counted, a match is ignored); gcrowd: may be matched again (cocoeval.cpp:96).  bbox and segm: the same array.
 __global__ __launch_bounds__(256) void coco_match_kernel(const int* __restrict__ cat_count,
                                                          const int* __restrict__ det_of,
                                                          const double* __restrict__ darea, int n, int max_det,
                                                          const double* __restrict__ garea,
+                                                         const unsigned char* __restrict__ gignore,
                                                          const unsigned char* __restrict__ gcrowd,
                                                          const int* __restrict__ cat_start, int K, int G,
                                                          const double* __restrict__ ious,
@@ -230,7 +282,7 @@ __global__ __launch_bounds__(256) void coco_match_kernel(const int* __restrict__
     if (g < ng) {
       const bool cr = gcrowd[g_lo + g] != 0;
       const double ar = garea[g_lo + g];
-      const bool ig = cr || ar < lo || ar > hi;
+      const bool ig = gignore[g_lo + g] != 0 || ar < lo || ar > hi;
       if (ig) ign |= 1ull << j;
       if (cr) crowd |= 1ull << j;
       if (!ig) ++valid;
@@ -475,13 +527,22 @@ extern "C" size_t jtsm_coco_image_workspace_bytes(int n, int G, int K, int H, in
   return a.off;
 }
 
-extern "C" int jtsm_coco_image(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
-                               const uint8_t* det_masks, int n, int H, int W, const double* gt_boxes,
-                               const double* gt_area, const uint8_t* gt_crowd, const int32_t* gt_cat_start,
-                               const uint64_t* gt_masks, int G, int K, int image_index, int max_det,
-                               const double* iou_thrs, const double* area_rng, int64_t* records, int64_t* npos,
-                               int64_t* stats, double* ious_debug, int32_t* rank_debug, void* workspace,
-                               size_t workspace_bytes, void* stream) {
+// The keypoints task's own arguments; P == 0: bbox or segm.
+struct KeypointArgs {
+  const float* det;                 // (n, P, 3)
+  const double* gt;                 // (G, P, 3)
+  const uint8_t* gt_ignore;         // (G)
+  const double* sigmas;             // (P)
+  int P;
+};
+
+static int coco_image_run(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                          const uint8_t* det_masks, int n, int H, int W, const double* gt_boxes,
+                          const double* gt_area, const uint8_t* gt_crowd, const int32_t* gt_cat_start,
+                          const uint64_t* gt_masks, int G, int K, int image_index, int max_det,
+                          const double* iou_thrs, const double* area_rng, int64_t* records, int64_t* npos,
+                          int64_t* stats, double* ious_debug, int32_t* rank_debug, void* workspace,
+                          size_t workspace_bytes, void* stream, const KeypointArgs& kp) {
   JTSM_REQUIRE(n >= 0 && G >= 0 && K >= 1 && H >= 0 && W >= 0 && image_index >= 0,
                "coco_image: n=%d G=%d K=%d H=%d W=%d image_index=%d", n, G, K, H, W, image_index);
   JTSM_REQUIRE(max_det >= 1 && max_det <= kMaxDet, "coco_image: max_det=%d exceeds the %d rank bits of the sort keys "
@@ -530,6 +591,11 @@ extern "C" int jtsm_coco_image(const float* det_boxes, const float* det_scores, 
         hipLaunchKernelGGL(coco_mask_iou_kernel, dim3(G, n), dim3(256), 0, st, w.dwords, w.area_i, det_classes, rank,
                            reinterpret_cast<const u64*>(gt_masks), gt_crowd, gt_cat_start, K, G, W64, ious);
         JTSM_CHECK_LAUNCH("coco mask iou");
+      } else if (kp.P > 0) {
+        hipLaunchKernelGGL(coco_oks_kernel, dim3(ceil_div((long)n * G, 256)), dim3(256), 0, st, kp.det, det_classes,
+                           rank, n, reinterpret_cast<const double4*>(gt_boxes), gt_area, kp.gt, kp.sigmas, kp.P,
+                           gt_cat_start, K, G, ious);
+        JTSM_CHECK_LAUNCH("coco oks");
       } else {
         hipLaunchKernelGGL(coco_box_iou_kernel, dim3(ceil_div((long)n * G, 256)), dim3(256), 0, st, w.dbox, det_classes,
                            rank, n, reinterpret_cast<const double4*>(gt_boxes), gt_crowd, gt_cat_start, K, G, ious);
@@ -538,10 +604,47 @@ extern "C" int jtsm_coco_image(const float* det_boxes, const float* det_scores, 
     }
   }
   hipLaunchKernelGGL(coco_match_kernel, dim3(ceil_div((long)K * kA * kT, 4)), dim3(256), 0, st, w.cat_count, w.det_of,
-                     w.darea, n, max_det, gt_area, gt_crowd, gt_cat_start, K, G, ious, iou_thrs, area_rng, rec,
-                     reinterpret_cast<u64*>(npos));
+                     w.darea, n, max_det, gt_area, kp.P > 0 ? kp.gt_ignore : gt_crowd, gt_crowd, gt_cat_start, K, G,
+                     ious, iou_thrs, area_rng, rec, reinterpret_cast<u64*>(npos));
   JTSM_CHECK_LAUNCH("coco match");
   return JTSM_OK;
+}
+
+extern "C" int jtsm_coco_image(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                               const uint8_t* det_masks, int n, int H, int W, const double* gt_boxes,
+                               const double* gt_area, const uint8_t* gt_crowd, const int32_t* gt_cat_start,
+                               const uint64_t* gt_masks, int G, int K, int image_index, int max_det,
+                               const double* iou_thrs, const double* area_rng, int64_t* records, int64_t* npos,
+                               int64_t* stats, double* ious_debug, int32_t* rank_debug, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  return coco_image_run(det_boxes, det_scores, det_classes, det_masks, n, H, W, gt_boxes, gt_area, gt_crowd,
+                        gt_cat_start, gt_masks, G, K, image_index, max_det, iou_thrs, area_rng, records, npos, stats,
+                        ious_debug, rank_debug, workspace, workspace_bytes, stream, KeypointArgs{});
+}
+
+extern "C" size_t jtsm_coco_image_keypoints_workspace_bytes(int n, int G, int K, int P, int max_det) {
+  if (P < 1 || P > kMaxKeypoints) return 0;
+  return jtsm_coco_image_workspace_bytes(n, G, K, 0, 0, max_det);
+}
+
+extern "C" int jtsm_coco_image_keypoints(const float* det_boxes, const float* det_scores, const int32_t* det_classes,
+                                         const float* det_keypoints, int n, int P, const double* gt_boxes,
+                                         const double* gt_area, const uint8_t* gt_crowd, const uint8_t* gt_ignore,
+                                         const double* gt_keypoints, const int32_t* gt_cat_start, int G, int K,
+                                         const double* sigmas, int image_index, int max_det, const double* iou_thrs,
+                                         const double* area_rng, int64_t* records, int64_t* npos, int64_t* stats,
+                                         double* ious_debug, int32_t* rank_debug, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  JTSM_REQUIRE(P >= 1 && P <= kMaxKeypoints, "coco_image_keypoints: P=%d keypoints (1 to %d)", P, kMaxKeypoints);
+  JTSM_REQUIRE(sigmas, "coco_image_keypoints: null sigmas");
+  JTSM_REQUIRE((n <= 0 || det_keypoints) && (G <= 0 || (gt_keypoints && gt_ignore)),
+               "coco_image_keypoints: null det_keypoints / gt_keypoints / gt_ignore");
+  JTSM_REQUIRE(((size_t)det_keypoints & 3) == 0 && ((size_t)gt_keypoints & 7) == 0 && ((size_t)sigmas & 7) == 0,
+               "coco_image_keypoints: det_keypoints 4-byte, gt_keypoints / sigmas 8-byte aligned");
+  return coco_image_run(det_boxes, det_scores, det_classes, nullptr, n, 0, 0, gt_boxes, gt_area, gt_crowd, gt_cat_start,
+                        nullptr, G, K, image_index, max_det, iou_thrs, area_rng, records, npos, stats, ious_debug,
+                        rank_debug, workspace, workspace_bytes, stream,
+                        KeypointArgs{det_keypoints, gt_keypoints, gt_ignore, sigmas, P});
 }
 
 extern "C" size_t jtsm_coco_accumulate_workspace_bytes(int D, int K) {

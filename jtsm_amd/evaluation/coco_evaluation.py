@@ -1,14 +1,14 @@
-"""COCO box and mask AP on the device: COCOEvaluator of the reference (detectron2/evaluation/coco_evaluation.py — its
-bbox and segm tasks through COCOeval_opt, evaluation/fast_eval_api.py) without the host round trip and without
-pycocotools.  process() makes one library call per image and task (jtsm_coco_image: ranks, IoUs, matching —
-jtsm_amd/csrc/coco_eval.hip) on the boxes and masks where inference left them and keeps one 32-byte record per
-detection on the device; evaluate() concatenates the records, makes one more call (jtsm_coco_accumulate: sort,
-precision / recall tables), reads the tables back once per task and summarises them with NumPy as pycocotools'
-_summarize does.  Semantics: DESIGN.md §4g.
+"""COCO box, mask and keypoint AP on the device: COCOEvaluator of the reference (detectron2/evaluation/coco_evaluation.py
+— its bbox, segm and keypoints tasks through COCOeval_opt, evaluation/fast_eval_api.py) without the host round trip and
+without pycocotools.  process() makes one library call per image and task (jtsm_coco_image / jtsm_coco_image_keypoints:
+ranks, IoUs or OKS, matching — jtsm_amd/csrc/coco_eval.hip) on the boxes, masks and keypoints where inference left them
+and keeps one 32-byte record per detection on the device; evaluate() concatenates the records, makes one more call
+(jtsm_coco_accumulate: sort, precision / recall tables), reads the tables back once per task and summarises them with
+NumPy as pycocotools' _summarize does.  Semantics: DESIGN.md §4g.
 
-Not reproduced: the keypoints task (OKS; the model side exists), _eval_box_proposals (AR of proposals), comm.gather across ranks (one rank's images only), the
-JSON / .pth dumps, LVIS, polygon rasterisation (ground-truth masks are bitmasks).  The AR lines of the summary are kept
-in `last_eval[task]["stats"]`; the reference does not report them either."""
+Not reproduced: keypoints under test-time augmentation, _eval_box_proposals (AR of proposals), comm.gather across ranks
+(one rank's images only), the JSON / .pth dumps, LVIS, polygon rasterisation (ground-truth masks are bitmasks).  The AR
+lines of the summary are kept in `last_eval[task]["stats"]`; the reference does not report them either."""
 import json
 from collections import OrderedDict
 
@@ -26,6 +26,14 @@ AREA_RNG = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2,
 METRICS = ["AP", "AP50", "AP75", "APs", "APm", "APl"]
 NUM_THRESHOLDS, NUM_AREAS = len(IOU_THRS), len(AREA_RNG)
 MAX_GT_PER_IMAGE = 4096      # jtsm_coco_image: one matched bit per 64 ground-truth rows in a lane's 64-bit word
+# pycocotools' Params.setKpParams: the thresholds above, one maxDets entry, no "small" range
+KP_MAX_DETS = [20]
+KP_AREA_RNG = [[0 ** 2, 1e5 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
+KP_METRICS = ["AP", "AP50", "AP75", "APm", "APl"]
+KP_NUM_AREAS = len(KP_AREA_RNG)
+COCO_KPT_OKS_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89,
+                                .89]) / 10.0
+MAX_KEYPOINTS = 64           # jtsm_coco_image_keypoints
 
 
 def pack_masks(masks):
@@ -57,8 +65,9 @@ def mask_from_rle_counts(counts, height, width):
 class COCOGroundTruth:
     """Per image id the objects of the evaluated categories, sorted by category index (annotation order inside): `cats`
     (G,) int32, `boxes` (G,4) float64 XYWH, `area` (G,) float64 — the annotation's area field —, `iscrowd` (G,) uint8,
-    `cat_start` (K+1,) int32 and, if the image has masks, `words` (G, ceil(H W / 64)) uint64 with `mask_shape`.  NumPy
-    arrays; the evaluator uploads an image's set when it is processed.  `image_ids` is sorted ascending: the
+    `cat_start` (K+1,) int32 and, if the image has masks, `words` (G, ceil(H W / 64)) uint64 with `mask_shape`; if it
+    has keypoints, `keypoints` (G,P,3) float64 (x, y, v as the COCO JSON holds them) and `num_keypoints` (G,) int64.
+    NumPy arrays; the evaluator uploads an image's set when it is processed.  `image_ids` is sorted ascending: the
     accumulation order (np.unique(imgIds))."""
 
     def __init__(self, num_categories):
@@ -66,6 +75,7 @@ class COCOGroundTruth:
         assert self.num_categories >= 1
         self._items = {}
         self.missing_masks = {}      # image id -> description of the first annotation without a usable mask
+        self.missing_keypoints = {}  # image id -> description of the first annotation without keypoints
 
     @property
     def image_ids(self):
@@ -81,7 +91,11 @@ class COCOGroundTruth:
         it = self._items[image_id]
         return len(it["cats"]) == 0 or it["words"] is not None
 
-    def add(self, image_id, cats, boxes, area, iscrowd, masks=None):
+    def has_keypoints(self, image_id):
+        it = self._items[image_id]
+        return len(it["cats"]) == 0 or it["keypoints"] is not None
+
+    def add(self, image_id, cats, boxes, area, iscrowd, masks=None, keypoints=None, num_keypoints=None):
         assert image_id not in self._items, "duplicate image id %r" % (image_id,)
         K = self.num_categories
         cats = np.asarray(cats, dtype=np.int64).reshape(-1)
@@ -101,18 +115,29 @@ class COCOGroundTruth:
             assert masks.ndim == 3 and masks.shape[0] == G, masks.shape
             shape = tuple(masks.shape[1:])
             words = pack_masks(masks[perm])
+        if keypoints is not None and G > 0:
+            keypoints = np.asarray(keypoints, dtype=np.float64).reshape(G, -1, 3)
+            if num_keypoints is None:
+                num_keypoints = (keypoints[:, :, 2] > 0).sum(1)
+            num_keypoints = np.asarray(num_keypoints, dtype=np.int64).reshape(G)
+            keypoints, num_keypoints = np.ascontiguousarray(keypoints[perm]), np.ascontiguousarray(num_keypoints[perm])
+        else:                                   # (an image without objects needs none)
+            keypoints = num_keypoints = None
         self._items[image_id] = dict(
             cats=cats[perm].astype(np.int32), boxes=np.ascontiguousarray(boxes[perm]),
             area=np.ascontiguousarray(area[perm]), iscrowd=np.ascontiguousarray(iscrowd[perm]), cat_start=cat_start,
-            words=words, mask_shape=shape, perm=perm)
+            words=words, mask_shape=shape, keypoints=keypoints, num_keypoints=num_keypoints, perm=perm)
 
     @classmethod
-    def from_arrays(cls, image_ids, cats, boxes, areas, iscrowds, num_categories, masks=None):
+    def from_arrays(cls, image_ids, cats, boxes, areas, iscrowds, num_categories, masks=None, keypoints=None,
+                    num_keypoints=None):
         """Parallel lists over the images: category indices (G,), XYWH boxes (G,4), areas (G,), iscrowd (G,), and
-        optionally (G,H,W) bitmasks."""
+        optionally (G,H,W) bitmasks, (G,P,3) keypoints and (G,) num_keypoints (default: the count of v > 0)."""
         gt = cls(num_categories)
+        at = lambda seq, i: None if seq is None else seq[i]  # noqa: E731
         for i, image_id in enumerate(image_ids):
-            gt.add(image_id, cats[i], boxes[i], areas[i], iscrowds[i], None if masks is None else masks[i])
+            gt.add(image_id, cats[i], boxes[i], areas[i], iscrowds[i], at(masks, i), at(keypoints, i),
+                   at(num_keypoints, i))
         return gt
 
     @classmethod
@@ -120,11 +145,14 @@ class COCOGroundTruth:
         """detectron2-format dicts (image_id, height, width, annotations: category_id — the contiguous index —, bbox
         with bbox_mode 0 = XYXY_ABS (the default) or 1 = XYWH_ABS, iscrowd, optionally a (H,W) bitmask array under
         `segmentation` and `area`).  Without `area`: the mask's pixel count, else the box's w * h — what the reference's
-        convert_to_coco_dict writes.  An image has masks only if every annotation carries a bitmask."""
+        convert_to_coco_dict writes.  An image has masks only if every annotation carries a bitmask.  `keypoints`
+        (3 P values or (P,3)): x and y minus 0.5 as convert_to_coco_dict writes them (datasets/coco.py:361-373; the
+        annotation is left alone), `num_keypoints` from the field or else the count of v > 0; an image has keypoints
+        only if every annotation carries them."""
         gt = cls(num_categories)
         for d in dicts:
             anns = d.get("annotations", [])
-            cats, boxes, areas, crowd, masks = [], [], [], [], []
+            cats, boxes, areas, crowd, masks, kps, nkp = [], [], [], [], [], [], []
             for a in anns:
                 b = [float(v) for v in a["bbox"]]
                 if int(a.get("bbox_mode", 0)) == 0:
@@ -139,8 +167,19 @@ class COCOGroundTruth:
                 areas.append(float(a["area"]) if "area" in a else
                              (float(mask.sum()) if mask is not None else b[2] * b[3]))
                 masks.append(mask)
+                kp = a.get("keypoints")
+                if kp is None:
+                    gt.missing_keypoints.setdefault(d["image_id"], "annotation %d of image %r"
+                                                    % (len(cats) - 1, d["image_id"]))
+                else:
+                    kp = np.array(kp, dtype=np.float64).reshape(-1, 3)
+                    kp[:, :2] -= 0.5
+                    nkp.append(int(a["num_keypoints"]) if "num_keypoints" in a else int((kp[:, 2] > 0).sum()))
+                kps.append(kp)
             all_masks = len(masks) > 0 and all(m is not None for m in masks)
-            gt.add(d["image_id"], cats, boxes, areas, crowd, np.stack(masks) if all_masks else None)
+            all_kps = len(kps) > 0 and all(k is not None for k in kps)
+            gt.add(d["image_id"], cats, boxes, areas, crowd, np.stack(masks) if all_masks else None,
+                   _stack_keypoints(kps, d["image_id"]) if all_kps else None, nkp if all_kps else None)
         return gt
 
     @classmethod
@@ -149,7 +188,9 @@ class COCOGroundTruth:
         order; annotations of other categories are left out.  Boxes, area and iscrowd come from the JSON.  Masks come
         from uncompressed-RLE `counts` lists (column-major) or from mask_loader(annotation) -> (H, W) array; a polygon
         or a compressed string without a loader leaves the image without segm ground truth (`missing_masks` names the
-        annotation, and a segm evaluation of that image raises)."""
+        annotation, and a segm evaluation of that image raises).  `keypoints` and `num_keypoints` are read as they
+        stand; an image whose annotations do not all carry keypoints has no keypoint ground truth
+        (`missing_keypoints` names the annotation)."""
         index = {(c["id"] if isinstance(c, dict) else c): i for i, c in enumerate(categories)}
         with open(json_path, "r") as f:
             data = json.load(f)
@@ -173,18 +214,34 @@ class COCOGroundTruth:
                     raise ValueError("annotation id %r: mask %s, image %s" % (ann.get("id"), mask.shape, sizes[image_id]))
                 masks.append(mask)
             all_masks = len(masks) > 0 and all(m is not None for m in masks)
+            kps = [np.asarray(a["keypoints"], np.float64).reshape(-1, 3) if "keypoints" in a else None for a in anns]
+            for ann, kp in zip(anns, kps):
+                if kp is None:
+                    gt.missing_keypoints.setdefault(image_id, "annotation id %r of image %r" % (ann.get("id"), image_id))
+            all_kps = len(kps) > 0 and all(k is not None for k in kps)
+            nkp = [int(a["num_keypoints"]) if "num_keypoints" in a else int((k[:, 2] > 0).sum())
+                   for a, k in zip(anns, kps)] if all_kps else None
             gt.add(image_id, [index[a["category_id"]] for a in anns], [a["bbox"] for a in anns],
                    [a["area"] for a in anns], [a.get("iscrowd", 0) for a in anns],
-                   np.stack(masks) if all_masks else None)
+                   np.stack(masks) if all_masks else None, _stack_keypoints(kps, image_id) if all_kps else None, nkp)
         return gt
 
 
-def new_state(num_categories, device):
+def _stack_keypoints(kps, image_id):
+    if len({k.shape for k in kps}) != 1:
+        raise ValueError("image %r: objects with %s keypoints" % (image_id, sorted({k.shape[0] for k in kps})))
+    return np.stack(kps)
+
+
+def new_state(num_categories, device, keypoints=False):
     """The evaluation's constants and zeroed running totals on the device: iou_thrs (10), area_rng (4,2), rec_thrs
-    (101) float64, max_dets (3) int32; npos (K,4) and stats (2) int64."""
+    (101) float64, max_dets (3) int32; npos (K,4) and stats (2) int64.  keypoints: max_dets (1) = [20] and the three
+    area ranges of the task; the device's records keep four, so the last row is repeated and its column of npos and
+    of the tables is dropped on the host."""
     f = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)  # noqa: E731
-    return dict(iou_thrs=f(IOU_THRS), area_rng=f(np.array(AREA_RNG)), rec_thrs=f(REC_THRS),
-                max_dets=torch.tensor(MAX_DETS, dtype=torch.int32).to(device),
+    area_rng = KP_AREA_RNG + KP_AREA_RNG[-1:] if keypoints else AREA_RNG
+    return dict(iou_thrs=f(IOU_THRS), area_rng=f(np.array(area_rng)), rec_thrs=f(REC_THRS),
+                max_dets=torch.tensor(KP_MAX_DETS if keypoints else MAX_DETS, dtype=torch.int32).to(device),
                 npos=torch.zeros(int(num_categories), NUM_AREAS, dtype=torch.int64, device=device),
                 stats=torch.zeros(2, dtype=torch.int64, device=device))
 
@@ -235,14 +292,51 @@ def coco_image(boxes, scores, classes, masks, gt, image_index, state, with_debug
 
 
 @torch.no_grad()
+def coco_image_keypoints(boxes, scores, classes, keypoints, gt, sigmas, image_index, state, with_debug=False):
+    """One jtsm_coco_image_keypoints call.  boxes, scores, classes as coco_image; keypoints (n,P,3) float32 as the model
+    leaves them (read only: the 0.5 shift happens in the kernel); gt: coco_image's boxes, area, iscrowd, cat_start plus
+    keypoints (G,P,3) float64 and ignore (G,) uint8; sigmas (P,) float64 on the device; state: new_state(keypoints=True).
+    -> dict(records (n,4) int64, and with_debug ious (n,G) float64 — the OKS — and rank (n,) int32)."""
+    L.require_gpu(boxes, scores, classes, keypoints, gt["boxes"], gt["area"], gt["iscrowd"], gt["ignore"],
+                  gt["keypoints"], gt["cat_start"], sigmas, state["npos"])
+    assert boxes.dtype == scores.dtype == keypoints.dtype == torch.float32
+    assert classes.dtype == gt["cat_start"].dtype == torch.int32
+    assert gt["boxes"].dtype == gt["area"].dtype == gt["keypoints"].dtype == sigmas.dtype == torch.float64
+    assert gt["iscrowd"].dtype == gt["ignore"].dtype == torch.uint8
+    n, G, K, P = scores.numel(), gt["area"].numel(), state["npos"].shape[0], sigmas.numel()
+    assert boxes.shape == (n, 4) and gt["boxes"].shape == (G, 4) and gt["cat_start"].numel() == K + 1
+    assert tuple(keypoints.shape) == (n, P, 3) and tuple(gt["keypoints"].shape) == (G, P, 3), (
+        tuple(keypoints.shape), tuple(gt["keypoints"].shape), P)
+    assert gt["iscrowd"].numel() == gt["ignore"].numel() == G and state["max_dets"].numel() == len(KP_MAX_DETS)
+    boxes, scores, classes, keypoints = boxes.contiguous(), scores.contiguous(), classes.contiguous(), keypoints.contiguous()
+    gkp, sigmas = gt["keypoints"].contiguous(), sigmas.contiguous()
+    dev = state["npos"].device
+    out = dict(records=torch.empty(n, 4, dtype=torch.int64, device=dev))
+    if with_debug:
+        out["ious"] = torch.full((n, G), -1.0, dtype=torch.float64, device=dev)
+        out["rank"] = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    nz = lambda t: L.ptr(t) if t is not None and t.numel() else None  # noqa: E731
+    lib = L.lib()
+    nbytes = lib.jtsm_coco_image_keypoints_workspace_bytes(n, G, K, P, KP_MAX_DETS[-1])
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    L.check(lib.jtsm_coco_image_keypoints(
+        nz(boxes), nz(scores), nz(classes), nz(keypoints), n, P, nz(gt["boxes"]), nz(gt["area"]), nz(gt["iscrowd"]),
+        nz(gt["ignore"]), nz(gkp), L.ptr(gt["cat_start"]), G, K, L.ptr(sigmas), int(image_index), KP_MAX_DETS[-1],
+        L.ptr(state["iou_thrs"]), L.ptr(state["area_rng"]), nz(out["records"]), L.ptr(state["npos"]),
+        L.ptr(state["stats"]), nz(out.get("ious")), nz(out.get("rank")), L.ptr(ws), ws.numel(), L.stream()),
+        "coco_image_keypoints")
+    return out
+
+
+@torch.no_grad()
 def coco_accumulate(records, num_images, state):
     """One jtsm_coco_accumulate call over the concatenated records (D,4) int64.  -> dict of device tensors: `tables`
-    (one float64 vector) and its views precision, scores (T,R,K,A,M) and recall (T,K,A,M)."""
+    (one float64 vector) and its views precision, scores (T,R,K,A,M) and recall (T,K,A,M); M = the state's max_dets."""
     L.require_gpu(records, state["npos"])
     assert records.dtype == torch.int64 and records.dim() == 2 and records.shape[1] == 4
     records = records.contiguous()
     D, K = records.shape[0], state["npos"].shape[0]
-    T, R, A, M = NUM_THRESHOLDS, len(REC_THRS), NUM_AREAS, len(MAX_DETS)
+    T, R, A, M = NUM_THRESHOLDS, len(REC_THRS), NUM_AREAS, state["max_dets"].numel()
     dev = state["npos"].device
     big, small = T * R * K * A * M, T * K * A * M
     tables = torch.empty(2 * big + small, dtype=torch.float64, device=dev)
@@ -257,9 +351,9 @@ def coco_accumulate(records, num_images, state):
     return out
 
 
-def split_tables(tables, num_categories):
+def split_tables(tables, num_categories, num_max_dets=len(MAX_DETS)):
     """The host copy of coco_accumulate's `tables` -> (precision, scores (T,R,K,A,M), recall (T,K,A,M)) NumPy arrays."""
-    T, R, K, A, M = NUM_THRESHOLDS, len(REC_THRS), int(num_categories), NUM_AREAS, len(MAX_DETS)
+    T, R, K, A, M = NUM_THRESHOLDS, len(REC_THRS), int(num_categories), NUM_AREAS, int(num_max_dets)
     t = tables.numpy()
     big = T * R * K * A * M
     return t[:big].reshape(T, R, K, A, M), t[big:2 * big].reshape(T, R, K, A, M), t[2 * big:].reshape(T, K, A, M)
@@ -280,13 +374,26 @@ def summarize(precision, recall):
                      one(0, area=3)], dtype=np.float64)
 
 
-def derive_coco_results(stats, precision, class_names=None):
+def summarize_keypoints(precision, recall):
+    """pycocotools' COCOeval._summarizeKps on the keypoints task's tables ((T,R,K,3,1) and (T,K,3,1)): the ten stats —
+    AP, AP50, AP75, APm, APl, then AR, AR50, AR75, ARm, ARl — all at maxDets 20."""
+    def one(ap, iou=None, area=0):
+        s = precision[:, :, :, area, 0] if ap else recall[:, :, area, 0]
+        if iou is not None:
+            s = s[np.where(iou == IOU_THRS)[0]]
+        return -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
+
+    return np.array([one(ap, **kw) for ap in (1, 0)
+                     for kw in ({}, dict(iou=.5), dict(iou=.75), dict(area=1), dict(area=2))], dtype=np.float64)
+
+
+def derive_coco_results(stats, precision, class_names=None, metrics=METRICS):
     """The reference's _derive_coco_results (coco_evaluation.py:288-354) without its logging: values x100, NaN for a
     negative stat; with more than one class name also "AP-<name>" from precision[:, :, k, 0, -1]; stats None (no
-    predictions at all): NaN for every metric."""
+    predictions at all): NaN for every metric.  metrics: METRICS, or KP_METRICS for the keypoints task."""
     if stats is None:
-        return {metric: float("nan") for metric in METRICS}
-    results = {metric: float(stats[idx] * 100 if stats[idx] >= 0 else "nan") for idx, metric in enumerate(METRICS)}
+        return {metric: float("nan") for metric in metrics}
+    results = {metric: float(stats[idx] * 100 if stats[idx] >= 0 else "nan") for idx, metric in enumerate(metrics)}
     if class_names is None or len(class_names) <= 1:
         return results
     assert len(class_names) == precision.shape[2]
@@ -299,14 +406,18 @@ def derive_coco_results(stats, precision, class_names=None):
 
 class COCOEvaluator(DatasetEvaluator):
     """ground_truth: COCOGroundTruth; class_names: the evaluated categories in index order (index = pred_classes
-    value) for the per-category AP; tasks: a subset of ("bbox", "segm"), or None to infer it from the first processed
-    output as the reference does (bbox, plus segm when pred_masks is present).  All images of the ground truth count
-    (the reference's default imgIds), processed or not."""
+    value) for the per-category AP; tasks: a subset of ("bbox", "segm", "keypoints"), or None to infer it from the
+    first processed output as the reference does (bbox, plus segm when pred_masks is present, plus keypoints when
+    pred_keypoints is present).  kpt_oks_sigmas: the OKS sigmas, one per keypoint (TEST.KEYPOINT_OKS_SIGMAS); empty:
+    the 17 of COCO.  All images of the ground truth count (the reference's default imgIds), processed or not."""
 
-    def __init__(self, ground_truth, class_names=None, tasks=None, device="cuda"):
+    def __init__(self, ground_truth, class_names=None, tasks=None, device="cuda", kpt_oks_sigmas=()):
         assert class_names is None or len(class_names) == ground_truth.num_categories
-        assert tasks is None or (len(tasks) and set(tasks) <= {"bbox", "segm"}), tasks
+        assert tasks is None or (len(tasks) and set(tasks) <= {"bbox", "segm", "keypoints"}), tasks
         self._gt = ground_truth
+        sigmas = np.asarray(kpt_oks_sigmas, dtype=np.float64).reshape(-1)
+        self._sigmas = sigmas if sigmas.size else COCO_KPT_OKS_SIGMAS
+        self._dev_sigmas = None
         self._class_names = None if class_names is None else list(class_names)
         self._given_tasks = None if tasks is None else tuple(tasks)
         self._device = torch.device(device)
@@ -315,14 +426,43 @@ class COCOEvaluator(DatasetEvaluator):
 
     def reset(self):
         self._tasks = self._given_tasks
-        self._state, self._records, self._seen, self._padded = {}, {"bbox": [], "segm": []}, set(), set()
+        self._state, self._seen, self._padded = {}, set(), set()
+        self._records = {"bbox": [], "segm": [], "keypoints": []}
         self._num_predictions = 0
         self.last_eval = {}
 
     def _state_of(self, task):
         if task not in self._state:
-            self._state[task] = new_state(self._gt.num_categories, self._device)
+            self._state[task] = new_state(self._gt.num_categories, self._device, keypoints=task == "keypoints")
         return self._state[task]
+
+    def _upload_keypoints(self, image_id, pred_keypoints):
+        """The image's ground truth for the keypoints task; the numbers of sigmas, predicted and ground-truth keypoints
+        must agree (the reference asserts it, coco_evaluation.py:561-570)."""
+        if not self._gt.has_keypoints(image_id):
+            raise ValueError("keypoints evaluation needs ground-truth keypoints: %s has none"
+                             % self._gt.missing_keypoints.get(image_id, "image %r" % (image_id,)))
+        it = self._gt[image_id]
+        P, G = len(self._sigmas), len(it["cats"])
+        if P > MAX_KEYPOINTS:
+            raise ValueError("%d keypoint sigmas (at most %d)" % (P, MAX_KEYPOINTS))
+        counts = dict(sigmas=P)
+        if pred_keypoints is not None:
+            counts["predictions"] = int(pred_keypoints.shape[1])
+        if it["keypoints"] is not None:
+            counts["ground truth"] = int(it["keypoints"].shape[1])
+        if len(set(counts.values())) != 1:
+            raise ValueError("image %r: the numbers of keypoints differ: %s" % (
+                image_id, ", ".join("%s %d" % kv for kv in counts.items())))
+        gt = self._upload(image_id, False)
+        kp = it["keypoints"] if it["keypoints"] is not None else np.zeros((0, P, 3))
+        nk = it["num_keypoints"] if it["num_keypoints"] is not None else np.zeros(0, np.int64)
+        gt["keypoints"] = torch.from_numpy(kp).to(self._device)
+        gt["ignore"] = torch.from_numpy(((it["iscrowd"] != 0) | (nk == 0)).astype(np.uint8)).to(self._device)
+        assert gt["ignore"].numel() == G
+        if self._dev_sigmas is None:
+            self._dev_sigmas = torch.from_numpy(self._sigmas).to(self._device)
+        return gt
 
     def _upload(self, image_id, segm):
         it = self._gt[image_id]
@@ -339,7 +479,8 @@ class COCOEvaluator(DatasetEvaluator):
 
     def process(self, inputs, outputs):
         """outputs[i]["instances"]: pred_boxes (Boxes or (n,4) tensor, XYXY), scores, pred_classes (contiguous category
-        indices) and optionally pred_masks (n,H,W) bool at the ground truth's resolution, on the device."""
+        indices) and optionally pred_masks (n,H,W) bool at the ground truth's resolution and pred_keypoints (n,P,3)
+        float32 (x, y, score), on the device.  Nothing of the Instances is written."""
         for inp, out in zip(inputs, outputs):
             if "instances" not in out:
                 continue
@@ -350,12 +491,24 @@ class COCOEvaluator(DatasetEvaluator):
                 raise ValueError("image_id %r was processed twice" % (image_id,))
             inst = out["instances"]
             if self._tasks is None:
-                self._tasks = ("bbox", "segm") if inst.has("pred_masks") else ("bbox",)
+                self._tasks = ("bbox",) + (("segm",) if inst.has("pred_masks") else ()) + \
+                    (("keypoints",) if inst.has("pred_keypoints") else ())
             boxes = inst.pred_boxes
             boxes = (boxes.tensor if hasattr(boxes, "tensor") else boxes).reshape(-1, 4).to(torch.float32)
             scores, classes = inst.scores.to(torch.float32), inst.pred_classes.to(torch.int32)
             n = scores.numel()
             for task in self._tasks:
+                if task == "keypoints":
+                    if not inst.has("pred_keypoints"):
+                        raise ValueError("keypoints evaluation needs pred_keypoints (image %r)" % (image_id,))
+                    kp = inst.pred_keypoints.to(torch.float32)
+                    if kp.dim() != 3 or kp.shape[0] != n or kp.shape[2] != 3:
+                        raise ValueError("image %r: pred_keypoints of shape %s" % (image_id, tuple(kp.shape)))
+                    gt = self._upload_keypoints(image_id, kp)
+                    self._records[task].append(coco_image_keypoints(
+                        boxes, scores, classes, kp, gt, self._dev_sigmas, self._index[image_id],
+                        self._state_of(task))["records"])
+                    continue
                 if task == "segm" and not inst.has("pred_masks"):
                     raise ValueError("segm evaluation needs pred_masks (image %r)" % (image_id,))
                 segm = task == "segm" and n > 0       # (without detections only npos is touched: no masks needed)
@@ -383,19 +536,28 @@ class COCOEvaluator(DatasetEvaluator):
         for image_id, i in self._index.items():
             if image_id in self._seen or len(self._gt[image_id]["cats"]) == 0:
                 continue
+            if task == "keypoints":                                # (only areas and ignore flags matter)
+                gt = self._upload_keypoints(image_id, None)
+                P = len(self._sigmas)
+                coco_image_keypoints(empty["b"], empty["s"], empty["c"],
+                                     torch.zeros(0, P, 3, dtype=torch.float32, device=self._device), gt,
+                                     self._dev_sigmas, i, state)
+                continue
             gt = self._upload(image_id, False)                     # (only areas and crowd flags matter)
             coco_image(empty["b"], empty["s"], empty["c"], None, gt, i, state)
 
     def evaluate(self):
-        """-> {"bbox": {AP, AP50, AP75, APs, APm, APl[, AP-<name> ...]}, "segm": {...}}, values x100 (NaN where a
-        metric has no entry, and for every metric when there was no prediction at all).  `last_eval[task]` holds
-        precision, scores, recall, npos and the twelve summary stats."""
+        """-> {"bbox": {AP, AP50, AP75, APs, APm, APl[, AP-<name> ...]}, "segm": {...}, "keypoints": {AP, AP50, AP75,
+        APm, APl[, AP-<name> ...]}}, values x100 (NaN where a metric has no entry, and for every metric when there was
+        no prediction at all).  `last_eval[task]` holds precision, scores, recall, npos and the summary stats: twelve,
+        or for keypoints ten, with three area ranges and one maxDets entry in the tables."""
         results = OrderedDict()
         tasks = self._tasks if self._tasks is not None else ("bbox",)
         K = self._gt.num_categories
         for task in tasks:
+            kpts = task == "keypoints"
             if self._num_predictions == 0:
-                results[task] = derive_coco_results(None, None)
+                results[task] = derive_coco_results(None, None, metrics=KP_METRICS if kpts else METRICS)
                 continue
             if task not in self._padded:                      # (a second evaluate() must not count them again)
                 self._add_unprocessed(task)
@@ -406,12 +568,15 @@ class COCOEvaluator(DatasetEvaluator):
             host = torch.cat([out["tables"], state["npos"].reshape(-1).view(torch.float64),
                               state["stats"].view(torch.float64)]).cpu()                    # the one read-back
             big = out["tables"].numel()
-            precision, scores, recall = split_tables(host[:big], K)
+            precision, scores, recall = split_tables(host[:big], K, len(KP_MAX_DETS if kpts else MAX_DETS))
             npos = host[big:big + K * NUM_AREAS].numpy().view(np.int64).reshape(K, NUM_AREAS)
             bad = int(host[big + K * NUM_AREAS:].numpy().view(np.int64)[0])
             if bad:
                 raise ValueError("%d detections carry a class outside [0, %d)" % (bad, K))
-            stats = summarize(precision, recall)
+            if kpts:                                          # the spare fourth area range of the device's records
+                precision, scores = precision[:, :, :, :KP_NUM_AREAS], scores[:, :, :, :KP_NUM_AREAS]
+                recall, npos = recall[:, :, :KP_NUM_AREAS], npos[:, :KP_NUM_AREAS]
+            stats = summarize_keypoints(precision, recall) if kpts else summarize(precision, recall)
             self.last_eval[task] = dict(precision=precision, scores=scores, recall=recall, npos=npos, stats=stats)
-            results[task] = derive_coco_results(stats, precision, self._class_names)
+            results[task] = derive_coco_results(stats, precision, self._class_names, KP_METRICS if kpts else METRICS)
         return results

@@ -8,6 +8,8 @@ Prints one JSON line and writes it to `--out`: device milliseconds per COCOEvalu
 and for bbox + segm (hipEvents around a pass over all images after `--warmup` images; a call is the Python wrapper, the
 upload of the image's ground truth, the workspace allocation and every launch), milliseconds per evaluate() for both
 tasks, the bytes of predicted masks an image has to read over the segm time as a share of the measured HBM copy rate,
+the same two figures for the keypoints task alone at that shape (one `person` category, 17 keypoints with the COCO
+sigmas, 20 kept detections and the same number of objects per image, each detected a few times with jitter),
 and the host seconds of the NumPy restatement (tests/coco_eval_ref.py) on the first `--host-images` images with whether
 the device's tables for those images agree bit for bit.  Needs the GPU; there is no fallback.
 
@@ -27,6 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 H, W, N_IMAGES, K, N_DET = 480, 640, 5000, 80, 100
+N_KEYPOINTS, N_DET_KP = 17, 20
 HBM_COPY_BYTES_PER_S = 6.29e12          # the measured float4 copy rate of the MI355X (8.0 TB/s on paper)
 
 
@@ -56,6 +59,31 @@ def pool_entry(rng):
                 det_classes=np.array(classes, np.int64))
 
 
+def keypoint_pool_entry(rng):
+    """-> dict of NumPy arrays for one pool image of the keypoints task: 3 to 11 persons (gt_boxes XYWH, gt_area,
+    gt_crowd, gt_keypoints (G,17,3) with about a fifth of the points unlabelled and now and then a person without
+    any), 20 detections (det_boxes XYXY float32, det_keypoints (20,17,3) float32): a person's points with jitter."""
+    G = int(rng.integers(3, 12))
+    gb, gk = [], []
+    for _ in range(G):
+        w, h = rng.uniform(30, 200), rng.uniform(60, 400)
+        x, y = rng.uniform(0, W - w), rng.uniform(0, max(H - h, 1))
+        xy = np.array([x, y]) + rng.random((N_KEYPOINTS, 2)) * np.array([w, h])
+        v = rng.choice([0.0, 1.0, 2.0], N_KEYPOINTS, p=[0.2, 0.2, 0.6]) * (rng.random() > 0.1)
+        gb.append([x, y, w, h])
+        gk.append(np.concatenate([np.round(xy), v[:, None]], 1))
+    gb, gk = np.array(gb, np.float64), np.array(gk, np.float64)
+    boxes, kps = [], []
+    for k in range(N_DET_KP):
+        b, kp = gb[k % G], gk[k % G]
+        j = rng.normal(0, 0.03, (N_KEYPOINTS, 2)) * b[2:]
+        boxes.append([b[0], b[1], b[0] + b[2], b[1] + b[3]])
+        kps.append(np.concatenate([kp[:, :2] + 0.5 + j, rng.random((N_KEYPOINTS, 1))], 1))
+    return dict(gt_cats=np.zeros(G, np.int64), gt_boxes=gb, gt_area=gb[:, 2] * gb[:, 3] * 0.5,
+                gt_crowd=(rng.random(G) < 0.05).astype(np.uint8), gt_keypoints=gk,
+                det_boxes=np.array(boxes, np.float32), det_keypoints=np.array(kps, np.float32))
+
+
 def rasterise(boxes_xyxy, dev):
     """(n,4) boxes -> (n,H,W) bool rectangles on the device (rounded to pixel edges)."""
     b = torch.as_tensor(np.asarray(boxes_xyxy, np.float32)).to(dev).round()
@@ -63,6 +91,43 @@ def rasterise(boxes_xyxy, dev):
     yy = torch.arange(H, device=dev).view(1, H, 1)
     x0, y0, x1, y1 = (b[:, k].view(-1, 1, 1) for k in range(4))
     return (xx >= x0) & (xx < x1) & (yy >= y0) & (yy < y1)
+
+
+def keypoints_run(a, dev, rng, ids):
+    """The keypoints task alone, timed as the other two -> (ms per process() image, ms per evaluate(), results)."""
+    from jtsm_amd.evaluation import COCOEvaluator, COCOGroundTruth
+    from jtsm_amd.structures import Boxes, Instances
+
+    pool = [keypoint_pool_entry(rng) for _ in range(a.pool)]
+    for p in pool:
+        p["dev_boxes"] = torch.from_numpy(p["det_boxes"]).to(dev)
+        p["dev_keypoints"] = torch.from_numpy(p["det_keypoints"]).to(dev)
+        p["dev_classes"] = torch.zeros(N_DET_KP, dtype=torch.int64, device=dev)
+    scores = torch.from_numpy((rng.integers(1, 1000, (a.images, N_DET_KP)) / 1000.0).astype(np.float32)).to(dev)
+    gt = COCOGroundTruth(1)
+    for i in range(a.images):
+        p = pool[i % a.pool]
+        gt.add(ids[i], p["gt_cats"], p["gt_boxes"], p["gt_area"], p["gt_crowd"], keypoints=p["gt_keypoints"])
+
+    def one(ev, i):
+        p = pool[i % a.pool]
+        ev.process([{"image_id": ids[i]}], [{"instances": Instances(
+            (H, W), pred_boxes=Boxes(p["dev_boxes"]), scores=scores[i], pred_classes=p["dev_classes"],
+            pred_keypoints=p["dev_keypoints"])}])
+
+    for i in range(min(a.warmup, a.images)):                           # warm-up on a throw-away evaluator
+        one(COCOEvaluator(gt, tasks=("keypoints",), device=dev), i)
+    ev = COCOEvaluator(gt, tasks=("keypoints",), device=dev)
+    torch.cuda.synchronize()
+    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    e[0].record()
+    for i in range(a.images):
+        one(ev, i)
+    e[1].record()
+    res = ev.evaluate()
+    e[2].record()
+    torch.cuda.synchronize()
+    return e[0].elapsed_time(e[1]) / max(a.images, 1), e[1].elapsed_time(e[2]), res
 
 
 def main():
@@ -127,6 +192,7 @@ def main():
     gt_masks = ground_truth(a.images, True)
     bbox_ms, bbox_eval_ms, _, res_b = run(a.images, False, gt_masks)
     both_ms, both_eval_ms, _, res_s = run(a.images, True, gt_masks)
+    kp_ms, kp_eval_ms, res_k = keypoints_run(a, dev, rng, ids)
     mask_bytes = N_DET * H * W
     segm_ms = max(both_ms - bbox_ms, 1e-9)
     line = {"workload": "COCO val2017 shape: %d images of %d x %d, %d categories, %d detections and %.1f ground-truth "
@@ -138,6 +204,10 @@ def main():
             "pred_mask_bytes_per_image": mask_bytes,
             "segm_share_of_hbm_copy_rate": round(mask_bytes / (segm_ms * 1e-3) / HBM_COPY_BYTES_PER_S, 4),
             "hbm_copy_rate_bytes_per_s": HBM_COPY_BYTES_PER_S,
+            "keypoints_workload": "one category, %d keypoints (COCO sigmas), %d detections per image"
+                                  % (N_KEYPOINTS, N_DET_KP),
+            "process_image_keypoints_ms": round(kp_ms, 4), "evaluate_keypoints_ms": round(kp_eval_ms, 3),
+            "keypoints": {k: round(v, 4) for k, v in res_k["keypoints"].items()},
             "bbox": {k: round(v, 4) for k, v in res_b["bbox"].items()},
             "segm": {k: round(v, 4) for k, v in res_s["segm"].items()}}
     if not a.skip_host:
