@@ -223,10 +223,11 @@ int jtsm_moi_pool_backward_f16(const uint16_t* grad, const uint16_t* rois, const
  * pointers, nlevels <= 8); roi_level[n] in [0,nlevels) picks roi n's map; output / argmax as above (NHWC).
  * Backward: with `scales` (the forward's level scales), a workspace
  * (jtsm_moi_pool_backward_levels_workspace_bytes) and C a multiple of 256, every gradient map is produced by a
- * gather — one workgroup per 8x8-cell tile sums, in roi / bin order, the gradients of the bins whose argmax fell
- * into it (LDS accumulation, no atomics, bitwise reproducible, every cell written once) — unless a census of the
- * roi boxes estimates more than 4000 (roi, bin) pairs on one tile (proposals piled on one spot), in which case, and otherwise (scales or workspace NULL)
- * each grad_inputs[l] is zero-filled and accumulated with float atomics. */
+ * gather — one workgroup per 8x8-cell tile (per 4x4-cell quadrant of a tile with an estimated 1024 pairs or more)
+ * sums, in a fixed order, the gradients of the bins whose argmax fell into it (LDS accumulation, no atomics, bitwise
+ * reproducible, every cell written once) — unless a census of the roi boxes estimates more than 64000 (roi, bin)
+ * pairs on one tile (proposals piled on one spot), in which case, and otherwise (scales or workspace NULL), each
+ * grad_inputs[l] is zero-filled and accumulated with float atomics. */
 size_t jtsm_moi_pool_levels_workspace_bytes(int B, const int* H, const int* W, int nlevels, int M, int L);
 int jtsm_moi_pool_forward_levels_f32(const float* const* inputs, const int* H, const int* W,
                                      const float* scales, int nlevels, const float* rois,
@@ -726,7 +727,7 @@ int jtsm_mask_bce_backward_f32(const float* logits, int ld, int num_classes, con
  * scatter per level (detectron2/modeling/poolers.py:236-247,
  * projects/WSL/wsl/modeling/poolers.py:300-320), without the host synchronisation: every
  * level's launch walks ALL M rois and serves only those with roi_level[m] == level, reading
- * that level's feature map and writing rows m of the shared (M,PH,PW,C) output (argmax) /
+ * that level's feature map and writing rows m of the shared (M,PH,PW,C) output /
  * scattering rows m of the shared gradient into that level's grad_input (zero-filled by the
  * call).  Rows of other levels are left untouched.
  * ------------------------------------------------------------------------- */
@@ -764,14 +765,6 @@ int jtsm_roi_align_backward_levels_f32(const float* grad, const float* rois, con
                                        int nlevels, int B, int C, int M, int pooled_h, int pooled_w, int sampling_ratio,
                                        int aligned, int accumulate, void* workspace, size_t workspace_bytes,
                                        void* stream);
-int jtsm_moi_pool_forward_level_f32(const float* input, const float* rois, const int32_t* roi_level,
-                                    int level, const int32_t* oh_labels, const int32_t* superpixels,
-                                    float* output, int32_t* argmax, void* workspace, int B, int C,
-                                    int H, int W, int M, int L, int Hs, int Ws, float spatial_scale,
-                                    int pooled_h, int pooled_w, void* stream);
-int jtsm_moi_pool_backward_level_f32(const float* grad, const float* rois, const int32_t* roi_level,
-                                     int level, const int32_t* argmax, float* grad_input, int B, int C,
-                                     int H, int W, int M, int pooled_h, int pooled_w, void* stream);
 
 
 /* ---------------------------------------------------------------------------

@@ -23,6 +23,8 @@
 #include <cfloat>
 
 #include "common.h"
+#include "pool_bins.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
@@ -42,8 +44,6 @@ __device__ __forceinline__ IBox round_box(const float* __restrict__ roi, float s
   r.y1 = (int)roundf(roi[4] * scale);
   return r;
 }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // cell_bits[(b*H+h)*W+w][words]: a wavefront sweeps the image block under a cell (MOIPool_cuda.cu:175-186 bounds),
 // OR-ing id bits into an LDS row, then stores the row.  `cpw` cells share a wavefront (64 / cpw lanes each): at stride 4
@@ -186,16 +186,7 @@ static bool moi_bits_small_ok(int H, int W, int Hs, int Ws) {
   return k == Ws / W && (k & (k - 1)) == 0 && k <= 8;
 }
 
-__global__ __launch_bounds__(256) void moi_cell_bits_kernel(const int* __restrict__ superpixels,
-                                                            unsigned* __restrict__ cell_bits,
-                                                            int B, int H, int W, int Hs, int Ws,
-                                                            int L, int words, int cpw) {
-  extern __shared__ __attribute__((aligned(16))) unsigned smem[];
-  if (cpw == 0) moi_cell_bits_small_any(superpixels, cell_bits, B, H, W, Hs, Ws, L, words, (long)blockIdx.x);
-  else moi_cell_bits_block(superpixels, cell_bits, B, H, W, Hs, Ws, L, words, cpw, (long)blockIdx.x, smem);
-}
-
-// cells that share a wavefront in moi_cell_bits_kernel: 64 / (pixels under a cell, rounded up to a power of two)
+// cells that share a wavefront in moi_cell_bits_block: 64 / (pixels under a cell, rounded up to a power of two)
 static int moi_cells_per_wave(int H, int W, int Hs, int Ws) {
   const long npix = (long)ceil_div(Hs, H > 0 ? H : 1) * ceil_div(Ws, W > 0 ? W : 1);
   int cpw = 1;
@@ -224,14 +215,8 @@ __device__ __forceinline__ void moi_roi_bits_block(const int* __restrict__ oh_la
   }
 }
 
-__global__ __launch_bounds__(256) void moi_roi_bits_kernel(const int* __restrict__ oh_labels,
-                                                           unsigned* __restrict__ roi_bits,
-                                                           long M, int L, int words) {
-  moi_roi_bits_block(oh_labels, roi_bits, M, L, words, (long)blockIdx.x);
-}
-
-// Both bit tables of a multi-level call in ONE launch (five launches of 10-15 us each before: four levels' cell bits
-// and the roi bits): the grid is the concatenation of the per-level cell-bit grids and the roi-bit grid.
+// Both bit tables of a call in ONE launch (five launches of 10-15 us each before, on four levels: their cell bits and
+// the roi bits): the grid is the concatenation of the per-level cell-bit grids and the roi-bit grid.
 struct MoiBitsPlan {
   unsigned* cell[8];
   int H[8], W[8], cpw[8];
@@ -330,23 +315,28 @@ struct BinRange { int hs, he, ws, we; };
 __device__ __forceinline__ BinRange bin_range(const IBox& r, int ph, int pw, int PH, int PW,
                                               int H, int W) {
 #pragma clang fp contract(off)
-  const int rw = max(r.x1 - r.x0 + 1, 1), rh = max(r.y1 - r.y0 + 1, 1);
-  const float bh = (float)rh / (float)PH, bw = (float)rw / (float)PW;
+  const float bh = bin_size(r.y0, r.y1, PH), bw = bin_size(r.x0, r.x1, PW);
   BinRange q;
-  q.hs = clampi((int)floorf((float)ph * bh) + r.y0, 0, H);
-  q.he = clampi((int)ceilf((float)(ph + 1) * bh) + r.y0, 0, H);
-  q.ws = clampi((int)floorf((float)pw * bw) + r.x0, 0, W);
-  q.we = clampi((int)ceilf((float)(pw + 1) * bw) + r.x0, 0, W);
+  q.hs = clampi(bin_lo(ph, bh, r.y0), 0, H);
+  q.he = clampi(bin_hi(ph, bh, r.y0), 0, H);
+  q.ws = clampi(bin_lo(pw, bw, r.x0), 0, W);
+  q.we = clampi(bin_hi(pw, bw, r.x0), 0, W);
   return q;
 }
+// [lo, hi) of bin p on one axis, clipped to the map [0, n) AND to the rounded (inclusive) box [s, e]: the rows form walks
+// only cells that pass both tests
+__device__ __forceinline__ void boxed_bin(int p, float bin, int s, int e, int n, int& lo, int& hi) {
+  lo = max(clampi(bin_lo(p, bin, s), 0, n), s);
+  hi = min(clampi(bin_hi(p, bin, s), 0, n), e + 1);
+}
 
-// any(cell_bits & roi_bits) for one cell, evaluated by the whole wave.
-__device__ __forceinline__ bool cell_hit(const unsigned* __restrict__ cell_row,
-                                         const unsigned* __restrict__ roi_row, unsigned mine,
-                                         int words, int lane) {
-  unsigned hit = (lane < words) ? (cell_row[lane] & mine) : 0u;
-  for (int i = 64 + lane; i < words; i += 64) hit |= cell_row[i] & roi_row[i];
-  return __ballot(hit != 0u) != 0ull;
+// mois[n,h,w] by one thread: inside the rounded (inclusive) box and any(cell_bits & roi_bits)
+__device__ __forceinline__ bool moi_cell_set(const IBox& r, int h, int w, const unsigned* __restrict__ cell_row,
+                                             const unsigned* __restrict__ roi_row, int words) {
+  if (!(w >= r.x0 && w <= r.x1 && h >= r.y0 && h <= r.y1)) return false;
+  unsigned hit = 0u;
+  for (int i = 0; i < words && !hit; ++i) hit = cell_row[i] & roi_row[i];
+  return hit != 0u;
 }
 
 template <int VEC>
@@ -435,24 +425,8 @@ __device__ __forceinline__ void moi_pool_wave(
   }
 }
 
-template <int VEC>
-__global__ __launch_bounds__(256) void moi_pool_fwd_nhwc(
-    const float* __restrict__ in, const float* __restrict__ rois,
-    const unsigned* __restrict__ cell_bits, const unsigned* __restrict__ roi_bits,
-    float* __restrict__ out, int* __restrict__ argmax, int C, int H, int W, int M, int words,
-    float scale, int PH, int PW, const int* __restrict__ roi_level, int level) {
-  const int nbins = PH * PW;
-  // (readfirstlane: the wavefront index is uniform, but the compiler cannot see that through threadIdx — with it
-  // the roi / bin / address arithmetic below runs on the scalar unit instead of once per lane)
-  const long wave = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (wave >= (long)M * nbins) return;
-  if (roi_level && roi_level[wave / nbins] != level) return;  // FPN: this roi lives on another level
-  const int n = (int)(wave / nbins), bin = (int)(wave - (long)n * nbins);
-  moi_pool_wave<VEC>(in, rois, cell_bits, roi_bits, out, argmax, C, H, W, words, scale, PH, PW, n, bin,
-                     threadIdx.x & 63);
-}
-
-// All FPN levels in one launch: each roi reads the map of its own level.
+// All FPN levels in one launch: each roi reads the map of its own level.  The single-level entry points run the same
+// kernels on a table of one level; roi_level == nullptr puts every roi on level 0.
 constexpr int kMaxLevels = 8;
 struct MoiLevels {
   const float* in[kMaxLevels];
@@ -472,16 +446,15 @@ __global__ __launch_bounds__(256) void moi_pool_fwd_levels(
   // pairs, so that the bins of a roi — which share a third of their cells — and neighbouring rois meet in one L2
   // (dealt out pair by pair every XCD fetched every roi's cells: 1.86 GB of fabric traffic per launch for 0.6 GB of
   // distinct bytes).  Speed only: any placement computes the same result.
-  const unsigned nblk = gridDim.x, per = (nblk + 7) / 8, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+  const unsigned nblk = gridDim.x, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
   const unsigned q = nblk >> 3, r8 = nblk & 7;   // XCDs 0 .. r8-1 hold q + 1 workgroups, the rest q
   const unsigned blk = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + idx;
-  (void)per;
   // (readfirstlane: the wavefront index is uniform, but the compiler cannot see that through threadIdx — with it
   // the roi / bin / address arithmetic below runs on the scalar unit instead of once per lane)
   const long wave = (long)blk * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (wave >= (long)M * nbins) return;
   const int n = (int)(wave / nbins), bin = (int)(wave - (long)n * nbins);
-  const int l = roi_level[n];
+  const int l = roi_level ? roi_level[n] : 0;
   if ((unsigned)l >= (unsigned)nlevels) return;
   moi_pool_wave<VEC>(lv.in[l], rois, lv.cell[l], roi_bits, out, argmax, C, lv.H[l], lv.W[l], words, lv.scale[l],
                      PH, PW, n, bin, threadIdx.x & 63);
@@ -513,7 +486,7 @@ template <int VEC, int AHEAD, int PWT, int W4, int NW, bool PIPE>
 __global__ __launch_bounds__(64 * NW) void moi_pool_fwd_rows(
     const MoiLevels lv, const float* __restrict__ rois, const unsigned* __restrict__ roi_bits,
     float* __restrict__ out, int* __restrict__ argmax, int C, int M, int words, int PH,
-    const int* __restrict__ roi_level, int nlevels, int only_level, const int* __restrict__ order, unsigned chunk) {
+    const int* __restrict__ roi_level, int nlevels, const int* __restrict__ order, unsigned chunk) {
 #pragma clang fp contract(off)
   __shared__ unsigned hit_list[NW][kRowsList];
   const int lane = threadIdx.x & 63;
@@ -533,29 +506,16 @@ __global__ __launch_bounds__(64 * NW) void moi_pool_fwd_rows(
   const long np = wave / ncb;
   const int slot = (int)(np / PH), ph = (int)(np - (long)slot * PH);
   const int n = order ? order[slot] : slot;        // (spatial order of the rois: moi_sort_block)
-  int l = 0;
-  if (roi_level) {
-    l = roi_level[n];
-    if (only_level >= 0) {
-      if (l != only_level) return;     // FPN, per-level entry point: this roi lives on another level
-      l = 0;
-    } else if ((unsigned)l >= (unsigned)nlevels) {
-      return;
-    }
-  }
+  const int l = roi_level ? roi_level[n] : 0;
+  if ((unsigned)l >= (unsigned)nlevels) return;
   const int H = lv.H[l], W = lv.W[l];
   const IBox r = round_box(rois + (size_t)n * 5, lv.scale[l]);
-  const int rw = max(r.x1 - r.x0 + 1, 1), rh = max(r.y1 - r.y0 + 1, 1);
-  const float bh = (float)rh / (float)PH, bw = (float)rw / (float)PWT;
+  const float bh = bin_size(r.y0, r.y1, PH), bw = bin_size(r.x0, r.x1, PWT);
   // rows of this bin row inside the rounded (inclusive) box and the map; column ranges of its PWT bins likewise
-  const int hs = max(clampi((int)floorf((float)ph * bh) + r.y0, 0, H), r.y0);
-  const int he = min(clampi((int)ceilf((float)(ph + 1) * bh) + r.y0, 0, H), r.y1 + 1);
-  int wsb[PWT], web[PWT];
+  int hs, he, wsb[PWT], web[PWT];
+  boxed_bin(ph, bh, r.y0, r.y1, H, hs, he);
 #pragma unroll
-  for (int pw = 0; pw < PWT; ++pw) {
-    wsb[pw] = max(clampi((int)floorf((float)pw * bw) + r.x0, 0, W), r.x0);
-    web[pw] = min(clampi((int)ceilf((float)(pw + 1) * bw) + r.x0, 0, W), r.x1 + 1);
-  }
+  for (int pw = 0; pw < PWT; ++pw) boxed_bin(pw, bw, r.x0, r.x1, W, wsb[pw], web[pw]);
   const int cx0 = clampi(r.x0, 0, W), cx1 = clampi(r.x1 + 1, 0, W);
   const int nbr = (cx1 - cx0 + 63) >> 6;                       // batches of 64 cells per row
   const int nrows = he > hs ? he - hs : 0;
@@ -708,33 +668,33 @@ static bool moi_sort_on() {
 
 template <int AHEAD, int W4>
 static void launch_fwd_rows_w(const MoiLevels& lv, const float* rois, const unsigned* roi_bits, float* out, int* argmax,
-                              int C, int M, int words, int PH, const int* roi_level, int nlevels, int only_level,
+                              int C, int M, int words, int PH, const int* roi_level, int nlevels,
                               const int* order, hipStream_t st) {
   const long waves = (long)M * PH * ceil_div(C, 256);
   const unsigned chunk = moi_rows_chunk();
   const long round = 8 * (long)chunk;                           // (workgroups beyond the last wavefront leave at once)
   hipLaunchKernelGGL((moi_pool_fwd_rows<4, AHEAD, 7, W4, 4, false>), dim3(ceil_div(ceil_div(waves, 4), round) * round), dim3(256), 0, st, lv, rois,
-                     roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, only_level, order, chunk);
+                     roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, order, chunk);
 }
 template <int AHEAD>
 static void launch_fwd_rows_as(const MoiLevels& lv, const float* rois, const unsigned* roi_bits, float* out, int* argmax,
-                               int C, int M, int words, int PH, const int* roi_level, int nlevels, int only_level,
+                               int C, int M, int words, int PH, const int* roi_level, int nlevels,
                                const int* order, hipStream_t st) {
   switch (words) {      // (moi_fwd_rows_words_ok: 4, 8, 16, 32 or 64 words = up to 128 ... 2048 superpixel ids)
-    case 4: return launch_fwd_rows_w<AHEAD, 1>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, only_level, order, st);
-    case 8: return launch_fwd_rows_w<AHEAD, 2>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, only_level, order, st);
-    case 16: return launch_fwd_rows_w<AHEAD, 4>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, only_level, order, st);
-    case 64: return launch_fwd_rows_w<AHEAD, 16>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, only_level, order, st);
-    default: return launch_fwd_rows_w<AHEAD, 8>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, only_level, order, st);
+    case 4: return launch_fwd_rows_w<AHEAD, 1>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, order, st);
+    case 8: return launch_fwd_rows_w<AHEAD, 2>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, order, st);
+    case 16: return launch_fwd_rows_w<AHEAD, 4>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, order, st);
+    case 64: return launch_fwd_rows_w<AHEAD, 16>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, order, st);
+    default: return launch_fwd_rows_w<AHEAD, 8>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, order, st);
   }
 }
 static bool moi_fwd_rows_words_ok(int words) { return words == 4 || words == 8 || words == 16 || words == 32 || words == 64; }
 static void launch_fwd_rows(const MoiLevels& lv, const float* rois, const unsigned* roi_bits, float* out, int* argmax, int C,
-                            int M, int words, int PH, const int* roi_level, int nlevels, int only_level, const int* order,
+                            int M, int words, int PH, const int* roi_level, int nlevels, const int* order,
                             hipStream_t st) {
   if (moi_fwd_rows_mode() == 2)
-    return launch_fwd_rows_as<4>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, only_level, order, st);
-  return launch_fwd_rows_as<8>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, only_level, order, st);
+    return launch_fwd_rows_as<4>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, order, st);
+  return launch_fwd_rows_as<8>(lv, rois, roi_bits, out, argmax, C, M, words, PH, roi_level, nlevels, order, st);
 }
 
 // grad_input[level(n)][b, argmax, c] += grad[n, bin, c]: a wavefront per (roi, bin).
@@ -747,7 +707,7 @@ __global__ __launch_bounds__(256) void moi_pool_bwd_levels(
   for (long wave = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); wave < (long)M * nbins;
        wave += (long)gridDim.x * 4) {
     const int n = (int)(wave / nbins);
-    const int l = roi_level[n];
+    const int l = roi_level ? roi_level[n] : 0;
     if ((unsigned)l >= (unsigned)nlevels) continue;
     const int b = (int)rois[(size_t)n * 5];
     float* __restrict__ g = lv.gin[l] + (size_t)b * lv.H[l] * lv.W[l] * C;
@@ -762,19 +722,13 @@ __global__ __launch_bounds__(256) void moi_pool_bwd_levels(
   }
 }
 
-// Gather form of the backward: a workgroup owns an 8 x 8-cell tile of one level's gradient map (x 256 channels, 64 KB
-// of LDS), finds the (roi, bin) pairs whose bin range touches the tile from the roi geometry alone, and adds their
-// gradients into LDS — thread c owns channel c, so there are no atomics, the order is the roi / bin order (bitwise
-// reproducible), and every cell of the map is written exactly once (no zero fill, no read-modify-write in L2; the
-// scatter form above spends its time in L2 atomic line operations).
+// The gather form of the backward (moi_gather_tile below) works on tiles of the levels' gradient maps:
 constexpr int kTile = 8;      // tile of the census and of the per-tile gather (cells, both axes)
-constexpr int kTileY = 8;
 constexpr int kQuad = 4;      // the busy-tile gather splits a tile into 2 x 2 quadrants of 4 x 4 cells
 struct MoiTiles {
   int first[kMaxLevels + 1];   // first workgroup of each level
   int tiles_x[kMaxLevels], tiles_y[kMaxLevels];
 };
-
 
 // rois of one (level, image), in index order: lists[(l * B + b) * M ...], counts[l * B + b].  One workgroup each.
 __global__ __launch_bounds__(256) void moi_roi_lists_kernel(const float* __restrict__ rois,
@@ -818,9 +772,9 @@ __global__ __launch_bounds__(256) void moi_tile_census_kernel(const MoiLevels lv
   const int H = lv.H[l], W = lv.W[l];
   const int xa = max(r.x0, 0), xz = min(r.x1, W - 1), ya = max(r.y0, 0), yz = min(r.y1, H - 1);
   if (xa > xz || ya > yz) return;
-  const float bw = (float)max(r.x1 - r.x0 + 1, 1) / (float)PW, bh = (float)max(r.y1 - r.y0 + 1, 1) / (float)PH;
-  for (int ty = ya / kTileY; ty <= yz / kTileY; ++ty) {
-    const int oy = min(yz, ty * kTileY + kTileY - 1) - max(ya, ty * kTileY) + 1;   // overlapped rows
+  const float bw = bin_size(r.x0, r.x1, PW), bh = bin_size(r.y0, r.y1, PH);
+  for (int ty = ya / kTile; ty <= yz / kTile; ++ty) {
+    const int oy = min(yz, ty * kTile + kTile - 1) - max(ya, ty * kTile) + 1;   // overlapped rows
     const int by = min(PH, (int)((float)oy / bh) + 2);                            // bins touching them (upper bound)
     for (int tx = xa / kTile; tx <= xz / kTile; ++tx) {
       const int ox = min(xz, tx * kTile + kTile - 1) - max(xa, tx * kTile) + 1;
@@ -830,74 +784,63 @@ __global__ __launch_bounds__(256) void moi_tile_census_kernel(const MoiLevels lv
   }
 }
 
-// Gather form, round 3.  What round 2's profile showed (rocprofv3 counters on the bench's proposals): the launch
-// averaged 2 resident wavefronts per CU — it was one long tail.  Proposals pile up on objects, small rois put all 49
-// bins of every piled roi on the same few cells, and a tile was ONE workgroup whose 256 threads (thread = channel)
-// added its ~2500 rows one dependent LDS read-modify-write after the other.  Now: (1) the maps are cleared by a memset
-// and only the tiles some box overlaps get a workgroup (the plan above), heaviest first, through a fixed grid that
-// strides the list; (2) a tile is 4 x 4 cells and its workgroup has 16 wavefronts: thread = (channel, copy), FOUR
-// copies of the tile in LDS, the row list dealt to the copies in batches of 16 rows, each copy's additions in list
-// order, the copies added in a fixed order at the end — still no atomics, still reproducible bit for bit; (3) a
-// batch's loads are in flight while the previous batch is applied.  (LDS float atomics — ds_add_f32, fire and forget —
-// were measured for the additions: 2-3x SLOWER than the plain read-modify-write.)
-constexpr int kPairCap = 1024;
+struct TileAt { int l, b, tx, ty; };
+__device__ __forceinline__ TileAt locate_tile(const MoiTiles& tl, int nlevels, int tile) {
+  TileAt a;
+  a.l = 0;
+  while (a.l + 1 < nlevels && tile >= tl.first[a.l + 1]) ++a.l;
+  int rel = tile - tl.first[a.l];
+  a.tx = rel % tl.tiles_x[a.l]; rel /= tl.tiles_x[a.l];
+  a.ty = rel % tl.tiles_y[a.l];
+  a.b = rel / tl.tiles_y[a.l];
+  return a;
+}
 
-// Gather form of the backward: a workgroup owns an 8 x 8-cell tile of one level's gradient map (x 256 channels, 64 KB
-// of LDS), finds the (roi, bin) pairs whose bin range touches the tile from the roi geometry alone, and adds their
-// gradients into LDS — thread c owns channel c, so there are no atomics, the order is the roi / bin order (bitwise
-// reproducible), and every cell of the map is written exactly once (no zero fill, no read-modify-write in L2; the
-// scatter form above spends its time in L2 atomic line operations).  Tiles no box overlaps (census 0: most of a call)
-// write their zeros at once, 16 bytes per lane; tiles at or above `heavy_min` (estimated) rows are left to
-// moi_pool_bwd_busy below.
-__global__ __launch_bounds__(256) void moi_pool_bwd_tiled(
-    const MoiLevels lv, const MoiTiles tl, const float* __restrict__ grad, const float* __restrict__ rois,
-    const int* __restrict__ argmax, int C, int M, int PH, int PW, int B, const int* __restrict__ lists,
-    const int* __restrict__ counts, int nlevels, const int* __restrict__ plan, const int* __restrict__ census,
-    int heavy_min, int accumulate, const int* __restrict__ tile_order) {
+// The gather of one tile: the workgroup's 256 * COPIES threads (thread = (channel, copy)) own the SIDE x SIDE cells at
+// (x0, y0) of level l, image b, channels [cb, cb + 256), with COPIES copies of the tile in LDS (`acc`, 64 KB).  It
+// finds the (roi, bin) pairs whose bin range touches the tile from the roi geometry alone and adds their gradients in
+// LDS, and every cell of the map is written exactly once (no zero fill, no read-modify-write in L2: the scatter form
+// above spends its time in L2 atomic line operations).  The rows are
+// dealt to the copies in batches of 16, each copy adds its rows in list order, and the copies are joined in a fixed
+// order at the end: still no atomics, still reproducible bit for bit.  A batch's loads are in flight while the
+// previous batch is applied.  (LDS float atomics — ds_add_f32, fire and forget — were measured for the additions:
+// 2-3x SLOWER than the plain read-modify-write.)
+//   <8, 1>  the light form: one long chain of dependent LDS read-modify-writes per channel, fine for a few hundred rows
+//   <4, 4>  the busy form.  What round 2's profile showed (rocprofv3 counters on the bench's proposals): the launch
+//           averaged 2 resident wavefronts per CU — it was one long tail.  Proposals pile up on objects, small rois
+//           put all 49 bins of every piled roi on the same few cells, and such a tile had ~2500 rows to add.
+// The pair list holds 1024 rows in the light form and 2048 in the busy one; where the list is drained decides which
+// copy a row goes to, so the busy form's capacity is part of its bitwise contract.
+template <int SIDE, int COPIES>
+__device__ __forceinline__ void moi_gather_tile(
+    const MoiLevels& lv, int l, int b, int x0, int y0, int cb, const float* __restrict__ grad,
+    const float* __restrict__ rois, const int* __restrict__ argmax, int C, int M, int PH, int PW, int B,
+    const int* __restrict__ lists, const int* __restrict__ counts, int accumulate, float* __restrict__ acc) {
 #pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) float acc[];   // [64 cells][256 channels]
+  static_assert(COPIES == 1 || COPIES == 4, "the copies are joined as a0 or (a0 + a1) + (a2 + a3)");
+  constexpr int kThreads = 256 * COPIES, kCells = SIDE * SIDE, kDepth = 16;
+  constexpr int kPairCap = COPIES == 1 ? 1024 : 2048;
   __shared__ int roi_list[256];
   __shared__ IBox roi_box[256];          // their rounded boxes (rounded once per roi, not once per (roi, bin))
-  __shared__ int pair_list[kPairCap];   // (roi * nbins + bin) rows whose bin range touches the tile, in order
-  __shared__ int wave_count[4];
-  const int t = threadIdx.x;
-  // workgroups start in index order: through the plan's permutation the heaviest tiles start first (tile_plan_kernel)
-  const int tile = tile_order ? tile_order[blockIdx.x] : (int)blockIdx.x;
-  int l = 0;
-  while (l + 1 < nlevels && tile >= tl.first[l + 1]) ++l;
-  const int H = lv.H[l], W = lv.W[l];
-  int rel = tile - tl.first[l];
-  const int tx = rel % tl.tiles_x[l]; rel /= tl.tiles_x[l];
-  const int ty = rel % tl.tiles_y[l];
-  const int b = rel / tl.tiles_y[l];
-  const int x0 = tx * kTile, y0 = ty * kTile, x1 = min(x0 + kTile, W) - 1, y1 = min(y0 + kTile, H) - 1;
-  const int c = blockIdx.y * 256 + t;
+  __shared__ int pair_list[kPairCap];    // (roi * nbins + bin) rows whose bin range touches the tile, in order
+  __shared__ int wave_count[4 * COPIES];
+  const int t = threadIdx.x, ch = COPIES > 1 ? t & 255 : t, copy = COPIES > 1 ? t >> 8 : 0;
+  const int H = lv.H[l], W = lv.W[l], nbins = PH * PW;
+  const int x1 = min(x0 + SIDE, W) - 1, y1 = min(y0 + SIDE, H) - 1;
+  const int c = cb + ch;
   const float scale = lv.scale[l];
-  const int nbins = PH * PW;
   float* __restrict__ out = lv.gin[l] + (size_t)b * H * W * C;
-  const int load = census[tile];
-  const bool fallback = plan[0] > kCensusLimit;   // too many rois on one tile somewhere: the scatter form adds into zeros
-  if (load == 0 || fallback) {
-    if (accumulate) return;   // the map holds another consumer's gradient: nothing to add here (the scatter form adds to it)
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = t; i < kTile * kTile * 64; i += 256) {
-      const int cell = i >> 6, y = y0 + cell / kTile, x = x0 + cell % kTile;
-      if (y <= y1 && x <= x1)
-        *reinterpret_cast<float4*>(out + ((size_t)y * W + x) * C + blockIdx.y * 256 + (i & 63) * 4) = z;
-    }
-    return;
-  }
-  if (load >= heavy_min) return;   // moi_pool_bwd_busy writes this tile
-  for (int i = t; i < kTile * kTile * 64; i += 256) reinterpret_cast<float4*>(acc)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  __syncthreads();                       // the previous tile's / channel block's readers of acc and the lists are done
+  for (int i = t; i < COPIES * kCells * 64; i += kThreads) reinterpret_cast<float4*>(acc)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   int np = 0;   // uniform
 
   // a / W by multiply-high (exact for a * W < 2^32: a is a cell index of one map; the host sends larger maps to the
   // scatter form): the drain runs it once per (row, channel)
-  const unsigned magicW = (unsigned)((0x100000000ull + (unsigned)W - 1) / (unsigned)W);
-  const unsigned magic_bins = (unsigned)((0x100000000ull + (unsigned)nbins - 1) / (unsigned)nbins);   // k < 256 * nbins
-  const unsigned magic_pw = (unsigned)((0x100000000ull + (unsigned)PW - 1) / (unsigned)PW);
-  constexpr int kDepth = 16;
-  float* __restrict__ mine_acc = acc + t;
+  // (ceil(2^32 / n) as floor((2^32 - 1) / n) + 1: a 32-bit division; the busy form comes here once per job)
+  const unsigned magicW = 0xFFFFFFFFu / (unsigned)W + 1u;
+  const unsigned magic_bins = 0xFFFFFFFFu / (unsigned)nbins + 1u;   // k < 256 * nbins
+  const unsigned magic_pw = 0xFFFFFFFFu / (unsigned)PW + 1u;
+  float* __restrict__ mine_acc = acc + copy * kCells * 256 + ch;
   const unsigned rows_in = (unsigned)(y1 - y0 + 1), cols_in = (unsigned)(x1 - x0 + 1);
   auto fetch = [&](int j, int (&a)[kDepth], float (&g)[kDepth]) {   // rows j .. j + kDepth - 1 of the list
 #pragma unroll
@@ -912,21 +855,24 @@ __global__ __launch_bounds__(256) void moi_pool_bwd_tiled(
     for (int u = 0; u < kDepth; ++u) {
       const unsigned ay = __umulhi((unsigned)a[u], magicW), ax = (unsigned)a[u] - ay * (unsigned)W;
       const unsigned ry = ay - (unsigned)y0, rx = ax - (unsigned)x0;
-      if ((a[u] >= 0) & (ry < rows_in) & (rx < cols_in)) mine_acc[(int)(ry * kTile + rx) * 256] += g[u];
+      if ((a[u] >= 0) & (ry < rows_in) & (rx < cols_in)) mine_acc[(int)(ry * SIDE + rx) * 256] += g[u];
     }
   };
-  // add the listed rows' gradients into the tile, in list order; two batches of kDepth rows alternate, the loads of one
-  // in flight while the other is applied
+  // add the listed rows' gradients into the tile: copy k takes the batches k, k + COPIES, ... of kDepth rows, in list
+  // order; two batches alternate, one's loads in flight while the other is applied.  (The list is rewritten only
+  // behind a barrier: compact_wg's first.)
   auto drain = [&]() {
     __syncthreads();
     int a0[kDepth], a1[kDepth];
     float g0[kDepth], g1[kDepth];
-    if (np > 0) fetch(0, a0, g0);
-    for (int j = 0; j < np; j += 2 * kDepth) {
-      if (j + kDepth < np) fetch(j + kDepth, a1, g1);
+    constexpr int kStep = COPIES * kDepth;
+    const int j0 = copy * kDepth;
+    if (j0 < np) fetch(j0, a0, g0);
+    for (int j = j0; j < np; j += 2 * kStep) {
+      if (j + kStep < np) fetch(j + kStep, a1, g1);
       apply(a0, g0);
-      if (j + kDepth < np) {
-        if (j + 2 * kDepth < np) fetch(j + 2 * kDepth, a0, g0);
+      if (j + kStep < np) {
+        if (j + 2 * kStep < np) fetch(j + 2 * kStep, a0, g0);
         apply(a1, g1);
       }
     }
@@ -937,7 +883,7 @@ __global__ __launch_bounds__(256) void moi_pool_bwd_tiled(
   const int nmine = counts[l * B + b];
   for (int base = 0; base < nmine; base += 256) {
     // ---- rois of this level / image whose box touches the tile, in index order
-    const int n = base + t < nmine ? mine[base + t] : -1;
+    const int n = ((COPIES == 1 || t < 256) && base + t < nmine) ? mine[base + t] : -1;
     bool hit = false;
     IBox r = {};
     if (n >= 0) {
@@ -945,7 +891,7 @@ __global__ __launch_bounds__(256) void moi_pool_bwd_tiled(
       hit = r.x0 <= x1 && r.x1 >= x0 && r.y0 <= y1 && r.y1 >= y0;
     }
     int nroi;
-    const int slot = compact_wg<4>(hit, wave_count, nroi);
+    const int slot = compact_wg<4 * COPIES>(hit, wave_count, nroi);
     if (hit) {
       roi_list[slot] = n;
       roi_box[slot] = r;
@@ -953,8 +899,8 @@ __global__ __launch_bounds__(256) void moi_pool_bwd_tiled(
     __syncthreads();
     // ---- their bins whose cell range touches the tile, in (roi, bin) order
     const int ncombo = nroi * nbins;
-    for (int k0 = 0; k0 < ncombo; k0 += 256) {
-      if (np > kPairCap - 256) drain();
+    for (int k0 = 0; k0 < ncombo; k0 += kThreads) {
+      if (np > kPairCap - kThreads) drain();
       const int k = k0 + t;
       bool bh = false;
       int row = 0;
@@ -967,7 +913,7 @@ __global__ __launch_bounds__(256) void moi_pool_bwd_tiled(
         row = m * nbins + bin;
       }
       int cnt;
-      const int ps = compact_wg<4>(bh, wave_count, cnt);
+      const int ps = compact_wg<4 * COPIES>(bh, wave_count, cnt);
       if (bh) pair_list[np + ps] = row;
       np += cnt;
     }
@@ -975,152 +921,64 @@ __global__ __launch_bounds__(256) void moi_pool_bwd_tiled(
   }
   drain();
   __syncthreads();
+  // every cell of the tile written once, whole 1 KiB rows; the copies joined in a fixed order
   for (int y = y0; y <= y1; ++y)
-    for (int x = x0; x <= x1; ++x)
-      {
-        float* dst = out + ((size_t)y * W + x) * C + c;
-        const float v = acc[((y - y0) * kTile + (x - x0)) * 256 + t];
-        *dst = accumulate ? *dst + v : v;
-      }
+    for (int x = x0 + copy; x <= x1; x += COPIES) {     // (the copies' threads share a row's cells between them)
+      const float* a = acc + ((y - y0) * SIDE + (x - x0)) * 256 + ch;
+      float* dst = out + ((size_t)y * W + x) * C + c;
+      const float v = COPIES == 1 ? a[0] : (a[0] + a[kCells * 256]) + (a[2 * kCells * 256] + a[3 * kCells * 256]);
+      *dst = accumulate ? *dst + v : v;
+    }
 }
 
-constexpr int kCopies = 4;
-constexpr int kPairCapBusy = 2048;
+// The light tiles: one workgroup per (tile, 256-channel block).  Tiles no box overlaps (census 0: most of a call) write
+// their zeros at once, 16 bytes per lane; tiles at or above `heavy_min` (estimated) rows are left to moi_pool_bwd_busy.
+__global__ __launch_bounds__(256) void moi_pool_bwd_tiled(
+    const MoiLevels lv, const MoiTiles tl, const float* __restrict__ grad, const float* __restrict__ rois,
+    const int* __restrict__ argmax, int C, int M, int PH, int PW, int B, const int* __restrict__ lists,
+    const int* __restrict__ counts, int nlevels, const int* __restrict__ plan, const int* __restrict__ census,
+    int heavy_min, int accumulate, const int* __restrict__ tile_order) {
+  extern __shared__ __attribute__((aligned(16))) float acc[];   // [64 cells][256 channels]
+  // workgroups start in index order: through the plan's permutation the heaviest tiles start first (tile_plan_kernel)
+  const int tile = tile_order ? tile_order[blockIdx.x] : (int)blockIdx.x;
+  const TileAt at = locate_tile(tl, nlevels, tile);
+  const int x0 = at.tx * kTile, y0 = at.ty * kTile;
+  const int load = census[tile];
+  const bool fallback = plan[0] > kCensusLimit;   // too many rois on one tile somewhere: the scatter form adds into zeros
+  if (load == 0 || fallback) {
+    if (accumulate) return;   // the map holds another consumer's gradient: nothing to add here (the scatter form adds to it)
+    const int H = lv.H[at.l], W = lv.W[at.l], x1 = min(x0 + kTile, W) - 1, y1 = min(y0 + kTile, H) - 1;
+    float* __restrict__ out = lv.gin[at.l] + (size_t)at.b * H * W * C;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = threadIdx.x; i < kTile * kTile * 64; i += 256) {
+      const int cell = i >> 6, y = y0 + cell / kTile, x = x0 + cell % kTile;
+      if (y <= y1 && x <= x1)
+        *reinterpret_cast<float4*>(out + ((size_t)y * W + x) * C + blockIdx.y * 256 + (i & 63) * 4) = z;
+    }
+    return;
+  }
+  if (load >= heavy_min) return;   // moi_pool_bwd_busy writes this tile
+  moi_gather_tile<kTile, 1>(lv, at.l, at.b, x0, y0, blockIdx.y * 256, grad, rois, argmax, C, M, PH, PW, B, lists, counts,
+                            accumulate, acc);
+}
 
+// The busy tiles: a fixed grid strides the plan's list of (tile, quadrant) entries, heaviest first.
+constexpr int kCopies = 4;
 __global__ __launch_bounds__(1024) void moi_pool_bwd_busy(
     const MoiLevels lv, const MoiTiles tl, const float* __restrict__ grad, const float* __restrict__ rois,
     const int* __restrict__ argmax, int C, int M, int PH, int PW, int B, const int* __restrict__ lists,
     const int* __restrict__ counts, int nlevels, const int* __restrict__ plan, int accumulate) {
-#pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) float acc[];   // [kCopies][kQuad * kQuad cells][256 channels]
-  __shared__ int roi_list[256];
-  __shared__ IBox roi_box[256];            // their rounded boxes (rounded once per roi, not once per (roi, bin))
-  __shared__ int pair_list[kPairCapBusy];  // (roi * nbins + bin) rows whose bin range touches the tile, in order
-  __shared__ int wave_count[16];
   if (plan[0] > kCensusLimit) return;      // piled-up rois beyond what one workgroup should walk: the scatter form
   const int nbusy = plan[1];
-  const int t = threadIdx.x, ch = t & 255, copy = t >> 8;
-  constexpr int kCells = kQuad * kQuad;
-  const int nbins = PH * PW;
-  const unsigned magic_bins = (unsigned)((0x100000000ull + (unsigned)nbins - 1) / (unsigned)nbins);   // k < 256 * nbins
-  const unsigned magic_pw = (unsigned)((0x100000000ull + (unsigned)PW - 1) / (unsigned)PW);
-  float* __restrict__ mine_acc = acc + copy * kCells * 256 + ch;
-  constexpr int kDepth = 16;
-
   for (int job = blockIdx.x; job < nbusy; job += gridDim.x) {
-    const int entry = plan[2 + job], tile = entry >> 2, quad = entry & 3;   // (tile of the census grid, its quadrant)
-    int l = 0;
-    while (l + 1 < nlevels && tile >= tl.first[l + 1]) ++l;
-    const int H = lv.H[l], W = lv.W[l];
-    int rel = tile - tl.first[l];
-    const int tx = rel % tl.tiles_x[l]; rel /= tl.tiles_x[l];
-    const int ty = rel % tl.tiles_y[l];
-    const int b = rel / tl.tiles_y[l];
-    const int x0 = tx * kTile + (quad & 1) * kQuad, y0 = ty * kTileY + (quad >> 1) * kQuad;
-    if (x0 >= W || y0 >= H) continue;        // (a quadrant beyond the map's edge; uniform)
-    const int x1 = min(x0 + kQuad, W) - 1, y1 = min(y0 + kQuad, H) - 1;
-    const float scale = lv.scale[l];
-    float* __restrict__ out = lv.gin[l] + (size_t)b * H * W * C;
-    // a / W by multiply-high (exact for a * W < 2^32: a is a cell index of one map; the host sends larger maps to the
-    // scatter form): the drain runs it once per (row, channel)
-    const unsigned magicW = (unsigned)((0x100000000ull + (unsigned)W - 1) / (unsigned)W);
-    const unsigned rows_in = (unsigned)(y1 - y0 + 1), cols_in = (unsigned)(x1 - x0 + 1);
-
-    for (int cb = 0; cb < C; cb += 256) {   // (256-channel blocks: one on the JTSM path)
-      const int c = cb + ch;
-      __syncthreads();                       // the previous job's / block's readers of acc and the lists are done
-      for (int i = t; i < kCopies * kCells * 64; i += 1024) reinterpret_cast<float4*>(acc)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      int np = 0;   // uniform
-
-      auto fetch = [&](int j, int (&a)[kDepth], float (&g)[kDepth]) {   // rows j .. j + kDepth - 1 of the list
-#pragma unroll
-        for (int u = 0; u < kDepth; ++u) {
-          const size_t row = (size_t)pair_list[min(j + u, np - 1)];
-          a[u] = j + u < np ? argmax[row * C + c] : -1;
-          g[u] = j + u < np ? grad[row * C + c] : 0.f;
-        }
-      };
-      auto apply = [&](const int (&a)[kDepth], const float (&g)[kDepth]) {
-#pragma unroll
-        for (int u = 0; u < kDepth; ++u) {
-          const unsigned ay = __umulhi((unsigned)a[u], magicW), ax = (unsigned)a[u] - ay * (unsigned)W;
-          const unsigned ry = ay - (unsigned)y0, rx = ax - (unsigned)x0;
-          if ((a[u] >= 0) & (ry < rows_in) & (rx < cols_in)) mine_acc[(int)(ry * kQuad + rx) * 256] += g[u];
-        }
-      };
-      // copy k takes the batches k, k + 4, ... of kDepth rows; two batches alternate, one's loads in flight while the
-      // other is applied
-      auto drain = [&]() {
-        __syncthreads();
-        int a0[kDepth], a1[kDepth];
-        float g0[kDepth], g1[kDepth];
-        constexpr int kStep = kCopies * kDepth;
-        const int j0 = copy * kDepth;
-        if (j0 < np) fetch(j0, a0, g0);
-        for (int j = j0; j < np; j += 2 * kStep) {
-          if (j + kStep < np) fetch(j + kStep, a1, g1);
-          apply(a0, g0);
-          if (j + kStep < np) {
-            if (j + 2 * kStep < np) fetch(j + 2 * kStep, a0, g0);
-            apply(a1, g1);
-          }
-        }
-        np = 0;
-        __syncthreads();                     // pair_list is rewritten next
-      };
-
-      const int* __restrict__ mine = lists + (size_t)(l * B + b) * M;
-      const int nmine = counts[l * B + b];
-      for (int base = 0; base < nmine; base += 256) {
-        // ---- rois of this level / image whose box touches the tile, in index order
-        const int n = (t < 256 && base + t < nmine) ? mine[base + t] : -1;
-        bool hit = false;
-        IBox r = {};
-        if (n >= 0) {
-          r = round_box(rois + (size_t)n * 5, scale);
-          hit = r.x0 <= x1 && r.x1 >= x0 && r.y0 <= y1 && r.y1 >= y0;
-        }
-        int nroi;
-        const int slot = compact_wg<16>(hit, wave_count, nroi);
-        if (hit) {
-          roi_list[slot] = n;
-          roi_box[slot] = r;
-        }
-        __syncthreads();
-        // ---- their bins whose cell range touches the tile, in (roi, bin) order
-        const int ncombo = nroi * nbins;
-        for (int k0 = 0; k0 < ncombo; k0 += 1024) {
-          if (np > kPairCapBusy - 1024) drain();
-          const int k = k0 + t;
-          bool bh = false;
-          int row = 0;
-          if (k < ncombo) {
-            const int i = (int)__umulhi((unsigned)k, magic_bins), bin = k - i * nbins, m = roi_list[i];
-            const IBox rb = roi_box[i];
-            const int ph = (int)__umulhi((unsigned)bin, magic_pw);
-            const BinRange q = bin_range(rb, ph, bin - ph * PW, PH, PW, H, W);
-            bh = q.he > q.hs && q.we > q.ws && q.hs <= y1 && q.he > y0 && q.ws <= x1 && q.we > x0;
-            row = m * nbins + bin;
-          }
-          int cnt;
-          const int ps = compact_wg<16>(bh, wave_count, cnt);
-          if (bh) pair_list[np + ps] = row;
-          np += cnt;
-        }
-        __syncthreads();   // roi_list is rewritten by the next chunk
-      }
-      drain();
-      // the four copies, added in a fixed order; whole 1 KiB rows
-      for (int i = t; i < kCells * 256; i += 1024) {
-        const int cell = i >> 8, cc = i & 255;
-        const int y = y0 + cell / kQuad, x = x0 + cell % kQuad;
-        if (y > y1 || x > x1) continue;
-        const float* a = acc + cell * 256 + cc;
-        float* dst = out + ((size_t)y * W + x) * C + cb + cc;
-        const float v = (a[0] + a[kCells * 256]) + (a[2 * kCells * 256] + a[3 * kCells * 256]);
-        *dst = accumulate ? *dst + v : v;
-      }
-    }
+    const int entry = plan[2 + job], quad = entry & 3;   // (tile of the census grid, its quadrant)
+    const TileAt at = locate_tile(tl, nlevels, entry >> 2);
+    const int x0 = at.tx * kTile + (quad & 1) * kQuad, y0 = at.ty * kTile + (quad >> 1) * kQuad;
+    if (x0 >= lv.W[at.l] || y0 >= lv.H[at.l]) continue;        // (a quadrant beyond the map's edge; uniform)
+    for (int cb = 0; cb < C; cb += 256)   // (256-channel blocks: one on the JTSM path)
+      moi_gather_tile<kQuad, kCopies>(lv, at.l, at.b, x0, y0, cb, grad, rois, argmax, C, M, PH, PW, B, lists, counts,
+                                      accumulate, acc);
   }
 }
 
@@ -1143,12 +1001,8 @@ __global__ __launch_bounds__(256) void moi_pool_fwd_nchw(
     int at = -1;
     for (int h = q.hs; h < q.he; ++h)
       for (int w = q.ws; w < q.we; ++w) {
-        if (!(w >= r.x0 && w <= r.x1 && h >= r.y0 && h <= r.y1)) continue;
         const int cell = h * W + w;
-        const unsigned* crow = cplane + (size_t)cell * words;
-        unsigned hit = 0u;
-        for (int i = 0; i < words && !hit; ++i) hit = crow[i] & rrow[i];
-        if (!hit) continue;
+        if (!moi_cell_set(r, h, w, cplane + (size_t)cell * words, rrow, words)) continue;
         const float x = plane[cell];
         if (x > best) { best = x; at = cell; }
       }
@@ -1166,71 +1020,116 @@ __global__ __launch_bounds__(256) void moi_mask_kernel(const float* __restrict__
   if (idx >= total) return;
   const int w = (int)(idx % W), h = (int)((idx / W) % H), n = (int)(idx / W / H);
   const IBox r = round_box(rois + (size_t)n * 5, scale);
-  int v = 0;
-  if (w >= r.x0 && w <= r.x1 && h >= r.y0 && h <= r.y1) {
-    const unsigned* crow = cell_bits + ((size_t)r.b * H * W + (size_t)h * W + w) * words;
-    const unsigned* rrow = roi_bits + (size_t)n * words;
-    unsigned hit = 0u;
-    for (int i = 0; i < words && !hit; ++i) hit = crow[i] & rrow[i];
-    v = hit != 0u;
-  }
-  mois[idx] = v;
+  mois[idx] = moi_cell_set(r, h, w, cell_bits + ((size_t)r.b * H * W + (size_t)h * W + w) * words,
+                           roi_bits + (size_t)n * words, words);
 }
 
-// Backward: grad_input[b, argmax] += grad (RoIPoolBackward, MOIPool_cuda.cu:296-338).
-template <bool NHWC>
+// Backward, NCHW: grad_input[b, argmax] += grad (RoIPoolBackward, MOIPool_cuda.cu:296-338), a thread per element.
 __global__ __launch_bounds__(256) void moi_pool_bwd(const float* __restrict__ grad,
                                                     const float* __restrict__ rois,
                                                     const int* __restrict__ argmax,
                                                     float* __restrict__ gin, int C, int H, int W,
-                                                    long total, int PH, int PW,
-                                                    const int* __restrict__ roi_level, int level) {
+                                                    long total, int PH, int PW) {
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (long)gridDim.x * blockDim.x) {
-    int c, n;
-    if (NHWC) {
-      c = (int)(idx % C);
-      n = (int)(idx / C / PW / PH);
-    } else {
-      c = (int)((idx / PW / PH) % C);
-      n = (int)(idx / PW / PH / C);
-    }
-    if (roi_level && roi_level[n] != level) continue;  // before touching argmax/grad: each level reads only its rois
     const int a = argmax[idx];
     if (a == -1) continue;
+    const int c = (int)((idx / PW / PH) % C), n = (int)(idx / PW / PH / C);
     const int b = (int)rois[(size_t)n * 5];
-    float* dst = NHWC ? gin + ((size_t)b * H * W + a) * C + c : gin + ((size_t)b * C + c) * H * W + a;
-    atomicAdd(dst, grad[idx]);
+    atomicAdd(gin + ((size_t)b * C + c) * H * W + a, grad[idx]);
   }
 }
 
 inline int bit_words(int L) { return (L + 31) / 32; }
 
-struct Workspace { unsigned* cell; unsigned* roi; };
-
-inline Workspace carve(void* ws, int B, int H, int W, int L) {
-  Workspace k;
-  k.cell = reinterpret_cast<unsigned*>(ws);
-  size_t cell_bytes = (size_t)B * H * W * bit_words(L) * sizeof(unsigned);
-  cell_bytes = (cell_bytes + 15) & ~(size_t)15;
-  k.roi = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + cell_bytes);
+// The forward's workspace (a single-level call is a table of one level): the rois' label words, every level's cell
+// words, the rois' spatial order.
+struct FwdWs { unsigned* roi_bits; unsigned* cell[kMaxLevels]; int* order; };
+FwdWs carve(Arena& a, int B, const int* H, const int* W, int nlevels, int M, int L) {
+  FwdWs k = {};
+  k.roi_bits = a.take<unsigned>((size_t)M * bit_words(L));
+  for (int l = 0; l < nlevels; ++l) k.cell[l] = a.take<unsigned>((size_t)B * H[l] * W[l] * bit_words(L));
+  k.order = a.take<int>(M);   // (unused by a call without a level table: the price of one layout for both)
   return k;
 }
+size_t forward_workspace_bytes(int B, const int* H, const int* W, int nlevels, int M, int L) {
+  Arena a{nullptr};
+  carve(a, B, H, W, nlevels, M, L);
+  return a.off;
+}
 
-int build_bits(const int* oh_labels, const int* superpixels, const Workspace& k, int B, int H,
-               int W, int M, int L, int Hs, int Ws, hipStream_t st) {
+// Both bit tables of a call and, with `sort`, the rois' spatial order (one more block), in one launch.  Returns the
+// order, or nullptr when there is none.
+const int* launch_bits(const MoiLevels& lv, int nlevels, const FwdWs& k, const float* rois, const int* roi_level,
+                       const int* oh_labels, const int* superpixels, int B, int M, int L, int Hs, int Ws, bool sort,
+                       hipStream_t st) {
   const int words = bit_words(L);
-  const long cells = (long)B * H * W;
-  const bool small = moi_bits_small_ok(H, W, Hs, Ws);
-  const int cpw = small ? 0 : moi_cells_per_wave(H, W, Hs, Ws);
-  hipLaunchKernelGGL(moi_cell_bits_kernel, dim3(small ? ceil_div(cells, 256) : ceil_div(cells, 4 * cpw)), dim3(256),
-                     4 * cpw * words * sizeof(unsigned), st, superpixels, k.cell, B, H, W, Hs, Ws, L,
-                     words, cpw);
-  JTSM_CHECK_LAUNCH("moi_cell_bits");
-  hipLaunchKernelGGL(moi_roi_bits_kernel, dim3(ceil_div((long)M, kRoiBitsRows)), dim3(256), 0, st, oh_labels,
-                     k.roi, (long)M, L, words);
-  JTSM_CHECK_LAUNCH("moi_roi_bits");
+  MoiBitsPlan bp = {};
+  int nblk = 0, max_cpw = 1;
+  for (int l = 0; l < nlevels; ++l) {
+    const long cells = (long)B * lv.H[l] * lv.W[l];
+    const bool small = moi_bits_small_ok(lv.H[l], lv.W[l], Hs, Ws);
+    const int cpw = small ? 0 : moi_cells_per_wave(lv.H[l], lv.W[l], Hs, Ws);
+    bp.cell[l] = k.cell[l]; bp.H[l] = lv.H[l]; bp.W[l] = lv.W[l]; bp.cpw[l] = cpw; bp.first[l] = nblk;
+    nblk += (int)(small ? ceil_div(cells, 256) : ceil_div(cells, 4 * cpw));
+    max_cpw = std::max(max_cpw, cpw);
+  }
+  bp.n = nlevels;
+  bp.first[nlevels] = nblk;
+  nblk += (int)ceil_div((long)M, kRoiBitsRows);
+  // the ordering's grid: the coarsest whose buckets fit the sort block's table
+  int* order = nullptr;
+  bp.sort_block = -1;
+  if (sort) {
+    int G = 16;
+    while (G > 1 && (long)nlevels * B * G * G > kSortBuckets) G >>= 1;
+    if ((long)nlevels * B * G * G <= kSortBuckets) {
+      order = k.order;
+      bp.sort_block = nblk++;
+      bp.grid = G;
+      bp.scale0 = lv.scale[0];
+    }
+  }
+  hipLaunchKernelGGL(moi_bits_all_kernel, dim3(nblk), dim3(256), 4 * max_cpw * words * sizeof(unsigned), st, bp, superpixels,
+                     oh_labels, k.roi_bits, B, Hs, Ws, L, words, (long)M, rois, roi_level, M, order, moi_bits_skip());
+  return order;
+}
+
+// The NHWC forward of both entry points: the bit tables, then the per-(roi, bin row) form where it applies (7 bins
+// across, a label width it is instantiated for, 16-byte rows), else a wavefront per (roi, bin).
+int forward_levels(MoiLevels lv, int nlevels, const float* rois, const int* roi_level, const int* oh_labels,
+                   const int* superpixels, float* output, int* argmax, void* workspace, int B, int C, int M, int L, int Hs,
+                   int Ws, int PH, int PW, hipStream_t st) {
+  const int words = bit_words(L);
+  Arena arena{static_cast<char*>(workspace)};
+  const FwdWs k = carve(arena, B, lv.H, lv.W, nlevels, M, L);
+  bool vec4 = C % 4 == 0, narrow = true;     // 16 bytes per lane; (h, w) of a cell in 16 bits each
+  for (int l = 0; l < nlevels; ++l) {
+    lv.cell[l] = k.cell[l];
+    vec4 = vec4 && ((uintptr_t)lv.in[l] & 15) == 0;
+    narrow = narrow && lv.H[l] < 65536 && lv.W[l] < 65536;
+  }
+  const bool rows_ok = moi_fwd_rows_mode() != 0 && PW == 7 && moi_fwd_rows_words_ok(words) && vec4 && narrow &&
+                       ((uintptr_t)output & 15) == 0 && ((uintptr_t)argmax & 15) == 0;
+  // (the spatial order keys on the rois' levels: calls with a level table only)
+  const int* order = launch_bits(lv, nlevels, k, rois, roi_level, oh_labels, superpixels, B, M, L, Hs, Ws,
+                                 rows_ok && roi_level && moi_sort_on(), st);
+  if (rows_ok) {
+    launch_fwd_rows(lv, rois, k.roi_bits, output, argmax, C, M, words, PH, roi_level, nlevels, order, st);
+  } else {
+    const auto kernel = vec4 ? moi_pool_fwd_levels<4> : moi_pool_fwd_levels<1>;
+    hipLaunchKernelGGL(kernel, dim3(ceil_div((long)M * PH * PW, 4)), dim3(256), 0, st, lv, rois, k.roi_bits, output, argmax,
+                       C, M, words, PH, PW, roi_level, nlevels);
+  }
+  JTSM_CHECK_LAUNCH("moi_pool forward");
   return JTSM_OK;
+}
+
+// The float-atomic scatter of the backward; with `census_max` it leaves at once unless the census sent the gather home.
+void launch_bwd_scatter(const MoiLevels& lv, int nlevels, const float* grad, const float* rois, const int* argmax, int C,
+                        int M, int nbins, const int* roi_level, const int* census_max, hipStream_t st) {
+  hipLaunchKernelGGL(moi_pool_bwd_levels, dim3(std::min(ceil_div((long)M * nbins, 4), 8192)), dim3(256), 0, st, lv, grad,
+                     rois, argmax, C, M, nbins, roi_level, nlevels, census_max, kCensusLimit);
 }
 
 }  // namespace
@@ -1242,16 +1141,14 @@ extern "C" {
 
 size_t jtsm_moi_pool_workspace_bytes(int B, int H, int W, int M, int L) {
   if (B < 0 || H < 0 || W < 0 || M < 0 || L < 0) return 0;
-  size_t cell = (size_t)B * H * W * bit_words(L) * sizeof(unsigned);
-  cell = (cell + 15) & ~(size_t)15;
-  return cell + (size_t)M * bit_words(L) * sizeof(unsigned) + 16;
+  return forward_workspace_bytes(B, &H, &W, 1, M, L);
 }
 
-static int moi_forward_impl(const float* input, const float* rois, const int32_t* oh_labels,
-                            const int32_t* superpixels, float* output, int32_t* argmax,
-                            void* workspace, int B, int C, int H, int W, int M, int L, int Hs,
-                            int Ws, float spatial_scale, int pooled_h, int pooled_w, int layout,
-                            void* stream, const int32_t* roi_level, int level) {
+int jtsm_moi_pool_forward_f32(const float* input, const float* rois, const int32_t* oh_labels,
+                              const int32_t* superpixels, float* output, int32_t* argmax,
+                              void* workspace, int B, int C, int H, int W, int M, int L, int Hs,
+                              int Ws, float spatial_scale, int pooled_h, int pooled_w, int layout,
+                              void* stream) {
   JTSM_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && M >= 0 && L >= 0 && pooled_h > 0 && pooled_w > 0,
                "moi_pool: negative size");
   JTSM_REQUIRE(layout == JTSM_NCHW || layout == JTSM_NHWC, "moi_pool: unknown layout %d", layout);
@@ -1262,39 +1159,24 @@ static int moi_forward_impl(const float* input, const float* rois, const int32_t
                "moi_pool: empty feature map / superpixel map / label table");
   JTSM_REQUIRE(((uintptr_t)workspace & 15) == 0, "moi_pool: workspace must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
-  const Workspace k = carve(workspace, B, H, W, L);
-  int rc = build_bits(oh_labels, superpixels, k, B, H, W, M, L, Hs, Ws, st);
-  if (rc) return rc;
-  const int words = bit_words(L);
-  if (layout == JTSM_NHWC) {
-    const int blocks = ceil_div((long)M * pooled_h * pooled_w, 4);
-    if (moi_fwd_rows_mode() != 0 && pooled_w == 7 && moi_fwd_rows_words_ok(words) && C % 4 == 0 && ((uintptr_t)input & 15) == 0 &&
-        ((uintptr_t)output & 15) == 0 && ((uintptr_t)argmax & 15) == 0 && H < 65536 && W < 65536) {
-      MoiLevels lv = {};
-      lv.in[0] = input; lv.cell[0] = k.cell; lv.H[0] = H; lv.W[0] = W; lv.scale[0] = spatial_scale;
-      launch_fwd_rows(lv, rois, k.roi, output, argmax, C, M, words, pooled_h, roi_level, 1, roi_level ? level : -1, nullptr, st);
-    } else if (C % 4 == 0 && ((uintptr_t)input & 15) == 0)
-      hipLaunchKernelGGL(moi_pool_fwd_nhwc<4>, dim3(blocks), dim3(256), 0, st, input, rois, k.cell,
-                         k.roi, output, argmax, C, H, W, M, words, spatial_scale, pooled_h,
-                         pooled_w, roi_level, level);
-    else
-      hipLaunchKernelGGL(moi_pool_fwd_nhwc<1>, dim3(blocks), dim3(256), 0, st, input, rois, k.cell,
-                         k.roi, output, argmax, C, H, W, M, words, spatial_scale, pooled_h,
-                         pooled_w, roi_level, level);
-  } else {
-    JTSM_REQUIRE(!roi_level, "moi_pool: per-level filtering needs the NHWC layout");
-    const long total = (long)M * C * pooled_h * pooled_w;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(moi_pool_fwd_nchw, dim3(blocks), dim3(256), 0, st, input, rois, k.cell, k.roi,
-                       output, argmax, C, H, W, total, words, spatial_scale, pooled_h, pooled_w);
-  }
+  MoiLevels lv = {};
+  lv.in[0] = input; lv.H[0] = H; lv.W[0] = W; lv.scale[0] = spatial_scale;
+  if (layout == JTSM_NHWC)
+    return forward_levels(lv, 1, rois, nullptr, oh_labels, superpixels, output, argmax, workspace, B, C, M, L, Hs, Ws,
+                          pooled_h, pooled_w, st);
+  Arena arena{static_cast<char*>(workspace)};
+  const FwdWs k = carve(arena, B, &H, &W, 1, M, L);
+  launch_bits(lv, 1, k, rois, nullptr, oh_labels, superpixels, B, M, L, Hs, Ws, false, st);
+  const long total = (long)M * C * pooled_h * pooled_w;
+  hipLaunchKernelGGL(moi_pool_fwd_nchw, dim3(std::min(ceil_div(total, 256), 8192)), dim3(256), 0, st, input, rois, k.cell[0],
+                     k.roi_bits, output, argmax, C, H, W, total, bit_words(L), spatial_scale, pooled_h, pooled_w);
   JTSM_CHECK_LAUNCH("moi_pool forward");
   return JTSM_OK;
 }
 
-static int moi_backward_impl(const float* grad, const float* rois, const int32_t* argmax,
-                             float* grad_input, int B, int C, int H, int W, int M, int pooled_h,
-                             int pooled_w, int layout, void* stream, const int32_t* roi_level, int level) {
+int jtsm_moi_pool_backward_f32(const float* grad, const float* rois, const int32_t* argmax,
+                               float* grad_input, int B, int C, int H, int W, int M, int pooled_h,
+                               int pooled_w, int layout, void* stream) {
   JTSM_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && M >= 0 && pooled_h > 0 && pooled_w > 0,
                "moi_pool backward: negative size");
   JTSM_REQUIRE(layout == JTSM_NCHW || layout == JTSM_NHWC, "moi_pool: unknown layout %d", layout);
@@ -1306,46 +1188,16 @@ static int moi_backward_impl(const float* grad, const float* rois, const int32_t
   const long total = (long)M * C * pooled_h * pooled_w;
   if (total == 0) return JTSM_OK;
   JTSM_REQUIRE(grad && rois && argmax, "moi_pool backward: null pointer");
-  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  if (layout == JTSM_NHWC)
-    hipLaunchKernelGGL(moi_pool_bwd<true>, dim3(blocks), dim3(256), 0, st, grad, rois, argmax,
-                       grad_input, C, H, W, total, pooled_h, pooled_w, roi_level, level);
-  else
-    hipLaunchKernelGGL(moi_pool_bwd<false>, dim3(blocks), dim3(256), 0, st, grad, rois, argmax,
-                       grad_input, C, H, W, total, pooled_h, pooled_w, roi_level, level);
+  if (layout == JTSM_NHWC) {
+    MoiLevels lv = {};
+    lv.gin[0] = grad_input; lv.H[0] = H; lv.W[0] = W;
+    launch_bwd_scatter(lv, 1, grad, rois, argmax, C, M, pooled_h * pooled_w, nullptr, nullptr, st);
+  } else {
+    hipLaunchKernelGGL(moi_pool_bwd, dim3(std::min(ceil_div(total, 256), 8192)), dim3(256), 0, st, grad, rois, argmax,
+                       grad_input, C, H, W, total, pooled_h, pooled_w);
+  }
   JTSM_CHECK_LAUNCH("moi_pool backward");
   return JTSM_OK;
-}
-
-int jtsm_moi_pool_forward_f32(const float* input, const float* rois, const int32_t* oh_labels,
-                              const int32_t* superpixels, float* output, int32_t* argmax,
-                              void* workspace, int B, int C, int H, int W, int M, int L, int Hs,
-                              int Ws, float spatial_scale, int pooled_h, int pooled_w, int layout,
-                              void* stream) {
-  return moi_forward_impl(input, rois, oh_labels, superpixels, output, argmax, workspace, B, C, H, W, M, L,
-                          Hs, Ws, spatial_scale, pooled_h, pooled_w, layout, stream, nullptr, 0);
-}
-int jtsm_moi_pool_backward_f32(const float* grad, const float* rois, const int32_t* argmax,
-                               float* grad_input, int B, int C, int H, int W, int M, int pooled_h,
-                               int pooled_w, int layout, void* stream) {
-  return moi_backward_impl(grad, rois, argmax, grad_input, B, C, H, W, M, pooled_h, pooled_w, layout,
-                           stream, nullptr, 0);
-}
-int jtsm_moi_pool_forward_level_f32(const float* input, const float* rois, const int32_t* roi_level,
-                                    int level, const int32_t* oh_labels, const int32_t* superpixels,
-                                    float* output, int32_t* argmax, void* workspace, int B, int C, int H,
-                                    int W, int M, int L, int Hs, int Ws, float spatial_scale, int pooled_h,
-                                    int pooled_w, void* stream) {
-  JTSM_REQUIRE(roi_level || M == 0, "moi_pool level: null roi_level");
-  return moi_forward_impl(input, rois, oh_labels, superpixels, output, argmax, workspace, B, C, H, W, M, L,
-                          Hs, Ws, spatial_scale, pooled_h, pooled_w, JTSM_NHWC, stream, roi_level, level);
-}
-int jtsm_moi_pool_backward_level_f32(const float* grad, const float* rois, const int32_t* roi_level,
-                                     int level, const int32_t* argmax, float* grad_input, int B, int C,
-                                     int H, int W, int M, int pooled_h, int pooled_w, void* stream) {
-  JTSM_REQUIRE(roi_level || M == 0, "moi_pool level: null roi_level");
-  return moi_backward_impl(grad, rois, argmax, grad_input, B, C, H, W, M, pooled_h, pooled_w, JTSM_NHWC,
-                           stream, roi_level, level);
 }
 
 int jtsm_moi_mask_f32(const float* rois, const int32_t* oh_labels, const int32_t* superpixels,
@@ -1355,12 +1207,14 @@ int jtsm_moi_mask_f32(const float* rois, const int32_t* oh_labels, const int32_t
   if (M == 0) return JTSM_OK;
   JTSM_REQUIRE(rois && oh_labels && superpixels && mois && workspace, "moi_mask: null pointer");
   hipStream_t st = as_stream(stream);
-  const Workspace k = carve(workspace, B, H, W, L);
-  int rc = build_bits(oh_labels, superpixels, k, B, H, W, M, L, Hs, Ws, st);
-  if (rc) return rc;
+  MoiLevels lv = {};
+  lv.H[0] = H; lv.W[0] = W;
+  Arena arena{static_cast<char*>(workspace)};
+  const FwdWs k = carve(arena, B, &H, &W, 1, M, L);
+  launch_bits(lv, 1, k, rois, nullptr, oh_labels, superpixels, B, M, L, Hs, Ws, false, st);
   const long total = (long)M * H * W;
-  hipLaunchKernelGGL(moi_mask_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, rois, k.cell,
-                     k.roi, mois, H, W, total, bit_words(L), spatial_scale);
+  hipLaunchKernelGGL(moi_mask_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, rois, k.cell[0], k.roi_bits, mois, H, W,
+                     total, bit_words(L), spatial_scale);
   JTSM_CHECK_LAUNCH("moi_mask");
   return JTSM_OK;
 }
@@ -1370,11 +1224,7 @@ int jtsm_moi_mask_f32(const float* rois, const int32_t* oh_labels, const int32_t
  * [0,nlevels) picks the map of roi n.  workspace: jtsm_moi_pool_levels_workspace_bytes. */
 size_t jtsm_moi_pool_levels_workspace_bytes(int B, const int* H, const int* W, int nlevels, int M, int L) {
   if (B < 0 || M < 0 || L < 0 || nlevels < 0 || nlevels > kMaxLevels || !H || !W) return 0;
-  size_t total = 16 + (((size_t)M * bit_words(L) * sizeof(unsigned) + 15) & ~(size_t)15);
-  for (int l = 0; l < nlevels; ++l)
-    total += (((size_t)B * H[l] * W[l] * bit_words(L) * sizeof(unsigned)) + 15) & ~(size_t)15;
-  total += ((size_t)M * sizeof(int) + 15) & ~(size_t)15;      // the rois' spatial order
-  return total;
+  return forward_workspace_bytes(B, H, W, nlevels, M, L);
 }
 
 int jtsm_moi_pool_forward_levels_f32(const float* const* inputs, const int* H, const int* W, const float* scales,
@@ -1389,58 +1239,15 @@ int jtsm_moi_pool_forward_levels_f32(const float* const* inputs, const int* H, c
                "moi_pool levels: null pointer");
   JTSM_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && L > 0 && C % 4 == 0, "moi_pool levels: empty map / C %% 4 != 0");
   JTSM_REQUIRE(((uintptr_t)workspace & 15) == 0, "moi_pool levels: workspace must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  const int words = bit_words(L);
-  char* w = reinterpret_cast<char*>(workspace);
-  unsigned* roi_bits = reinterpret_cast<unsigned*>(w);
-  w += (((size_t)M * words * sizeof(unsigned)) + 15) & ~(size_t)15;
   MoiLevels lv = {};
-  MoiBitsPlan bp = {};
-  int nblk = 0, max_cpw = 1;
   for (int l = 0; l < nlevels; ++l) {
     JTSM_REQUIRE(inputs[l] && H[l] > 0 && W[l] > 0 && ((uintptr_t)inputs[l] & 15) == 0, "moi_pool levels: bad level %d", l);
     lv.in[l] = inputs[l]; lv.H[l] = H[l]; lv.W[l] = W[l]; lv.scale[l] = scales[l];
-    unsigned* cell = reinterpret_cast<unsigned*>(w);
-    lv.cell[l] = cell;
-    w += (((size_t)B * H[l] * W[l] * words * sizeof(unsigned)) + 15) & ~(size_t)15;
-    const long cells = (long)B * H[l] * W[l];
-    const bool small = moi_bits_small_ok(H[l], W[l], Hs, Ws);
-    const int cpw = small ? 0 : moi_cells_per_wave(H[l], W[l], Hs, Ws);
-    bp.cell[l] = cell; bp.H[l] = H[l]; bp.W[l] = W[l]; bp.cpw[l] = cpw; bp.first[l] = nblk;
-    nblk += (int)(small ? ceil_div(cells, 256) : ceil_div(cells, 4 * cpw));
-    max_cpw = std::max(max_cpw, cpw);
   }
-  bp.n = nlevels;
-  bp.first[nlevels] = nblk;
-  nblk += (int)ceil_div((long)M, kRoiBitsRows);
-  bool rows_ok = moi_fwd_rows_mode() != 0 && pooled_w == 7 && moi_fwd_rows_words_ok(words) && ((uintptr_t)output & 15) == 0 &&
-                 ((uintptr_t)argmax & 15) == 0;
-  for (int l = 0; l < nlevels; ++l) rows_ok = rows_ok && H[l] < 65536 && W[l] < 65536;
-  // the rois' spatial order (one more block of the same launch): the coarsest grid whose buckets fit the block's table
-  int* order = nullptr;
-  bp.sort_block = -1;
-  if (rows_ok && moi_sort_on()) {
-    int G = 16;
-    while (G > 1 && (long)nlevels * B * G * G > kSortBuckets) G >>= 1;
-    if ((long)nlevels * B * G * G <= kSortBuckets) {
-      order = reinterpret_cast<int*>(w);
-      bp.sort_block = nblk++;
-      bp.grid = G;
-      bp.scale0 = scales[0];
-    }
-  }
-  hipLaunchKernelGGL(moi_bits_all_kernel, dim3(nblk), dim3(256), 4 * max_cpw * words * sizeof(unsigned), st, bp, superpixels,
-                     oh_labels, roi_bits, B, Hs, Ws, L, words, (long)M, rois, roi_level, M, order, moi_bits_skip());
-  if (rows_ok) {
-    launch_fwd_rows(lv, rois, roi_bits, output, argmax, C, M, words, pooled_h, roi_level, nlevels, -1, order, st);
-  } else {
-    const int blocks = ceil_div((long)M * pooled_h * pooled_w, 4);
-    hipLaunchKernelGGL(moi_pool_fwd_levels<4>, dim3(blocks), dim3(256), 0, st, lv, rois, roi_bits, output, argmax, C, M,
-                       words, pooled_h, pooled_w, roi_level, nlevels);
-  }
-  JTSM_CHECK_LAUNCH("moi_pool forward levels");
-  return JTSM_OK;
+  return forward_levels(lv, nlevels, rois, roi_level, oh_labels, superpixels, output, argmax, workspace, B, C, M, L, Hs, Ws,
+                        pooled_h, pooled_w, as_stream(stream));
 }
+
 
 // The side stream and the fork / join events of the backward's two gathers, created once per device (JTSM_MOI_BWD_STREAMS=0:
 // one stream, the gathers one after the other).
@@ -1464,18 +1271,38 @@ static bool moi_bwd_events(hipEvent_t* fork, hipEvent_t* join) {
   return true;
 }
 
-static long census_tiles(const int* H, const int* W, int nlevels, int B) {
-  long n = 0;
-  for (int l = 0; l < nlevels; ++l) n += (long)B * ceil_div(W[l], kTile) * ceil_div(H[l], kTileY);
-  return n;
+// The census grid: kTile x kTile-cell tiles, level after level, image after image.  Returns their number.
+static int plan_tiles(const int* H, const int* W, int nlevels, int B, MoiTiles& tl) {
+  int tiles = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    tl.first[l] = tiles;
+    tl.tiles_x[l] = ceil_div(W[l], kTile);
+    tl.tiles_y[l] = ceil_div(H[l], kTile);
+    tiles += B * tl.tiles_x[l] * tl.tiles_y[l];
+  }
+  tl.first[nlevels] = tiles;
+  return tiles;
+}
+
+// The gather's workspace: per-(level, image) roi lists and their counts, the tile census, the launch plan ([0] census
+// maximum, [1] number of busy entries, then at most 4 quadrant entries per tile) and the light gather's tile order.
+struct GatherWs { int* lists; int* counts; int* census; int* plan; int* tile_order; };
+static GatherWs carve(Arena& a, int nlevels, int B, int M, int ntile) {
+  GatherWs k;
+  k.lists = a.take<int>((size_t)nlevels * B * M);
+  k.counts = a.take<int>((size_t)nlevels * B);
+  k.census = a.take<int>(ntile);
+  k.plan = a.take<int>(2 + 4 * (size_t)ntile);
+  k.tile_order = a.take<int>(ntile);
+  return k;
 }
 
 size_t jtsm_moi_pool_backward_levels_workspace_bytes(const int* H, const int* W, int nlevels, int B, int M) {
   if (nlevels <= 0 || nlevels > kMaxLevels || B <= 0 || M <= 0 || !H || !W) return 0;
-  // per-(level, image) roi lists + counts, then the tile census and the launch plan (maximum, count, busy tiles)
-  // (... and the light-tile gather's workgroup order: one more int per tile)
-  return (((size_t)nlevels * B * ((size_t)M + 1) + 6 * (size_t)census_tiles(H, W, nlevels, B) + 8) * sizeof(int) + 15) &
-         ~(size_t)15;
+  MoiTiles tl = {};
+  Arena a{nullptr};
+  carve(a, nlevels, B, M, plan_tiles(H, W, nlevels, B, tl));
+  return a.off;
 }
 
 int jtsm_moi_pool_backward_levels_f32(const float* grad, const float* rois, const int32_t* roi_level,
@@ -1486,6 +1313,7 @@ int jtsm_moi_pool_backward_levels_f32(const float* grad, const float* rois, cons
   JTSM_REQUIRE(B >= 0 && C >= 0 && M >= 0 && pooled_h > 0 && pooled_w > 0 && C % 4 == 0,
                "moi_pool levels backward: bad sizes (C %% 4 must be 0)");
   hipStream_t st = as_stream(stream);
+  const int nbins = pooled_h * pooled_w;
   MoiLevels lv = {};
   bool all = true;
   for (int l = 0; l < nlevels; ++l) {
@@ -1499,30 +1327,18 @@ int jtsm_moi_pool_backward_levels_f32(const float* grad, const float* rois, cons
   const bool tiled = scales && workspace && all && small_maps && C % 256 == 0 && M > 0 && B > 0;
   if (tiled) {
     JTSM_REQUIRE(grad && rois && roi_level && argmax, "moi_pool levels backward: null pointer");
-    const size_t need = jtsm_moi_pool_backward_levels_workspace_bytes(H, W, nlevels, B, M);
-    JTSM_REQUIRE(workspace_bytes >= need && ((uintptr_t)workspace & 3) == 0,
-                 "moi_pool levels backward: workspace of %zu bytes needed", need);
-    int* lists = reinterpret_cast<int*>(workspace);
-    int* counts = lists + (size_t)nlevels * B * M;
-    int* census = counts + (size_t)nlevels * B;
-    const int ntile = (int)census_tiles(H, W, nlevels, B);
-    int* plan = census + ntile;            // [0] census maximum, [1] number of busy tiles, [2 ...] their indices
-    hipLaunchKernelGGL(moi_roi_lists_kernel, dim3(nlevels * B), dim3(256), 0, st, rois, roi_level, M, B, lists, counts);
     MoiTiles tl = {};
-    int blocks = 0;
-    for (int l = 0; l < nlevels; ++l) {
-      tl.first[l] = blocks;
-      tl.tiles_x[l] = ceil_div(W[l], kTile);
-      tl.tiles_y[l] = ceil_div(H[l], kTileY);
-      blocks += B * tl.tiles_x[l] * tl.tiles_y[l];
-    }
-    tl.first[nlevels] = blocks;
-    JTSM_CHECK_HIP(hipMemsetAsync(census, 0, (size_t)ntile * sizeof(int), st));
+    const int ntile = plan_tiles(H, W, nlevels, B, tl);
+    Arena arena{static_cast<char*>(workspace)};
+    const GatherWs k = carve(arena, nlevels, B, M, ntile);
+    JTSM_REQUIRE(workspace_bytes >= arena.off && ((uintptr_t)workspace & 3) == 0,
+                 "moi_pool levels backward: workspace of %zu bytes needed", arena.off);
+    hipLaunchKernelGGL(moi_roi_lists_kernel, dim3(nlevels * B), dim3(256), 0, st, rois, roi_level, M, B, k.lists, k.counts);
+    JTSM_CHECK_HIP(hipMemsetAsync(k.census, 0, (size_t)ntile * sizeof(int), st));
     hipLaunchKernelGGL(moi_tile_census_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, st, lv, tl, rois, roi_level, M, nlevels,
-                       pooled_h, pooled_w, census);
+                       pooled_h, pooled_w, k.census);
     // the plan: the census maximum and the heavy tiles (4 quadrant entries each), heaviest first
-    int* tile_order = plan + 2 + 4 * (size_t)ntile;   // (behind the busy list's at most 4 entries per tile)
-    hipLaunchKernelGGL(tile_plan_kernel, dim3(1), dim3(1024), 0, st, census, ntile, plan, moi_heavy_min(), 4, tile_order);
+    hipLaunchKernelGGL(tile_plan_kernel, dim3(1), dim3(1024), 0, st, k.census, ntile, k.plan, moi_heavy_min(), 4, k.tile_order);
     // The two gathers write disjoint cells and each ends in a tail of a few long workgroups (the light form's
     // heaviest tiles; the piled quadrants): side by side on two streams the tails overlap.  Fork / join by events on a
     // side stream the library keeps per device (no host synchronisation; the caller's stream waits for the join).
@@ -1535,17 +1351,15 @@ int jtsm_moi_pool_backward_levels_f32(const float* grad, const float* rois, cons
       side = st;
     }
     hipLaunchKernelGGL(moi_pool_bwd_busy, dim3(256), dim3(1024), (size_t)kCopies * kQuad * kQuad * 256 * sizeof(float), side,
-                       lv, tl, grad, rois, argmax, C, M, pooled_h, pooled_w, B, lists, counts, nlevels, plan, accumulate);
-    hipLaunchKernelGGL(moi_pool_bwd_tiled, dim3(blocks, C / 256), dim3(256), kTile * kTile * 256 * sizeof(float), st, lv, tl,
-                       grad, rois, argmax, C, M, pooled_h, pooled_w, B, lists, counts, nlevels, plan, census, moi_heavy_min(),
-                       accumulate, tile_order);
+                       lv, tl, grad, rois, argmax, C, M, pooled_h, pooled_w, B, k.lists, k.counts, nlevels, k.plan, accumulate);
+    hipLaunchKernelGGL(moi_pool_bwd_tiled, dim3(ntile, C / 256), dim3(256), kTile * kTile * 256 * sizeof(float), st, lv, tl,
+                       grad, rois, argmax, C, M, pooled_h, pooled_w, B, k.lists, k.counts, nlevels, k.plan, k.census,
+                       moi_heavy_min(), accumulate, k.tile_order);
     if (side != st) {
       JTSM_CHECK_HIP(hipEventRecord(join, side));
       JTSM_CHECK_HIP(hipStreamWaitEvent(st, join, 0));
     }
-    // (returns at once unless the census sent the gather home)
-    hipLaunchKernelGGL(moi_pool_bwd_levels, dim3(std::min(ceil_div((long)M * pooled_h * pooled_w, 4), 8192)), dim3(256), 0,
-                       st, lv, grad, rois, argmax, C, M, pooled_h * pooled_w, roi_level, nlevels, plan, kCensusLimit);
+    launch_bwd_scatter(lv, nlevels, grad, rois, argmax, C, M, nbins, roi_level, k.plan, st);
     JTSM_CHECK_LAUNCH("moi_pool backward levels (tiled)");
     return JTSM_OK;
   }
@@ -1557,9 +1371,7 @@ int jtsm_moi_pool_backward_levels_f32(const float* grad, const float* rois, cons
   JTSM_REQUIRE(grad && rois && roi_level && argmax, "moi_pool levels backward: null pointer");
   for (int l = 0; l < nlevels; ++l)
     JTSM_REQUIRE(grad_inputs[l], "moi_pool levels backward: every level needs a gradient buffer");
-  const int nbins = pooled_h * pooled_w;
-  hipLaunchKernelGGL(moi_pool_bwd_levels, dim3(std::min(ceil_div((long)M * nbins, 4), 8192)), dim3(256), 0, st, lv, grad,
-                     rois, argmax, C, M, nbins, roi_level, nlevels, (const int*)nullptr, 0);
+  launch_bwd_scatter(lv, nlevels, grad, rois, argmax, C, M, nbins, roi_level, nullptr, st);
   JTSM_CHECK_LAUNCH("moi_pool backward levels");
   return JTSM_OK;
 }

@@ -142,7 +142,9 @@ class _AlignLevels(Function):
 
 
 class _MOILevels(Function):
-    """MOIPool over all FPN levels in one launch each way (csrc/moi_pool.hip: moi_pool_fwd_levels / _bwd_levels)."""
+    """MOIPool over all FPN levels in one call each way (csrc/moi_pool.hip: forward moi_bits_all_kernel + moi_pool_fwd_rows,
+    or moi_pool_fwd_levels for other bin counts / label widths; backward the census, the plan and the two tile gathers
+    moi_pool_bwd_tiled / moi_pool_bwd_busy, or the moi_pool_bwd_levels scatter)."""
 
     @staticmethod
     def forward(ctx, rois, roi_level, res, scales, oh_labels, superpixels, fans, *feats):

@@ -252,6 +252,37 @@ def test_moi_pool_jtsm_shape(cuda, nhwc):
     assert (a0 >= 0).mean() > 0.3  # the case is not degenerate
 
 
+@pytest.mark.parametrize("Cc,Lw", [(8, 128), (6, 128), (8, 96)])
+def test_moi_pool_single_level_nhwc_forms(cuda, Cc, Lw):
+    """The channels-last single-map entry points run the multi-level kernels on a table of one level.  The three
+    forward forms it can take: (8, 128) four label words, the per-(roi, bin row) kernel; (6, 128) C % 4 != 0, a
+    wavefront per (roi, bin) with one channel per lane; (8, 96) three label words, a wavefront per (roi, bin) with four
+    channels per lane.  Values and arg-max bit-exact, the backward (a wavefront per (roi, bin), float atomics) at 1e-5.
+    The 16 x 16 blocks of 4 px carry the ids (block index) mod Lw, so an id lies under two or three blocks; a roi's
+    labels are the ids with a block centre inside the box."""
+    rng = np.random.default_rng(1000 * Cc + Lw)
+    B, H, W, stride, blk, M = 1, 16, 16, 4, 4, 24
+    Hs = Ws = H * stride
+    nb = Hs // blk
+    block = (np.arange(Hs)[:, None] // blk) * nb + (np.arange(Ws)[None, :] // blk)
+    sp = (block % Lw).astype(np.int32)[None]
+    r = _fpn_like_rois(rng, M, B, Hs)
+    centre = np.arange(nb) * blk + blk / 2.0
+    oh = np.zeros((M, Lw), np.int32)
+    for m in range(M):
+        iny = (centre >= r[m, 2]) & (centre <= r[m, 4])
+        inx = (centre >= r[m, 1]) & (centre <= r[m, 3])
+        oh[m, np.unique((np.arange(nb * nb) % Lw)[(iny[:, None] & inx[None, :]).ravel()])] = 1
+    x = rng.standard_normal((B, Cc, H, W)).astype(np.float32)
+    g = rng.standard_normal((M, Cc, 7, 7)).astype(np.float32)
+    y0, a0 = P.moi_pool_forward(x, r, 1.0 / stride, 7, 7, oh, sp)
+    assert (a0 >= 0).mean() > 0.05
+    gx0 = P.moi_pool_backward(g, r, a0, 1.0 / stride, 7, 7, B, Cc, H, W)
+    y, a, gx = run_moi(dict(x=x, rois=r, oh=oh, sp=sp), cuda, True, 1.0 / stride, 7, 7, g=g)
+    assert np.array_equal(a, a0) and np.array_equal(y, y0)
+    assert np.allclose(gx, gx0, rtol=1e-5, atol=1e-5)
+
+
 def test_fpn_level_assignment_and_multilevel_pooling_match_oracle(cuda):
     """the integer FPN level of every box (floor(4 + log2(sqrt(area)/224 + 1e-8)),
     clamped to [2,5]) computed on the device equals the CPU restatement — including boxes sitting exactly
@@ -459,30 +490,66 @@ def test_multilevel_moi_pool_backward_gather_matches_oracle_and_scatter(cuda):
         assert torch.equal(a.grad, b.grad)
 
 
-def test_multilevel_moi_pool_backward_falls_back_when_rois_pile_up(cuda):
-    """More than 4000 (roi, bin) pairs on one 8x8-cell tile (1300 small rois on one spot): the gather only clears the maps and the float-atomic scatter does
-    the work (csrc/moi_pool.hip: census).  Same gradients as the oracle either way."""
+def _moi_census_max(boxes, scale, H, W, P=7, tile=8):
+    """The largest entry of the backward's tile census for rois of one image on one level — csrc/moi_pool.hip,
+    moi_tile_census_kernel, restated: boxes rounded half away from zero, float32 bin sizes, and per overlapped tile an
+    upper bound min(P, int(overlap / bin) + 2) of the bins touching it on each axis."""
+    census = np.zeros(((H + tile - 1) // tile, (W + tile - 1) // tile), np.int64)
+    for box in np.asarray(boxes, np.float32):
+        v = (box * np.float32(scale)).astype(np.float64)
+        x0, y0, x1, y1 = (int(q) for q in np.copysign(np.floor(np.abs(v) + 0.5), v))
+        xa, xz, ya, yz = max(x0, 0), min(x1, W - 1), max(y0, 0), min(y1, H - 1)
+        if xa > xz or ya > yz:
+            continue
+        bw = np.float32(max(x1 - x0 + 1, 1)) / np.float32(P)
+        bh = np.float32(max(y1 - y0 + 1, 1)) / np.float32(P)
+        for ty in range(ya // tile, yz // tile + 1):
+            oy = min(yz, ty * tile + tile - 1) - max(ya, ty * tile) + 1
+            by = min(P, int(np.float32(oy) / bh) + 2)
+            for tx in range(xa // tile, xz // tile + 1):
+                ox = min(xz, tx * tile + tile - 1) - max(xa, tx * tile) + 1
+                census[ty, tx] += by * min(P, int(np.float32(ox) / bw) + 2)
+    return int(census.max())
+
+
+@pytest.mark.parametrize("M", [60, 1300, 2000])
+def test_multilevel_moi_pool_backward_regimes_when_rois_pile_up(cuda, M):
+    """M small rois piled on one spot of one 128x128 image, so that one 8x8-cell tile of level 0 has to take (by the
+    census's estimate, restated in _moi_census_max) 2801, 60823 or 93716 (roi, bin) pairs.  From 1024 pairs on a tile its
+    quadrants go to the busy-tile gather (csrc/moi_pool.hip: moi_pool_bwd_busy), so M = 60 and M = 1300 are gather
+    calls and must give the same bits twice; above 64000 pairs the gathers only clear the maps and the float-atomic
+    scatter does the work (M = 2000).  Same arg-max and gradients as the oracle in every regime."""
     from jtsm_amd.modeling.poolers import ROIPooler
     from jtsm_amd.structures import Boxes
     from oracle import model as OM
 
     rng = np.random.default_rng(43)
     B, Cc, size, sp = 1, 256, 128, 8
-    M = 1300
     x0 = rng.uniform(40, 44, M).astype(np.float32)
     y0 = rng.uniform(40, 44, M).astype(np.float32)
     wh = rng.uniform(17, 30, (M, 2)).astype(np.float32)
     boxes = [torch.from_numpy(np.stack([x0, y0, x0 + wh[:, 0], y0 + wh[:, 1]], 1))]
+    assert int(OM.assign_levels(boxes[0]).max()) == 0          # every roi pools from the stride-4 map
+    census = _moi_census_max(boxes[0].numpy(), 1 / 4, size // 4, size // 4)
+    if M == 2000:
+        assert census > 64000
+    else:
+        assert 1024 <= census <= 64000
     grid = size // sp
     ids = (torch.arange(size)[:, None] // sp) * grid + (torch.arange(size)[None, :] // sp)
     superpixels = ids.to(torch.int32)[None]
     oh = [torch.ones(M, grid * grid, dtype=torch.int32)]
     feats = [rng.standard_normal((B, Cc, (size // 4) >> i, (size // 4) >> i)).astype(np.float32) for i in range(4)]
+    g = rng.standard_normal((M, Cc, 7, 7)).astype(np.float32)
     pooler = ROIPooler(7, [1 / 4, 1 / 8, 1 / 16, 1 / 32], 0, "MOIPool")
-    xs = [dev(f, cuda, True).requires_grad_() for f in feats]
-    y, arg = pooler(xs, [Boxes(boxes[0].to(cuda))], oh_labels_list=[oh[0].to(cuda)], superpixels=superpixels.to(cuda))
-    g = rng.standard_normal(tuple(y.shape)).astype(np.float32)
-    y.backward(dev(g, cuda, True))
+
+    def run():
+        xs = [dev(f, cuda, True).requires_grad_() for f in feats]
+        y, arg = pooler(xs, [Boxes(boxes[0].to(cuda))], oh_labels_list=[oh[0].to(cuda)], superpixels=superpixels.to(cuda))
+        y.backward(dev(g, cuda, True))
+        return xs, arg
+
+    xs, arg = run()
     fr = [torch.from_numpy(f).requires_grad_() for f in feats]
     y0_, a0 = OM.moi_pool_levels(fr, boxes, oh, superpixels)
     y0_.backward(torch.from_numpy(g))
@@ -491,6 +558,10 @@ def test_multilevel_moi_pool_backward_falls_back_when_rois_pile_up(cuda):
         ref = b.grad.numpy()
         assert np.allclose(a.grad.cpu().numpy(), ref, rtol=1e-4, atol=1e-4 * max(1.0, float(np.abs(ref).max())))
     assert float(xs[0].grad.abs().sum()) > 0
+    if M != 2000:
+        xs2, _ = run()
+        for a, b in zip(xs, xs2):
+            assert torch.equal(a.grad, b.grad)
 
 
 def test_roi_align_backward_gather_reproducible_and_fallback(cuda):
