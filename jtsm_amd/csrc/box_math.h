@@ -32,8 +32,14 @@ __device__ __forceinline__ float box_iou(const float4 a, const float4 b) {
   return inter > 0.f ? inter / (aa + ab - inter) : 0.f;
 }
 
+// Row r of a (n, 4) box array: load_box in one 16-byte load, for entry points that require the alignment; box_at in
+// four loads, for those that do not promise it.
 __device__ __forceinline__ float4 load_box(const float* __restrict__ boxes, long r) {
   return *reinterpret_cast<const float4*>(boxes + r * 4);
+}
+__device__ __forceinline__ float4 box_at(const float* __restrict__ boxes, long r) {
+  const float* __restrict__ p = boxes + r * 4;
+  return make_float4(p[0], p[1], p[2], p[3]);
 }
 
 // torchvision's nms IoU test (ops/csrc/cuda/nms_cuda.cu devIoU @0.8.1; the CPU kernel computes the same expression)

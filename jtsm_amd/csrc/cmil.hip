@@ -41,12 +41,12 @@
 //     else bg_lo <= IoU < bg_hi and at most num_neg negatives so far -> num_classes, w; else the seed's class, 0.
 //     With fg >= bg_hi (required) an overflowed positive can never be a negative, so the two caps are two independent
 //     exclusive prefix counts along perm: ballots and a running total per 1024 positions.
-//   The score is S[r, c], or exp(S[r, c] - lse[r]) with lse, as mine_top1 forms it.
+//   The score is class_score (mining_common.h): mine_top1's.
 // No atomics anywhere: the same inputs give the same outputs on every run.
 #include <cfloat>
 
-#include "box_math.h"
-#include "common.h"
+#include "mining_common.h"
+#include "reduce.h"
 #include "workspace.h"
 
 namespace jtsm {
@@ -60,12 +60,6 @@ constexpr int kTop = 200;        // ROIMerge_cpu.cpp:105
 constexpr int kWindow = 40;      // :116
 constexpr int kThreads = 1024;
 constexpr int kMaxSeeds = 256;   // present classes x top_k of one image (LDS: 6 KiB)
-
-__device__ __forceinline__ int image_of(const int* __restrict__ offsets, int nimg, int r) {
-  int i = 0;
-  while (i + 1 < nimg && r >= offsets[i + 1]) ++i;
-  return i;
-}
 
 struct Bag { int off, n, top; };
 __device__ __forceinline__ Bag bag_of(const int* __restrict__ bag_off, int b) {
@@ -86,20 +80,13 @@ __global__ __launch_bounds__(kThreads) void merge_rank_kernel(const float* __res
   // (the grid is sized from the caller's max_bag_rows; the stride makes every row covered whatever it was)
   for (int base = blockIdx.x * kThreads; base < g.n; base += gridDim.x * kThreads) {   // (uniform)
     const int i = base + threadIdx.x;
-    const u64 key = i < g.n ? order_key(S[g.off + i], i) : ~0ull;   // nothing precedes a padding key
-    int before = 0;
-    for (int t0 = 0; t0 < g.n; t0 += kThreads) {
-      const int tn = min(kThreads, g.n - t0);
-      __syncthreads();                                  // the previous tile's readers are done
-      if ((int)threadIdx.x < tn) tile[threadIdx.x] = order_key(S[g.off + t0 + threadIdx.x], t0 + threadIdx.x);
-      __syncthreads();
-#pragma unroll 8
-      for (int j = 0; j < tn; ++j) before += tile[j] > key ? 1 : 0;
-    }
+    const u64 key[1] = {i < g.n ? order_key(S[g.off + i], i) : ~0ull};   // nothing precedes a padding key
+    int before[1];
+    count_before<1, kThreads, kThreads, 8>(g.n, [&](int j) { return order_key(S[g.off + j], j); }, key, 1, before, tile);
     if (i < g.n) {
-      const bool kept = before < kTop;
-      slot[g.off + i] = kept ? before : -1;
-      if (kept) top_row[b * kTop + before] = i;
+      const bool kept = before[0] < kTop;
+      slot[g.off + i] = kept ? before[0] : -1;
+      if (kept) top_row[b * kTop + before[0]] = i;
     }
   }
 }
@@ -271,27 +258,6 @@ MergeWs carve(Arena& a, int B, int R) {
 }
 
 // ---- ROILabel ----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float class_score(const float* __restrict__ scores, int ld, const float* __restrict__ lse,
-                                             int r, int cls) {
-  float v = scores[(size_t)r * ld + cls];
-  if (lse) v = expf(v - lse[r]);      // (as mine_top1_kernel forms it)
-  return v;
-}
-
-// max over the workgroup, the same value in every thread
-__device__ __forceinline__ u64 wg_max(u64 v, u64* __restrict__ wave_slot) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const u64 w = ((u64)(unsigned)__shfl_xor((int)(v >> 32), o) << 32) | (unsigned)__shfl_xor((int)(v & 0xffffffffull), o);
-    v = w > v ? w : v;
-  }
-  __syncthreads();                    // previous readers of wave_slot are done
-  if ((threadIdx.x & 63) == 0) wave_slot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  u64 r = wave_slot[0];
-  for (int w = 1; w < kThreads / 64; ++w) r = wave_slot[w] > r ? wave_slot[w] : r;
-  return r;
-}
-
 __global__ __launch_bounds__(kThreads) void roi_label_kernel(
     const float* __restrict__ S, int ld, const float* __restrict__ lse, const float* __restrict__ boxes,
     const int* __restrict__ bag_off, const int* __restrict__ classes, const int* __restrict__ counts, int G,
@@ -324,9 +290,10 @@ __global__ __launch_bounds__(kThreads) void roi_label_kernel(
           if (!taken) { best = v; at = i; }
         }
       }
-      const u64 key = wg_max(at >= 0 ? order_key(best, at) : 0ull, wave_slot);   // lowest row among equal scores
+      // (order_key: the lowest row among equal scores)
+      const u64 key = wg_reduce<kThreads / 64>(at >= 0 ? order_key(best, at) : 0ull, Max(), wave_slot);
       if (key == 0ull) { out_of_rows = true; break; }   // (uniform)
-      const int row = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
+      const int row = (int)key_index(key);
       if (t == 0) {
         s_row[ns] = row;
         s_cls[ns] = cls;

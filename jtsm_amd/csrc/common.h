@@ -61,11 +61,15 @@ __device__ __forceinline__ float float_from_order_bits(unsigned e) {
 }
 __device__ __forceinline__ unsigned ordered_bits(float v) { return v != v ? 0xffffffffu : float_order_bits(v + 0.f); }
 __device__ __forceinline__ unsigned ordered_desc(float f) { return ~float_order_bits(f); }
-// Total order of (value, index) pairs — higher key = earlier: value descending, then index ascending.  A position in
-// that order is the NUMBER OF KEYS ABOVE one's own: counted, not sorted (mist.hip, cmil.hip).
-__device__ __forceinline__ unsigned long long order_key(float v, int index) {
-  return ((unsigned long long)ordered_bits(v) << 32) | (unsigned long long)(0xffffffffu - (unsigned)index);
+// Key of an arg-max over (unsigned value, index) in which the LOWEST index wins ties: value in the high word, inverted
+// index in the low word; and the index back out of it.
+__device__ __forceinline__ unsigned long long index_key(unsigned v, unsigned index) {
+  return ((unsigned long long)v << 32) | (unsigned long long)(0xffffffffu - index);
 }
+__device__ __forceinline__ unsigned key_index(unsigned long long k) { return 0xffffffffu - (unsigned)(k & 0xffffffffull); }
+// Total order of (value, index) pairs — higher key = earlier: value descending, then index ascending.  A position in
+// that order is the NUMBER OF KEYS ABOVE one's own: counted, not sorted (count_before, mining_common.h).
+__device__ __forceinline__ unsigned long long order_key(float v, int index) { return index_key(ordered_bits(v), (unsigned)index); }
 
 // Ordered compaction of a per-thread flag over the NW wavefronts of the workgroup: this thread's slot (if flagged) and
 // the total; two barriers.

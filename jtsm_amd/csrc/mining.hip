@@ -13,8 +13,8 @@
 // reference's operation order.
 #include <cfloat>
 
-#include "box_math.h"
-#include "common.h"
+#include "mining_common.h"
+#include "reduce.h"
 
 namespace jtsm {
 namespace {
@@ -30,17 +30,16 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ 
   const float* row = z + (size_t)r * ld;
   float mx = -FLT_MAX;
   for (int c = lane; c < ncls; c += 64) mx = fmaxf(mx, row[c]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  mx = wave_max(mx);
   float sm = 0.f;
   for (int c = lane; c < ncls; c += 64) sm += expf(row[c] - mx);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o);
+  sm = wave_sum(sm);
   if (lane == 0) lse[r] = mx + logf(sm);
 }
 
 // One workgroup per (image, class slot): arg-max over the image's proposals of the class score
-// (score = scores[r,cls], or exp(scores[r,cls] - lse[r]) when lse is given); lowest row wins ties.
+// (class_score); lowest row wins ties.  A NaN is never picked, nor a score that does not exceed -FLT_MAX: an image
+// with nothing to pick answers with its first row.
 __global__ __launch_bounds__(256) void mine_top1_kernel(const float* __restrict__ scores, int ld,
                                                         const float* __restrict__ lse,
                                                         const float* __restrict__ proposals,
@@ -52,38 +51,26 @@ __global__ __launch_bounds__(256) void mine_top1_kernel(const float* __restrict_
                                                         int* __restrict__ out_idx, float* __restrict__ out_box,
                                                         float* __restrict__ out_score,
                                                         float* __restrict__ out_weight) {
-  __shared__ float sv[256];
-  __shared__ int si[256];
+  __shared__ BestPair slot[4];
   const int img = blockIdx.x / Gmax, g = blockIdx.x - img * Gmax;
   if (g >= counts[img]) return;
   const int cls = classes[img * Gmax + g];
   const int r0 = bag_off[img], r1 = bag_off[img + 1];
   float best = -FLT_MAX;
-  int at = 0x7fffffff;
+  int at = kNoIndex;
   for (int r = r0 + threadIdx.x; r < r1; r += 256) {
-    float v = scores[(size_t)r * ld + cls];
-    if (lse) v = expf(v - lse[r]);
+    const float v = class_score(scores, ld, lse, r, cls);
     if (v > best) { best = v; at = r; }
   }
-  sv[threadIdx.x] = best;
-  si[threadIdx.x] = at;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      const float v = sv[threadIdx.x + o];
-      const int i = si[threadIdx.x + o];
-      if (v > sv[threadIdx.x] || (v == sv[threadIdx.x] && i < si[threadIdx.x])) { sv[threadIdx.x] = v; si[threadIdx.x] = i; }
-    }
-    __syncthreads();
-  }
+  const BestPair top = wg_arg_best<4>(best, at, slot);
   if (threadIdx.x == 0) {
-    const int r = si[0] == 0x7fffffff ? r0 : si[0];
+    const int r = best_index(top) == kNoIndex ? r0 : best_index(top);
     const int o = img * Gmax + g;
     out_idx[o] = r - r0;
-    out_score[o] = sv[0];
+    out_score[o] = best_value(top);
     out_weight[o] = img_probs[(size_t)img * nprob + cls];
-    if (deltas) decode_box(proposals + 4 * (size_t)r, deltas + (size_t)r * ld_d + 4 * cls, out_box + 4 * o);
-    else for (int k = 0; k < 4; ++k) out_box[4 * o + k] = proposals[4 * (size_t)r + k];
+    const float4 bx = mined_box(proposals, deltas, ld_d, 0, r, cls);
+    out_box[4 * o] = bx.x; out_box[4 * o + 1] = bx.y; out_box[4 * o + 2] = bx.z; out_box[4 * o + 3] = bx.w;
   }
 }
 
@@ -103,20 +90,14 @@ __global__ __launch_bounds__(256) void match_label_kernel(const float* __restric
 #pragma clang fp contract(off)
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
-  int img = 0;
-  while (img + 1 < B && r >= bag_off[img + 1]) ++img;
+  const int img = image_of(bag_off, B, r);
   const float* p = proposals + 4 * (size_t)r;
-  const float area_p = (p[2] - p[0]) * (p[3] - p[1]);
+  const float4 pb = box_at(proposals, r);
   const int n = counts[img];
   float best = -1.f;
   int at = 0;
   for (int g = 0; g < n; ++g) {
-    const float* q = pgt_box + 4 * ((size_t)img * Gmax + g);
-    const float area_q = (q[2] - q[0]) * (q[3] - q[1]);
-    const float w = fmaxf(fminf(q[2], p[2]) - fmaxf(q[0], p[0]), 0.f);
-    const float h = fmaxf(fminf(q[3], p[3]) - fmaxf(q[1], p[1]), 0.f);
-    const float inter = w * h;
-    const float iou = inter > 0.f ? inter / (area_q + area_p - inter) : 0.f;
+    const float iou = box_iou(box_at(pgt_box, (long)img * Gmax + g), pb);   // (target, proposal)
     if (iou > best) { best = iou; at = g; }
   }
   const int o = img * Gmax + at;
@@ -139,25 +120,13 @@ __global__ __launch_bounds__(256) void match_label_kernel(const float* __restric
 // FOREGROUND proposals of its image by IoU with it (torch.topk over pairwise_iou(targets, fg proposals), k = min(#fg,
 // top_k)); ordering here: IoU descending, equal IoUs by ascending proposal row.  One workgroup per (image, pseudo box);
 // round j picks the smallest key (−IoU, row) greater than round j-1's.  near_rows (B, Gmax, K): proposal rows, -1 pad.
-__device__ __forceinline__ float iou_tp(const float* __restrict__ q /* target */, const float* __restrict__ p) {
-#pragma clang fp contract(off)
-  const float area_q = (q[2] - q[0]) * (q[3] - q[1]), area_p = (p[2] - p[0]) * (p[3] - p[1]);
-  const float w = fmaxf(fminf(q[2], p[2]) - fmaxf(q[0], p[0]), 0.f);
-  const float h = fmaxf(fminf(q[3], p[3]) - fmaxf(q[1], p[1]), 0.f);
-  const float inter = w * h;
-  return inter > 0.f ? inter / (area_q + area_p - inter) : 0.f;
-}
-
 __global__ __launch_bounds__(256) void near_targets_kernel(const float* __restrict__ proposals,
                                                            const int* __restrict__ bag_off,
                                                            const int* __restrict__ labels, int bg_label,
                                                            const float* __restrict__ pgt_box,
                                                            const int* __restrict__ counts, int Gmax, int K,
                                                            int* __restrict__ near_rows) {
-  __shared__ float s_iou[256];
-  __shared__ int s_row[256];
-  __shared__ float last_iou;
-  __shared__ int last_row;
+  __shared__ BestPair slot[4];
   const int img = blockIdx.x / Gmax, g = blockIdx.x % Gmax;
   int* out = near_rows + (size_t)blockIdx.x * K;
   if (g >= counts[img]) {
@@ -165,38 +134,23 @@ __global__ __launch_bounds__(256) void near_targets_kernel(const float* __restri
     return;
   }
   const int r0 = bag_off[img], r1 = bag_off[img + 1];
-  const float* q = pgt_box + 4 * ((size_t)img * Gmax + g);
-  if (threadIdx.x == 0) { last_iou = 2.f; last_row = -1; }
-  __syncthreads();
+  const float4 q = box_at(pgt_box, (long)img * Gmax + g);
+  float li = 2.f;                                                       // the previous pick (uniform)
+  int lr = -1;
   for (int k = 0; k < K; ++k) {
-    const float li = last_iou;
-    const int lr = last_row;
     float best = -1.f;
-    int at = -1;
+    int at = kNoIndex;
     for (int r = r0 + threadIdx.x; r < r1; r += blockDim.x) {
       if (labels[r] == bg_label || labels[r] < 0) continue;           // foreground proposals only
-      const float v = iou_tp(q, proposals + 4 * (size_t)r);
+      const float v = box_iou(q, box_at(proposals, r));               // (target, proposal)
       const bool after = v < li || (v == li && r > lr);               // strictly after the previous pick
       if (after && (v > best || (v == best && r < at))) { best = v; at = r; }
     }
-    s_iou[threadIdx.x] = best;
-    s_row[threadIdx.x] = at;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-      if (threadIdx.x < st) {
-        const float a = s_iou[threadIdx.x], b = s_iou[threadIdx.x + st];
-        const int ra = s_row[threadIdx.x], rb = s_row[threadIdx.x + st];
-        if (rb >= 0 && (ra < 0 || b > a || (b == a && rb < ra))) { s_iou[threadIdx.x] = b; s_row[threadIdx.x] = rb; }
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      out[k] = s_row[0];
-      last_iou = s_iou[0];
-      last_row = s_row[0] >= 0 ? s_row[0] : 0x7fffffff;   // exhausted: nothing comes after
-      if (s_row[0] < 0) last_iou = -2.f;
-    }
-    __syncthreads();
+    const BestPair top = wg_arg_best<4>(best, at, slot);
+    const bool found = best_index(top) != kNoIndex;
+    if (threadIdx.x == 0) out[k] = found ? best_index(top) : -1;
+    li = found ? best_value(top) : -2.f;                               // exhausted: nothing comes after
+    lr = best_index(top);
   }
 }
 
@@ -211,9 +165,8 @@ __global__ __launch_bounds__(256) void match_near_kernel(const float* __restrict
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
   if (labels[r] == bg_label || labels[r] < 0) { matched_near[r] = -1; return; }
-  int img = 0;
-  while (img + 1 < B && r >= bag_off[img + 1]) ++img;
-  const float* p = proposals + 4 * (size_t)r;
+  const int img = image_of(bag_off, B, r);
+  const float4 p = box_at(proposals, r);
   float best = -1.f;
   int at = -1;
   const int n = counts[img];
@@ -221,107 +174,91 @@ __global__ __launch_bounds__(256) void match_near_kernel(const float* __restrict
     for (int k = 0; k < K; ++k) {
       const int row = near_rows[((size_t)img * Gmax + g) * K + k];
       if (row < 0) break;
-      const float v = iou_tp(proposals + 4 * (size_t)row, p);
+      const float v = box_iou(box_at(proposals, row), p);                 // (target, proposal)
       if (v > best) { best = v; at = row; }
     }
   matched_near[r] = at;
 }
 
-// ---- pseudo semantic target (get_pgt_sem_seg, roi_heads_jtsm.py:2025-2070, with the rectangle substitution of
-// SURVEY F8): every pseudo box paints its rectangle shrunk by `erode` pixels with value class - class_base, in
-// ascending score order (the best box ends on top); then, in list order, a class whose pixels were all painted
-// over is painted once more.  Pass A is pixel-parallel (max score RANK among the covering boxes) and counts the
-// pixels of every value; pass B (one workgroup per image) replays the sequential "missing class" rule on those
-// counts, touching only the rectangles it repaints.  No host synchronisation: list lengths stay on the device.
-__device__ __forceinline__ bool paint_inside(const float* __restrict__ b, int x, int y, float erode) {
-  const float xs = (float)x + 0.5f, ys = (float)y + 0.5f;
-  return xs >= b[0] + erode && xs <= b[2] - erode && ys >= b[1] + erode && ys <= b[3] - erode;
-}
-
+// ---- pseudo semantic target (get_pgt_sem_seg, roi_heads_jtsm.py:2025-2070): every pseudo target paints the pixels it
+// covers with value class - class_base, in ascending score order (the best target ends on top); then, in list order, a
+// class whose pixels were all painted over is painted once more.  The top pass is pixel-parallel (max score RANK among
+// the covering targets) and counts the pixels of every value; the missing pass (one workgroup per image) replays the
+// sequential "missing class" rule on those counts, touching only the pixels it repaints.  No host synchronisation:
+// list lengths stay on the device.  What a target covers is the Cover policy's:
+//   RectCover      the rectangle substitution of SURVEY F8: the target's box shrunk by `erode` pixels; a repaint walks
+//                  the eroded box's bounding rectangle.
+//   EvidenceCover  the reference's masks (need_mask=True -> get_pgt_top_k :1333-1334 -> object_evidence :1928-1994,
+//                  superpixel branch): the union of the superpixels the target's oh_labels row marks,
+//                  mask_j(y, x) = oh_labels[row_j][superpixels[y][x]] != 0 (a superpixel id outside [0, L) belongs to no
+//                  mask: the reference's `poses` loop covers range(L) only); a repaint walks the whole image.  The
+//                  full-image masks are never rasterised.
+// A policy names its per-target state (Target, staged in LDS by the top pass), what it reads of a pixel (Pixel, with
+// its flat index `at`), the pixels a repaint of one target walks (Domain) and the coverage test.
 constexpr int kPaintValues = 64;   // painted values are 1 .. 63 (0 = untouched)
+constexpr int kPaintTargets = 64;  // targets per image
 
-__global__ __launch_bounds__(256) void paint_top_kernel(const float* __restrict__ boxes, const int* __restrict__ classes,
+struct RectCover {
+  const float* __restrict__ boxes;   // (B, G, 4)
+  float erode;
+  struct Target { float b[4]; };
+  struct Pixel { long at; int x, y; };
+  struct Domain { int x0, y0, bw; long count; };
+  __device__ Target target(int b, int G, int j) const {
+    Target t;
+    for (int e = 0; e < 4; ++e) t.b[e] = boxes[((size_t)b * G + j) * 4 + e];
+    return t;
+  }
+  __device__ Pixel pixel(int, long at, int, int W) const {
+    const int y = (int)(at / W);
+    return {at, (int)(at - (long)y * W), y};
+  }
+  __device__ Domain domain(const Target& t, int H, int W) const {
+    const int x0 = max(0, (int)floorf(t.b[0] + erode - 0.5f)), x1 = min(W - 1, (int)ceilf(t.b[2] - erode - 0.5f));
+    const int y0 = max(0, (int)floorf(t.b[1] + erode - 0.5f)), y1 = min(H - 1, (int)ceilf(t.b[3] - erode - 0.5f));
+    const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
+    return {x0, y0, bw, bw > 0 && bh > 0 ? (long)bw * bh : 0};
+  }
+  __device__ Pixel pixel_of(int, const Domain& d, long i, int, int W) const {
+    const int y = d.y0 + (int)(i / d.bw), x = d.x0 + (int)(i % d.bw);
+    return {(long)y * W + x, x, y};
+  }
+  __device__ bool covers(const Target& t, const Pixel& p) const {
+    const float xs = (float)p.x + 0.5f, ys = (float)p.y + 0.5f;
+    return xs >= t.b[0] + erode && xs <= t.b[2] - erode && ys >= t.b[1] + erode && ys <= t.b[3] - erode;
+  }
+};
+
+struct EvidenceCover {
+  const int* __restrict__ target_idx;    // (B, G) row of the target within its image
+  const int* __restrict__ bag_offsets;
+  const int* __restrict__ oh_labels;     // (R, L)
+  int L;
+  const int* __restrict__ superpixels;   // (B, H, W)
+  struct Target { const int* row; };
+  struct Pixel { long at; int s; };      // s: the pixel's superpixel, -1 when it is outside [0, L)
+  struct Domain { long count; };
+  __device__ Target target(int b, int G, int j) const {
+    return {oh_labels + ((long)bag_offsets[b] + target_idx[b * G + j]) * L};
+  }
+  __device__ Pixel pixel(int b, long at, int H, int W) const {
+    const int s = superpixels[(size_t)b * H * W + at];
+    return {at, s >= 0 && s < L ? s : -1};
+  }
+  __device__ Domain domain(const Target&, int H, int W) const { return {(long)H * W}; }
+  __device__ Pixel pixel_of(int b, const Domain&, long i, int H, int W) const { return pixel(b, i, H, W); }
+  __device__ bool covers(const Target& t, const Pixel& p) const { return p.s >= 0 && t.row[p.s] != 0; }
+};
+
+template <class Cover>
+__global__ __launch_bounds__(256) void paint_top_kernel(const Cover cover, const int* __restrict__ classes,
                                                         const float* __restrict__ scores, const int* __restrict__ counts,
-                                                        int G, int class_base, int H, int W, float erode,
-                                                        long* __restrict__ out, int* __restrict__ value_counts) {
+                                                        int G, int class_base, int H, int W, long* __restrict__ out,
+                                                        int* __restrict__ value_counts) {
   __shared__ int hist[kPaintValues];
-  __shared__ float sb[64 * 4];
-  __shared__ int srank[64], sval[64];
-  const int b = blockIdx.y, n = min(counts[b], 64);
-  if (threadIdx.x < kPaintValues) hist[threadIdx.x] = 0;
-  if (threadIdx.x < n) {
-    const int j = threadIdx.x;
-    const float sj = scores[b * G + j];
-    int r = 0;   // position of box j in ascending (score, index) order
-    for (int k = 0; k < n; ++k) {
-      const float sk = scores[b * G + k];
-      r += (sk < sj || (sk == sj && k < j)) ? 1 : 0;
-    }
-    srank[j] = r;
-    sval[j] = classes[b * G + j] - class_base;
-    for (int e = 0; e < 4; ++e) sb[j * 4 + e] = boxes[((size_t)b * G + j) * 4 + e];
-  }
-  __syncthreads();
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p < (long)H * W) {
-    const int y = (int)(p / W), x = (int)(p - (long)y * W);
-    int best = -1, val = 0;
-    for (int j = 0; j < n; ++j)
-      if (paint_inside(sb + j * 4, x, y, erode) && srank[j] > best) { best = srank[j]; val = sval[j]; }
-    out[(size_t)b * H * W + p] = val;
-    atomicAdd(&hist[val & (kPaintValues - 1)], 1);
-  }
-  __syncthreads();
-  if (threadIdx.x < kPaintValues && hist[threadIdx.x]) atomicAdd(value_counts + b * kPaintValues + threadIdx.x, hist[threadIdx.x]);
-}
-
-__global__ __launch_bounds__(256) void paint_missing_kernel(const float* __restrict__ boxes, const int* __restrict__ classes,
-                                                            const int* __restrict__ counts, int G, int class_base, int H,
-                                                            int W, float erode, long* __restrict__ out,
-                                                            const int* __restrict__ value_counts) {
-  __shared__ int cnt[kPaintValues];
-  const int b = blockIdx.x, n = min(counts[b], 64);
-  if (threadIdx.x < kPaintValues) cnt[threadIdx.x] = value_counts[b * kPaintValues + threadIdx.x];
-  __syncthreads();
-  long* img = out + (size_t)b * H * W;
-  for (int j = 0; j < n; ++j) {
-    const int v = (classes[b * G + j] - class_base) & (kPaintValues - 1);
-    const bool missing = cnt[v] == 0;   // uniform: read before anyone updates it in this round
-    __syncthreads();
-    if (missing) {
-      const float* bx = boxes + ((size_t)b * G + j) * 4;
-      const int x0 = max(0, (int)floorf(bx[0] + erode - 0.5f)), x1 = min(W - 1, (int)ceilf(bx[2] - erode - 0.5f));
-      const int y0 = max(0, (int)floorf(bx[1] + erode - 0.5f)), y1 = min(H - 1, (int)ceilf(bx[3] - erode - 0.5f));
-      const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
-      if (bw > 0 && bh > 0)
-        for (long i = threadIdx.x; i < (long)bw * bh; i += 256) {
-          const int y = y0 + (int)(i / bw), x = x0 + (int)(i % bw);
-          if (!paint_inside(bx, x, y, erode)) continue;
-          const long old = img[(size_t)y * W + x];
-          img[(size_t)y * W + x] = v;
-          atomicSub(&cnt[(int)old & (kPaintValues - 1)], 1);
-          atomicAdd(&cnt[v], 1);
-        }
-    }
-    __syncthreads();
-  }
-}
-
-
-// ---- pseudo semantic target with the reference's masks (get_pgt_sem_seg :2038-2069 with need_mask=True ->
-// get_pgt_top_k :1333-1334 -> object_evidence :1928-1994, superpixel branch): target j's mask is the union of the
-// superpixels its oh_labels row marks, mask_j(y, x) = oh_labels[row_j][superpixels[y][x]] != 0 (a superpixel id outside
-// [0, L) belongs to no mask: the reference's `poses` loop covers range(L) only).  Same two passes as above; the
-// full-image masks are never rasterised.
-__global__ __launch_bounds__(256) void paint_top_evidence_kernel(
-    const int* __restrict__ target_idx, const int* __restrict__ bag_offsets, const int* __restrict__ oh_labels, int L,
-    const int* __restrict__ superpixels, const int* __restrict__ classes, const float* __restrict__ scores,
-    const int* __restrict__ counts, int G, int class_base, int H, int W, long* __restrict__ out,
-    int* __restrict__ value_counts) {
-  __shared__ int hist[kPaintValues];
-  __shared__ int srank[64], sval[64];
-  __shared__ long srow[64];
-  const int b = blockIdx.y, n = min(counts[b], 64);
+  __shared__ typename Cover::Target starget[kPaintTargets];
+  __shared__ int srank[kPaintTargets], sval[kPaintTargets];
+  const int b = blockIdx.y, n = min(counts[b], kPaintTargets);
   if (threadIdx.x < kPaintValues) hist[threadIdx.x] = 0;
   if (threadIdx.x < n) {
     const int j = threadIdx.x;
@@ -333,16 +270,15 @@ __global__ __launch_bounds__(256) void paint_top_evidence_kernel(
     }
     srank[j] = r;
     sval[j] = classes[b * G + j] - class_base;
-    srow[j] = ((long)bag_offsets[b] + target_idx[b * G + j]) * L;
+    starget[j] = cover.target(b, G, j);
   }
   __syncthreads();
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
   if (p < (long)H * W) {
-    const int s = superpixels[(size_t)b * H * W + p];
+    const typename Cover::Pixel px = cover.pixel(b, p, H, W);
     int best = -1, val = 0;
-    if (s >= 0 && s < L)
-      for (int j = 0; j < n; ++j)
-        if (srank[j] > best && oh_labels[srow[j] + s] != 0) { best = srank[j]; val = sval[j]; }
+    for (int j = 0; j < n; ++j)   // the highest rank that covers the pixel
+      if (srank[j] > best && cover.covers(starget[j], px)) { best = srank[j]; val = sval[j]; }
     out[(size_t)b * H * W + p] = val;
     atomicAdd(&hist[val & (kPaintValues - 1)], 1);
   }
@@ -350,33 +286,50 @@ __global__ __launch_bounds__(256) void paint_top_evidence_kernel(
   if (threadIdx.x < kPaintValues && hist[threadIdx.x]) atomicAdd(value_counts + b * kPaintValues + threadIdx.x, hist[threadIdx.x]);
 }
 
-__global__ __launch_bounds__(1024) void paint_missing_evidence_kernel(
-    const int* __restrict__ target_idx, const int* __restrict__ bag_offsets, const int* __restrict__ oh_labels, int L,
-    const int* __restrict__ superpixels, const int* __restrict__ classes, const int* __restrict__ counts, int G,
-    int class_base, int H, int W, long* __restrict__ out, const int* __restrict__ value_counts) {
+template <class Cover, int THREADS>
+__global__ __launch_bounds__(THREADS) void paint_missing_kernel(const Cover cover, const int* __restrict__ classes,
+                                                                const int* __restrict__ counts, int G, int class_base,
+                                                                int H, int W, long* __restrict__ out,
+                                                                const int* __restrict__ value_counts) {
   __shared__ int cnt[kPaintValues];
-  const int b = blockIdx.x, n = min(counts[b], 64);
+  const int b = blockIdx.x, n = min(counts[b], kPaintTargets);
   if (threadIdx.x < kPaintValues) cnt[threadIdx.x] = value_counts[b * kPaintValues + threadIdx.x];
   __syncthreads();
   long* img = out + (size_t)b * H * W;
-  const int* sp = superpixels + (size_t)b * H * W;
   for (int j = 0; j < n; ++j) {
     const int v = (classes[b * G + j] - class_base) & (kPaintValues - 1);
     const bool missing = cnt[v] == 0;   // uniform: read before anyone updates it in this round
     __syncthreads();
     if (missing) {
-      const int* row = oh_labels + ((long)bag_offsets[b] + target_idx[b * G + j]) * L;
-      for (long i = threadIdx.x; i < (long)H * W; i += 1024) {
-        const int s = sp[i];
-        if (s < 0 || s >= L || row[s] == 0) continue;
-        const long old = img[i];
-        img[i] = v;
+      const typename Cover::Target t = cover.target(b, G, j);
+      const typename Cover::Domain d = cover.domain(t, H, W);
+      for (long i = threadIdx.x; i < d.count; i += THREADS) {
+        const typename Cover::Pixel px = cover.pixel_of(b, d, i, H, W);
+        if (!cover.covers(t, px)) continue;
+        const long old = img[px.at];
+        img[px.at] = v;
         atomicSub(&cnt[(int)old & (kPaintValues - 1)], 1);
         atomicAdd(&cnt[v], 1);
       }
     }
     __syncthreads();
   }
+}
+
+// The two passes of one painter; value_counts (B, kPaintValues) is the workspace.
+template <class Cover, int MISSING_THREADS>
+int paint_sem_seg(const Cover& cover, const int* classes, const float* scores, const int* counts, int B, int G,
+                  int class_base, int H, int W, int64_t* out, void* workspace, void* stream, const char* what) {
+  hipStream_t st = as_stream(stream);
+  int* value_counts = reinterpret_cast<int*>(workspace);
+  JTSM_CHECK_HIP(hipMemsetAsync(value_counts, 0, (size_t)B * kPaintValues * sizeof(int), st));
+  const long hw = (long)H * W;
+  hipLaunchKernelGGL((paint_top_kernel<Cover>), dim3((unsigned)((hw + 255) / 256), B), dim3(256), 0, st, cover, classes,
+                     scores, counts, G, class_base, H, W, reinterpret_cast<long*>(out), value_counts);
+  hipLaunchKernelGGL((paint_missing_kernel<Cover, MISSING_THREADS>), dim3(B), dim3(MISSING_THREADS), 0, st, cover, classes,
+                     counts, G, class_base, H, W, reinterpret_cast<long*>(out), value_counts);
+  JTSM_CHECK_LAUNCH(what);
+  return JTSM_OK;
 }
 
 
@@ -390,11 +343,6 @@ struct ImageRows {
   const void* ptr[kMaxImages];
   int first[kMaxImages + 1];      // first[b] .. first[b + 1]: the rows of image b in the concatenation
 };
-__device__ __forceinline__ int image_of_row(const ImageRows& im, int B, int m) {
-  int b = 0;
-  while (b + 1 < B && m >= im.first[b + 1]) ++b;
-  return b;
-}
 
 // detectron2 poolers.py:22-58 + 61-95 as ONE pass: rois (M,5) = [image, x0, y0, x1, y1] and the 0-based level
 //   floor(canonical_level + log2(sqrt(area) / canonical_size + 1e-8)) clamped to [min_level, max_level] (NaN -> min).
@@ -406,7 +354,7 @@ __global__ __launch_bounds__(256) void pooler_rois_levels_kernel(const ImageRows
 #pragma clang fp contract(off)
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= M) return;
-  const int b = image_of_row(im, B, m);
+  const int b = image_of(im.first, B, m);
   const float4 bx = reinterpret_cast<const float4*>(im.ptr[b])[m - im.first[b]];
   rois[(size_t)m * 5 + 0] = (float)b;
   rois[(size_t)m * 5 + 1] = bx.x; rois[(size_t)m * 5 + 2] = bx.y;
@@ -428,7 +376,7 @@ __global__ __launch_bounds__(256) void roi_scale_kernel(const int* __restrict__ 
   if (m >= M) return;
   int nvalid = 0;
   for (int i = 0; i < bins; ++i) nvalid += arg[((size_t)m * bins + i) * C] != -1;
-  const int b = image_of_row(obj, B, m);
+  const int b = image_of(obj.first, B, m);
   const float o = reinterpret_cast<const float*>(obj.ptr[b])[m - obj.first[b]];
   out[m] = ((float)bins * (1.0f / ((float)nvalid + 1.0f))) * (o + 1.0f);
 }
@@ -510,9 +458,8 @@ __global__ __launch_bounds__(1024) void fg_compact_kernel(const int* __restrict_
     int cnt;
     const int slot = filled + compact_wg<16>(fg, wave_count, cnt);
     if (fg) {
-      int b = 0;
-      while (b + 1 < B && r >= bag_offsets[b + 1]) ++b;
-      const float4 bx = reinterpret_cast<const float4*>(boxes)[r];
+      const int b = image_of(bag_offsets, B, r);
+      const float4 bx = load_box(boxes, r);
       fg_rows[slot] = r;
       reinterpret_cast<float4*>(fg_boxes)[slot] = bx;
       fg_classes[slot] = lab;
@@ -598,16 +545,8 @@ int jtsm_paint_sem_seg(const float* boxes, const int32_t* classes, const float* 
   JTSM_REQUIRE(B >= 0 && G > 0 && G <= 64 && H > 0 && W > 0, "paint_sem_seg: bad sizes (at most 64 boxes per image)");
   if (B == 0) return JTSM_OK;
   JTSM_REQUIRE(boxes && classes && scores && counts && out && workspace, "paint_sem_seg: null pointer");
-  hipStream_t st = as_stream(stream);
-  int* value_counts = reinterpret_cast<int*>(workspace);
-  JTSM_CHECK_HIP(hipMemsetAsync(value_counts, 0, (size_t)B * kPaintValues * sizeof(int), st));
-  const long hw = (long)H * W;
-  hipLaunchKernelGGL(paint_top_kernel, dim3((unsigned)((hw + 255) / 256), B), dim3(256), 0, st, boxes, classes, scores,
-                     counts, G, class_base, H, W, erode, reinterpret_cast<long*>(out), value_counts);
-  hipLaunchKernelGGL(paint_missing_kernel, dim3(B), dim3(256), 0, st, boxes, classes, counts, G, class_base, H, W, erode,
-                     reinterpret_cast<long*>(out), value_counts);
-  JTSM_CHECK_LAUNCH("paint_sem_seg");
-  return JTSM_OK;
+  return paint_sem_seg<RectCover, 256>({boxes, erode}, classes, scores, counts, B, G, class_base, H, W, out, workspace,
+                                       stream, "paint_sem_seg");
 }
 
 int jtsm_paint_sem_seg_evidence(const int32_t* target_idx, const int32_t* bag_offsets, const int32_t* oh_labels, int L,
@@ -619,17 +558,8 @@ int jtsm_paint_sem_seg_evidence(const int32_t* target_idx, const int32_t* bag_of
   if (B == 0) return JTSM_OK;
   JTSM_REQUIRE(target_idx && bag_offsets && oh_labels && superpixels && classes && scores && counts && out && workspace,
                "paint_sem_seg_evidence: null pointer");
-  hipStream_t st = as_stream(stream);
-  int* value_counts = reinterpret_cast<int*>(workspace);
-  JTSM_CHECK_HIP(hipMemsetAsync(value_counts, 0, (size_t)B * kPaintValues * sizeof(int), st));
-  const long hw = (long)H * W;
-  hipLaunchKernelGGL(paint_top_evidence_kernel, dim3((unsigned)((hw + 255) / 256), B), dim3(256), 0, st, target_idx,
-                     bag_offsets, oh_labels, L, superpixels, classes, scores, counts, G, class_base, H, W,
-                     reinterpret_cast<long*>(out), value_counts);
-  hipLaunchKernelGGL(paint_missing_evidence_kernel, dim3(B), dim3(1024), 0, st, target_idx, bag_offsets, oh_labels, L,
-                     superpixels, classes, counts, G, class_base, H, W, reinterpret_cast<long*>(out), value_counts);
-  JTSM_CHECK_LAUNCH("paint_sem_seg_evidence");
-  return JTSM_OK;
+  return paint_sem_seg<EvidenceCover, 1024>({target_idx, bag_offsets, oh_labels, L, superpixels}, classes, scores, counts,
+                                            B, G, class_base, H, W, out, workspace, stream, "paint_sem_seg_evidence");
 }
 
 namespace {

@@ -5,7 +5,7 @@
 // Per image b with n proposals, c = counts[b] present classes and t = min(top_t[b], n):
 //   1. per class slot g < c, the t rows with the highest class score, descending, equal scores by ascending row
 //      (torch.topk, :730-733); candidate (j, g) has list index j * c + g (the (t, c) tensor flattened, :783-785);
-//      its box is the proposal, or the class's box decoded from the deltas (decode_box: mine_top1's);
+//      its box is mined_box (mining_common.h: mine_top1's);
 //   2. one greedy NMS over the t * c candidates as a single class (batched_nms with all-zero idxs, :564-568: the
 //      coordinate offset is zero): visited by descending score, equal scores by ascending list index, a candidate is
 //      dropped when its IoU with an earlier survivor is > iou_thresh (iou_above: the detections' NMS test);
@@ -28,8 +28,8 @@
 // Nothing depends on the arrival order of atomics: there are none.
 #include <cfloat>
 
-#include "box_math.h"
-#include "common.h"
+#include "mining_common.h"
+#include "reduce.h"
 #include "workspace.h"
 
 namespace jtsm {
@@ -41,14 +41,7 @@ constexpr int kThreads = 1024;
 constexpr int kOwn = 8;         // rows a thread counts for in one pass of mist_topk
 constexpr int kTile = 4096;     // keys in LDS at a time
 
-// (ordered_bits, order_key — score descending, then index ascending: common.h)
-
-__device__ __forceinline__ float class_score(const float* __restrict__ scores, int ld, const float* __restrict__ lse,
-                                             int r, int cls) {
-  float v = scores[(size_t)r * ld + cls];
-  if (lse) v = expf(v - lse[r]);      // (as mine_top1_kernel forms it)
-  return v;
-}
+// (order_key — score descending, then index ascending: common.h; class_score, mined_box, count_before: mining_common.h)
 
 struct ImageList { int r0, n, c, t, N; };
 __device__ __forceinline__ ImageList image_list(const int* __restrict__ bag_off, const int* __restrict__ counts,
@@ -82,20 +75,9 @@ __global__ __launch_bounds__(kThreads) void mist_topk_kernel(
       const int i = own0 + u * kThreads + (int)threadIdx.x;
       val[u] = (u < own_n && i < l.n) ? class_score(scores, ld, lse, l.r0 + i, cls) : 0.f;
       key[u] = (u < own_n && i < l.n) ? order_key(val[u], i) : ~0ull;   // nothing precedes a padding key
-      before[u] = 0;
     }
-    for (int t0 = 0; t0 < l.n; t0 += kTile) {
-      const int tn = min(kTile, l.n - t0);
-      __syncthreads();                                  // the previous tile's readers are done
-      for (int i = threadIdx.x; i < tn; i += kThreads) tile[i] = order_key(class_score(scores, ld, lse, l.r0 + t0 + i, cls), t0 + i);
-      __syncthreads();
-      for (int i = 0; i < tn; ++i) {
-        const u64 k = tile[i];
-#pragma unroll
-        for (int u = 0; u < kOwn; ++u)
-          if (u < own_n) before[u] += k > key[u] ? 1 : 0;
-      }
-    }
+    count_before<kOwn, kTile, kThreads, 0>(l.n, [&](int i) { return order_key(class_score(scores, ld, lse, l.r0 + i, cls), i); }, key,
+                                           own_n, before, tile);
 #pragma unroll
     for (int u = 0; u < kOwn; ++u) {
       const int i = own0 + u * kThreads + (int)threadIdx.x;
@@ -104,16 +86,7 @@ __global__ __launch_bounds__(kThreads) void mist_topk_kernel(
         const int r = l.r0 + i;
         cand_score[o] = val[u];
         cand_row[o] = i;
-        float bx[4];
-        if (deltas) {
-          decode_box(proposals + 4 * (size_t)r, deltas + (size_t)r * ld_d + 4 * cls, bx);
-        } else if (decode_zero) {                       // a branch without regression: the reference decodes zeros
-          const float zero[4] = {0.f, 0.f, 0.f, 0.f};
-          decode_box(proposals + 4 * (size_t)r, zero, bx);
-        } else {
-          for (int k = 0; k < 4; ++k) bx[k] = proposals[4 * (size_t)r + k];
-        }
-        cand_box[o] = make_float4(bx[0], bx[1], bx[2], bx[3]);
+        cand_box[o] = mined_box(proposals, deltas, ld_d, decode_zero, r, cls);
       }
     }
   }
@@ -129,28 +102,13 @@ __global__ __launch_bounds__(kThreads) void mist_rank_kernel(
   if ((int)blockIdx.x * kThreads >= l.N) return;        // (uniform)
   const float* sc = cand_score + (size_t)b * P;
   const int i = blockIdx.x * kThreads + threadIdx.x;
-  const u64 key = i < l.N ? order_key(sc[i], i) : ~0ull;
-  int before = 0;
-  for (int t0 = 0; t0 < l.N; t0 += kThreads) {
-    const int tn = min(kThreads, l.N - t0);
-    __syncthreads();
-    if ((int)threadIdx.x < tn) tile[threadIdx.x] = order_key(sc[t0 + threadIdx.x], t0 + threadIdx.x);
-    __syncthreads();
-    for (int j = 0; j < tn; ++j) before += tile[j] > key ? 1 : 0;
-  }
+  const u64 key[1] = {i < l.N ? order_key(sc[i], i) : ~0ull};
+  int before[1];
+  count_before<1, kThreads, kThreads, 0>(l.N, [&](int j) { return order_key(sc[j], j); }, key, 1, before, tile);
   if (i < l.N) {
-    sorted_box[(size_t)b * P + before] = cand_box[(size_t)b * P + i];
-    sorted_idx[(size_t)b * P + before] = i;
+    sorted_box[(size_t)b * P + before[0]] = cand_box[(size_t)b * P + i];
+    sorted_idx[(size_t)b * P + before[0]] = i;
   }
-}
-
-__device__ __forceinline__ float4 shfl_box(const float4& v, int src) {
-  return make_float4(__shfl(v.x, src), __shfl(v.y, src), __shfl(v.z, src), __shfl(v.w, src));
-}
-__device__ __forceinline__ u64 shfl_word(u64 v, int src) {
-  const int lo = __shfl((int)(unsigned)(v & 0xffffffffull), src);
-  const int hi = __shfl((int)(unsigned)(v >> 32), src);
-  return ((u64)(unsigned)hi << 32) | (unsigned)lo;
 }
 
 // out_box is read back by the workgroup that writes it (behind a barrier): no __restrict__, no const.
@@ -184,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void mist_nms_kernel(
         }
         u64 gone = ~__ballot(live), kept = 0;
         for (int j = 0; j < 64; ++j) {
-          const u64 w = shfl_word(mine, j);
+          const u64 w = shfl64(mine, j);
           if (!((gone >> j) & 1ull)) { kept |= 1ull << j; gone |= w; }
         }
         const int slot = __popcll(kept & ((1ull << lane) - 1ull));

@@ -6,6 +6,7 @@
 // words per row (a class never has more than max_per_class members; the includer's kernel) -> one wavefront per class
 // walks its segment -> second radix sort puts the survivors first, by descending score, ties by index.
 #pragma once
+#include "reduce.h"
 #include "sorted_segments.h"
 #include "workspace.h"
 
@@ -33,8 +34,7 @@ __global__ void nms_header_init(NmsHeader* h) {
 __device__ __forceinline__ void header_accumulate(NmsHeader* h, bool ok, float cmax) {
   // wave-level reduction, then one atomic per wavefront (integer atomics: order-independent results)
   const u64 b = __ballot(ok);
-  unsigned m = float_order_bits(ok ? cmax : -INFINITY);
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+  const unsigned m = wave_reduce(float_order_bits(ok ? cmax : -INFINITY), Max());
   if ((threadIdx.x & 63) == 0 && b) {
     atomicAdd(&h->n_valid, __popcll(b));
     atomicMax(&h->max_coord, m);
@@ -47,12 +47,6 @@ __global__ __launch_bounds__(256) void nms_keys_kernel(const float* __restrict__
   if (e >= N) return;
   key[e] = ((u64)(unsigned)eclass[e] << 32) | ordered_desc(escore[e]);
   iota[e] = e;
-}
-
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-  const int lo = __shfl((int)(unsigned)(v & 0xffffffffull), src);
-  const int hi = __shfl((int)(unsigned)(v >> 32), src);
-  return ((u64)(unsigned)hi << 32) | (unsigned)lo;
 }
 
 // One wavefront per class walks its segment in score order.  Per 64-row block: the intra-block decisions are made

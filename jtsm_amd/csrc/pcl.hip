@@ -35,8 +35,9 @@
 // the same inputs give the same tables on every run.
 #include <algorithm>
 
-#include "box_math.h"
-#include "common.h"
+#include "mining_common.h"
+#include "reduce.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
@@ -57,29 +58,7 @@ __device__ __forceinline__ float clip_prob(float v) { return fminf(fmaxf(v, kCli
 
 // (box_iou — detectron2's pairwise_iou, un-contracted — and load_box: box_math.h)
 
-// Workgroup reductions: a butterfly inside the wavefront (both partners form the same sum, so every lane holds the
-// same value), then a fold of the per-wave values in wave order.  `slot` is a __shared__ array of one value per wave.
-template <class T, class Op>
-__device__ __forceinline__ T wg_reduce(T v, Op op, T* __restrict__ slot) {
-  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
-  __syncthreads();                       // previous readers of slot are done
-  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T r = slot[0];
-  const int nw = blockDim.x >> 6;
-  for (int w = 1; w < nw; ++w) r = op(r, slot[w]);
-  return r;
-}
-
-struct MaxU64 { __device__ u64 operator()(u64 a, u64 b) const { return a > b ? a : b; } };
-struct MaxF { __device__ float operator()(float a, float b) const { return fmaxf(a, b); } };
-struct MinF { __device__ float operator()(float a, float b) const { return fminf(a, b); } };
-struct AddD { __device__ double operator()(double a, double b) const { return a + b; } };
-struct AddU64 { __device__ u64 operator()(u64 a, u64 b) const { return a + b; } };
-
-// key of an arg-max with the LOWEST index winning ties: value in the high word, inverted index in the low word
-__device__ __forceinline__ u64 argmax_key(unsigned v, unsigned idx) { return ((u64)v << 32) | (0xFFFFFFFFu - idx); }
-__device__ __forceinline__ unsigned key_index(u64 k) { return 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull); }
+// (wg_reduce and its ops: reduce.h; index_key / key_index — an arg-max whose LOWEST index wins ties: common.h)
 
 // ---- centre search: one workgroup of 1024 per image ------------------------------------------------------------------
 // ws_adj: (max_rows, words) u64 adjacency rows of the top-ranking set; ws_keep_node / ws_keep_score: the centres the
@@ -133,14 +112,14 @@ __global__ __launch_bounds__(kThreads) void pcl_centres_kernel(
         ++n_local;
         lo = fminf(lo, vals[q]);
         hi = fmaxf(hi, vals[q]);
-        amax = max(amax, argmax_key(__float_as_uint(vals[q]), (unsigned)r));   // (positive floats order as their bits)
+        amax = max(amax, index_key(__float_as_uint(vals[q]), (unsigned)r));   // (positive floats order as their bits)
       }
     }
-    const int n = (int)wg_reduce((u64)n_local, AddU64(), slot_u);
+    const int n = (int)wg_reduce((u64)n_local, Add(), slot_u);
     if (n == 0) continue;                                                    // (uniform)
-    lo = wg_reduce(lo, MinF(), slot_f);
-    hi = wg_reduce(hi, MaxF(), slot_f);
-    amax = wg_reduce(amax, MaxU64(), slot_u);
+    lo = wg_reduce(lo, Min(), slot_f);
+    hi = wg_reduce(hi, Max(), slot_f);
+    amax = wg_reduce(amax, Max(), slot_u);
     // ---- Lloyd
     const int nc = min(3, n);
     double ctr[3] = {(double)lo, nc == 3 ? ((double)lo + (double)hi) / 2.0 : (double)hi, (double)hi};
@@ -165,11 +144,11 @@ __global__ __launch_bounds__(kThreads) void pcl_centres_kernel(
         if (best == 0) s0 += v; else if (best == 1) s1 += v; else s2 += v;
         packed += 1ull << (16 * best);
       }
-      packed = wg_reduce(packed, AddU64(), slot_u);
+      packed = wg_reduce(packed, Add(), slot_u);
       if ((packed >> 48) == 0) break;                // no assignment changed (uniform)
-      s0 = wg_reduce(s0, AddD(), slot_d);
-      s1 = wg_reduce(s1, AddD(), slot_d);
-      s2 = wg_reduce(s2, AddD(), slot_d);
+      s0 = wg_reduce(s0, Add(), slot_d);
+      s1 = wg_reduce(s1, Add(), slot_d);
+      s2 = wg_reduce(s2, Add(), slot_d);
       const unsigned n0 = packed & 0xFFFF, n1 = (packed >> 16) & 0xFFFF, n2 = (packed >> 32) & 0xFFFF;
       if (n0) ctr[0] = s0 / (double)n0;
       if (n1) ctr[1] = s1 / (double)n1;
@@ -219,9 +198,9 @@ __global__ __launch_bounds__(kThreads) void pcl_centres_kernel(
         if (!((alive[a >> 6] >> (a & 63)) & 1ull)) continue;
         unsigned deg = 0;
         for (int w = 0; w < words; ++w) deg += __popcll(adj[(size_t)a * words + w] & alive[w]);
-        key = max(key, argmax_key(deg, (unsigned)a));
+        key = max(key, index_key(deg, (unsigned)a));
       }
-      key = wg_reduce(key, MaxU64(), slot_u);
+      key = wg_reduce(key, Max(), slot_u);
       const int deg = (int)(key >> 32);
       if (deg == 0) break;                           // (nothing left; with self edges only when count is 0)
       const int node = (int)key_index(key);
@@ -234,7 +213,7 @@ __global__ __launch_bounds__(kThreads) void pcl_centres_kernel(
           sc = fmaxf(sc, clip_prob(col[(size_t)tlist[b] * ld_prev]));
         }
       }
-      sc = wg_reduce(sc, MaxF(), slot_f);            // (its barriers order the reads of alive above before the update)
+      sc = wg_reduce(sc, Max(), slot_f);            // (its barriers order the reads of alive above before the update)
       if (t < words) alive[t] &= ~nb;
       if (t == 0) { keep_node[nk] = node; keep_score[nk] = sc; }
       ++nk;
@@ -247,9 +226,9 @@ __global__ __launch_bounds__(kThreads) void pcl_centres_kernel(
       u64 key = 0;
       for (int k = t; k < nk; k += kThreads) {
         const float v = keep_score[k];
-        if (v > 0.f) key = max(key, argmax_key(__float_as_uint(v), (unsigned)k));
+        if (v > 0.f) key = max(key, index_key(__float_as_uint(v), (unsigned)k));
       }
-      key = wg_reduce(key, MaxU64(), slot_u);
+      key = wg_reduce(key, Max(), slot_u);
       if (key == 0) break;
       const int k = (int)key_index(key);
       if (t == 0) {
@@ -265,12 +244,6 @@ __global__ __launch_bounds__(kThreads) void pcl_centres_kernel(
     }
   }
   if (t == 0) pc_num[img] = G;
-}
-
-__device__ __forceinline__ int image_of(const int* __restrict__ offsets, int nimg, int r) {
-  int i = 0;
-  while (i + 1 < nimg && r >= offsets[i + 1]) ++i;
-  return i;
 }
 
 // ---- every proposal to its highest-IoU centre: one thread per proposal
@@ -325,8 +298,8 @@ __global__ __launch_bounds__(256) void pcl_stats_kernel(const float* __restrict_
       ++cnt;
       sum += (double)clip_prob(probs[(size_t)r * ld_probs + cls]);
     }
-  sum = wg_reduce(sum, AddD(), slot_d);
-  cnt = wg_reduce(cnt, AddU64(), slot_u);
+  sum = wg_reduce(sum, Add(), slot_d);
+  cnt = wg_reduce(cnt, Add(), slot_u);
   if (threadIdx.x == 0) {
     pci[1] = (int)cnt;
     pcf[1] = (float)((double)pcf[0] * (double)cnt);   // every member carries the centre's score
@@ -362,7 +335,7 @@ __global__ __launch_bounds__(256) void pcl_loss_image_kernel(const float* __rest
   double bg = 0.0;
   for (int r = off + (int)threadIdx.x; r < end; r += 256)
     if (row_label[r] == 0) bg -= (double)row_weight[r] * log((double)fmaxf(probs[(size_t)r * ld_probs], 1e-6f));
-  bg = wg_reduce(bg, AddD(), slot_d);
+  bg = wg_reduce(bg, Add(), slot_d);
   if (threadIdx.x == 0) {
     const int* __restrict__ pci = pc_int + (size_t)img * maxc * 3;
     const float* __restrict__ pcf = pc_flt + (size_t)img * maxc * 3;
@@ -417,7 +390,16 @@ __global__ __launch_bounds__(256) void pcl_backward_kernel(const float* __restri
   }
 }
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+// adj (nimg, rows, words) adjacency bits | keep_node (nimg, rows) | keep_score (nimg, rows), in 16-byte pieces
+struct ClusterWs { u64* adj; int* keep_node; float* keep_score; };
+ClusterWs carve(Arena& a, int nimg, int rows) {
+  const size_t words = ((size_t)rows + 63) / 64;
+  ClusterWs k;
+  k.adj = a.take<u64>((size_t)nimg * rows * words);
+  k.keep_node = a.take<int>((size_t)nimg * rows);
+  k.keep_score = a.take<float>((size_t)nimg * rows);
+  return k;
+}
 
 }  // namespace
 }  // namespace jtsm
@@ -428,8 +410,9 @@ extern "C" {
 
 size_t jtsm_pcl_cluster_workspace_bytes(int nimg, int max_rows) {
   if (nimg <= 0 || max_rows <= 0) return 16;
-  const size_t words = ((size_t)max_rows + 63) / 64;
-  return align16((size_t)nimg * max_rows * words * sizeof(u64)) + 2 * align16((size_t)nimg * max_rows * 4);
+  Arena a{nullptr, false, 16};
+  carve(a, nimg, max_rows);
+  return a.off;
 }
 
 int jtsm_pcl_cluster_f32(const float* boxes, const int32_t* offsets, int nimg, int max_rows, int total_rows,
@@ -451,15 +434,10 @@ int jtsm_pcl_cluster_f32(const float* boxes, const int32_t* offsets, int nimg, i
   hipStream_t st = as_stream(stream);
   const int maxc = kMaxPC * num_classes;
   const int rows_ws = std::max(max_rows, 1);
-  const size_t words = ((size_t)rows_ws + 63) / 64;
-  char* ws = reinterpret_cast<char*>(workspace);
-  u64* adj = reinterpret_cast<u64*>(ws);
-  ws += align16((size_t)nimg * rows_ws * words * sizeof(u64));
-  int* keep_node = reinterpret_cast<int*>(ws);
-  ws += align16((size_t)nimg * rows_ws * 4);
-  float* keep_score = reinterpret_cast<float*>(ws);
+  Arena arena{static_cast<char*>(workspace), false, 16};
+  const ClusterWs k = carve(arena, nimg, rows_ws);
   hipLaunchKernelGGL(pcl_centres_kernel, dim3(nimg), dim3(kThreads), 0, st, boxes, offsets, prev_probs, ld_prev, prev_col0,
-                     labels, num_classes, maxc, rows_ws, adj, keep_node, keep_score, pc_int, pc_flt, pc_num);
+                     labels, num_classes, maxc, rows_ws, k.adj, k.keep_node, k.keep_score, pc_int, pc_flt, pc_num);
   if (total_rows > 0)
     hipLaunchKernelGGL(pcl_assign_kernel, dim3(ceil_div(total_rows, 256)), dim3(256), 0, st, boxes, offsets, nimg, maxc,
                        pc_int, pc_flt, pc_num, row_label, row_assign, row_weight);
@@ -479,7 +457,11 @@ int jtsm_pcl_softmax_f32(const float* logits, int ld, int num_cls, int R, float*
   return JTSM_OK;
 }
 
-size_t jtsm_pcl_loss_workspace_bytes(int nimg) { return align16((size_t)std::max(nimg, 1) * sizeof(double)); }
+size_t jtsm_pcl_loss_workspace_bytes(int nimg) {
+  Arena a{nullptr, false, 16};
+  a.take<double>((size_t)std::max(nimg, 1));   // per_image
+  return a.off;
+}
 
 int jtsm_pcl_loss_forward_f32(const float* probs, int ld_probs, const int32_t* offsets, int nimg, int num_classes,
                               const int32_t* row_label, const float* row_weight, const int32_t* pc_int,

@@ -6,6 +6,7 @@
 #include "box_math.h"
 #include "common.h"
 #include "nms_stages.h"
+#include "reduce.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -19,15 +20,6 @@ struct HeadPtrs { const float* p[kMaxHeads]; };
 // ---------------------------------------------------------------------------------------------------------------
 // OICROutputLayers.predict_probs_K / predict_boxes_K (fast_rcnn_oicr.py:712-783): mean over heads of the row
 // soft-max, mean over heads of the deltas, Box2BoxTransform.apply_deltas.  One wavefront per proposal.
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void oicr_predict_kernel(HeadPtrs logits, HeadPtrs deltas, int heads, int R, int C1,
                                                            int Kb, const float* __restrict__ proposals,
                                                            float wx, float wy, float ww, float wh, float clampv,
@@ -366,7 +358,7 @@ __global__ __launch_bounds__(256) void pan_extent_kernel(const uint8_t* __restri
   } else {
     for (int x = lane; x < W; x += 64) cnt += m[x] != 0;
   }
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  cnt = wave_sum(cnt);
   if (lane == 0 && cnt) {
     atomicAdd(&extent[3 * inst], cnt);
     atomicMin(&extent[3 * inst + 1], y);
@@ -453,7 +445,7 @@ __global__ __launch_bounds__(256) void pan_step_kernel(const uint8_t* __restrict
       for (int x = lane; x < W; x += 64) inter += (m[x] != 0 && p[x] > 0);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) inter += __shfl_xor(inter, o);
+  inter = wave_sum(inter);
   if (lane == 0 && inter) atomicAdd(&counters[visit], inter);
 }
 

@@ -1,6 +1,8 @@
-// One arena for the caller-owned, 256-byte aligned workspaces: an entry point's `carve(Arena&, dims...)` names every
-// buffer once, with its element type and count, and is run twice — over a null base by `*_workspace_bytes` (measure:
-// `off` is the answer) and over the caller's buffer by the call itself.  Host code only.
+// One arena for the caller-owned workspaces: an entry point's `carve(Arena&, dims...)` names every buffer once, with its
+// element type and count, and is run twice — over a null base by `*_workspace_bytes` (measure: `off` is the answer) and
+// over the caller's buffer by the call itself.  Buffers start on multiples of `granule` bytes: 256 everywhere but in
+// the two oldest layouts (the MIL and PCL workspaces), whose published byte counts are sums of 16-byte pieces.
+// Host code only.
 #pragma once
 #include <cstddef>
 
@@ -10,13 +12,14 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct Arena {
   char* base;               // nullptr: measure only
-  bool pad_empty = false;   // an empty buffer still takes 256 bytes (the evaluators) instead of none (NMS, the miners)
+  bool pad_empty = false;   // an empty buffer still takes a granule (the evaluators) instead of none (NMS, the miners)
+  size_t granule = 256;     // a power of two
   size_t off = 0;
 
   template <class T>
   T* take(size_t count) {
     const size_t at = off, bytes = count * sizeof(T);
-    off += align256(bytes || !pad_empty ? bytes : 1);
+    off += ((bytes || !pad_empty ? bytes : 1) + granule - 1) & ~(granule - 1);
     return base ? reinterpret_cast<T*>(base + at) : nullptr;
   }
   size_t mark() const { return off; }   // the ends of a contiguous region that one memset clears

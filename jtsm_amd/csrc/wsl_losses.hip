@@ -19,6 +19,8 @@
 #include <cfloat>
 
 #include "common.h"
+#include "reduce.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
@@ -27,15 +29,48 @@ constexpr int SLOTS = 3;      // classes per lane: nc <= 192
 constexpr int WAVES = 4;      // per workgroup
 constexpr float kTiny = 1e-6f;
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
+// (wave_max, wave_sum: reduce.h)
+
+// Online merge of a (max, sum-exp) partial q into the running (M, Z): Z e^M + q.y e^q.x, rescaled to the new max.
+__device__ __forceinline__ void lse_merge(float& M, float& Z, float2 q) {
+  const float mn = fmaxf(M, q.x);
+  Z = Z * __expf(M - mn) + q.y * __expf(q.x - mn);
+  M = mn;
 }
-__device__ __forceinline__ float wave_sum(float v) {
+
+// Soft-max pieces of one row of n <= 64 * SLOTS values, the lane holding columns lane + 64 k: e[k] = exp(v - max)
+// (0 past n); returns the row max and the sum of e over the row, the same in every lane.
+struct RowStats { float mx, sm; };
+__device__ __forceinline__ RowStats row_softmax(const float* __restrict__ row, int n, int lane, float (&e)[SLOTS]) {
+  RowStats s;
+  s.mx = -FLT_MAX;
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
+  for (int k = 0; k < SLOTS; ++k) {
+    e[k] = lane + 64 * k < n ? row[lane + 64 * k] : -FLT_MAX;
+    s.mx = fmaxf(s.mx, e[k]);
+  }
+  s.mx = wave_max(s.mx);
+  s.sm = 0.f;
+#pragma unroll
+  for (int k = 0; k < SLOTS; ++k) {
+    e[k] = lane + 64 * k < n ? __expf(e[k] - s.mx) : 0.f;
+    s.sm += e[k];
+  }
+  s.sm = wave_sum(s.sm);
+  return s;
+}
+
+// Sum over a workgroup of 256 through an LDS halving tree (NOT the butterfly order of wave_sum: these sums keep the
+// order they have always had); the result is valid in thread 0.
+template <class T>
+__device__ __forceinline__ T tree_sum_256(T v, T* __restrict__ red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  return red[0];
 }
 
 struct SlabRange { int bag, r0, r1; };
@@ -85,12 +120,7 @@ __global__ __launch_bounds__(256) void mil_colstats(const float* __restrict__ D,
       const int c = lane + 64 * k;
       if (c >= nc) continue;
       float M = -FLT_MAX, Z = 0.f;
-      for (int w = 0; w < WAVES; ++w) {
-        const float2 q = red[w][c];
-        const float mn = fmaxf(M, q.x);
-        Z = Z * __expf(M - mn) + q.y * __expf(q.x - mn);
-        M = mn;
-      }
+      for (int w = 0; w < WAVES; ++w) lse_merge(M, Z, red[w][c]);
       part[(size_t)blockIdx.x * nc + c] = make_float2(M, Z);
     }
   }
@@ -107,12 +137,7 @@ __device__ __forceinline__ void fold_colstats(const float2* __restrict__ part, i
 #pragma unroll
     for (int k = 0; k < SLOTS; ++k) {
       const int c = lane + 64 * k;
-      if (c < nc) {
-        const float2 q = p[c];
-        const float mn = fmaxf(M[k], q.x);
-        Z[k] = Z[k] * __expf(M[k] - mn) + q.y * __expf(q.x - mn);
-        M[k] = mn;
-      }
+      if (c < nc) lse_merge(M[k], Z[k], p[c]);
     }
   }
 }
@@ -134,18 +159,9 @@ __global__ __launch_bounds__(64 * SLOTS) void mil_fold(const float2* __restrict_
 #pragma unroll
     for (int u = 0; u < 16; ++u) q[u] = p[(size_t)(s + u) * nc];
 #pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const float mn = fmaxf(M, q[u].x);
-      Z = Z * __expf(M - mn) + q[u].y * __expf(q[u].x - mn);
-      M = mn;
-    }
+    for (int u = 0; u < 16; ++u) lse_merge(M, Z, q[u]);
   }
-  for (; s < slabs_per_bag; ++s) {
-    const float2 q = p[(size_t)s * nc];
-    const float mn = fmaxf(M, q.x);
-    Z = Z * __expf(M - mn) + q.y * __expf(q.x - mn);
-    M = mn;
-  }
+  for (; s < slabs_per_bag; ++s) lse_merge(M, Z, p[(size_t)s * nc]);
   folded[(size_t)bag * nc + c] = make_float2(M, Z);
 }
 
@@ -153,23 +169,7 @@ __global__ __launch_bounds__(64 * SLOTS) void mil_fold(const float2* __restrict_
 __device__ __forceinline__ void mil_row(const float* __restrict__ Crow, const float* __restrict__ Drow,
                                         int nc, int lane, const float (&M)[SLOTS],
                                         const float (&Z)[SLOTS], float (&a)[SLOTS], float (&b)[SLOTS]) {
-  float cv[SLOTS], mx = -FLT_MAX;
-#pragma unroll
-  for (int k = 0; k < SLOTS; ++k) {
-    const int c = lane + 64 * k;
-    cv[k] = c < nc ? Crow[c] : -FLT_MAX;
-    mx = fmaxf(mx, cv[k]);
-  }
-  mx = wave_max(mx);
-  float sm = 0.f;
-#pragma unroll
-  for (int k = 0; k < SLOTS; ++k) {
-    const int c = lane + 64 * k;
-    a[k] = c < nc ? __expf(cv[k] - mx) : 0.f;
-    sm += a[k];
-  }
-  sm = wave_sum(sm);
-  const float inv = 1.f / sm;
+  const float inv = 1.f / row_softmax(Crow, nc, lane, a).sm;
 #pragma unroll
   for (int k = 0; k < SLOTS; ++k) {
     const int c = lane + 64 * k;
@@ -252,13 +252,8 @@ __global__ __launch_bounds__(256) void mil_finish(const float* __restrict__ psum
     const bool pass = sum >= kTiny && sum <= 1.f - kTiny;
     gp[idx] = pass ? (p - y) / (p * (1.f - p)) * norm : 0.f;
   }
-  red[threadIdx.x] = part;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *loss = red[0] * norm;
+  part = tree_sum_256(part, red);
+  if (threadIdx.x == 0) *loss = part * norm;
 }
 
 // ---- MIL backward: dC, dD (Appendix B) ------------------------------------------------------------
@@ -338,19 +333,9 @@ __global__ __launch_bounds__(256) void oicr_forward(const float* __restrict__ Zl
     const float w = y == -1 ? 0.f : weights[r];
     if (w > 1e-12f) nv += 1.f;
     const float* row = Zl + (size_t)r * ldz;
-    float v[SLOTS], mx = -FLT_MAX;
-#pragma unroll
-    for (int k = 0; k < SLOTS; ++k) {
-      const int c = lane + 64 * k;
-      v[k] = c < ncls ? row[c] : -FLT_MAX;
-      mx = fmaxf(mx, v[k]);
-    }
-    mx = wave_max(mx);
-    float sm = 0.f;
-#pragma unroll
-    for (int k = 0; k < SLOTS; ++k) sm += (lane + 64 * k) < ncls ? __expf(v[k] - mx) : 0.f;
-    sm = wave_sum(sm);
-    if (y >= 0) ce += w * (logf(sm) + mx - row[y]);            // same value in every lane
+    float v[SLOTS];
+    const RowStats st = row_softmax(row, ncls, lane, v);
+    if (y >= 0) ce += w * (logf(st.sm) + st.mx - row[y]);      // same value in every lane
     if (y >= 0 && y < ncls - 1 && Dl) {
       float t[4];
       box_target(prop + 4 * (size_t)r, gt + 4 * (size_t)r, t);
@@ -407,19 +392,8 @@ __global__ __launch_bounds__(256) void oicr_backward(const float* __restrict__ Z
     const int y = labels[r];
     const float w = y == -1 ? 0.f : weights[r];
     const float* row = Zl + (size_t)r * ldz;
-    float v[SLOTS], mx = -FLT_MAX;
-#pragma unroll
-    for (int k = 0; k < SLOTS; ++k) {
-      const int c = lane + 64 * k;
-      v[k] = c < ncls ? row[c] : -FLT_MAX;
-      mx = fmaxf(mx, v[k]);
-    }
-    mx = wave_max(mx);
-    float sm = 0.f;
-#pragma unroll
-    for (int k = 0; k < SLOTS; ++k) { v[k] = (lane + 64 * k) < ncls ? __expf(v[k] - mx) : 0.f; sm += v[k]; }
-    sm = wave_sum(sm);
-    const float inv = 1.f / sm;
+    float v[SLOTS];
+    const float inv = 1.f / row_softmax(row, ncls, lane, v).sm;
 #pragma unroll
     for (int k = 0; k < SLOTS; ++k) {
       const int c = lane + 64 * k;
@@ -452,16 +426,17 @@ inline void mil_plan(int max_bag_rows, int nbags, int* slabs_per_bag, int* rows_
   if (*slabs_per_bag < 1) *slabs_per_bag = 1;
 }
 
-struct MilWs { float2* part; float* psum_part; float* psum; float* gp; float2* folded; };
-inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+// in 16-byte pieces, 16 bytes of slack behind the last (a null ws: measure only, `bytes` is the answer)
+struct MilWs { float2* part; float* psum_part; float* psum; float* gp; float2* folded; size_t bytes; };
 inline MilWs mil_carve(void* ws, int nbags, int spb, int nc) {
-  char* p = (char*)ws;
+  Arena a{static_cast<char*>(ws), false, 16};
   MilWs k;
-  k.part = (float2*)p; p += align16((size_t)nbags * spb * nc * sizeof(float2));
-  k.psum_part = (float*)p; p += align16((size_t)nbags * spb * nc * sizeof(float));
-  k.psum = (float*)p; p += align16((size_t)nbags * nc * sizeof(float));
-  k.gp = (float*)p; p += align16((size_t)nbags * nc * sizeof(float));
-  k.folded = (float2*)p;
+  k.part = a.take<float2>((size_t)nbags * spb * nc);
+  k.psum_part = a.take<float>((size_t)nbags * spb * nc);
+  k.psum = a.take<float>((size_t)nbags * nc);
+  k.gp = a.take<float>((size_t)nbags * nc);
+  k.folded = a.take<float2>((size_t)nbags * nc);
+  k.bytes = a.off + 16;
   return k;
 }
 
@@ -479,13 +454,8 @@ __global__ __launch_bounds__(256) void mask_bce_fwd(const float* __restrict__ z,
     const float t = target[i] ? 1.f : 0.f;
     s += fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+  s = tree_sum_256(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void mask_bce_finish(const float* __restrict__ part, int nblocks, long npix,
@@ -493,13 +463,8 @@ __global__ __launch_bounds__(256) void mask_bce_finish(const float* __restrict__
   __shared__ double red[256];
   double s = 0.0;
   for (int b = threadIdx.x; b < nblocks; b += 256) s += part[b];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)(red[0] / (double)npix);
+  s = tree_sum_256(s, red);
+  if (threadIdx.x == 0) out[0] = (float)(s / (double)npix);
 }
 
 // dz[i, c] = (sigmoid(z) - t) * upstream / npix on the class channel, zero elsewhere (dense, as the predictor's
@@ -555,8 +520,7 @@ size_t jtsm_mil_workspace_bytes(int nbags, int max_bag_rows, int nc) {
   if (nbags <= 0 || nc <= 0 || max_bag_rows < 0) return 16;
   int spb, rps;
   mil_plan(max_bag_rows, nbags, &spb, &rps);
-  return align16((size_t)nbags * spb * nc * sizeof(float2)) + align16((size_t)nbags * spb * nc * sizeof(float)) +
-         2 * align16((size_t)nbags * nc * sizeof(float)) + align16((size_t)nbags * nc * sizeof(float2)) + 16;
+  return mil_carve(nullptr, nbags, spb, nc).bytes;
 }
 
 int jtsm_mil_forward_f32(const float* cls_logits, const float* det_logits, int ld, int nc,
