@@ -37,11 +37,6 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
-// The fp16 operand-plane word of v * 2^shift (DESIGN.md "Operand planes").  ldexp, not a multiply: a multiply in front
-// of the conversion is folded into v_fma_mix{lo,hi}_f16 (v * s + 0) on SOME lanes of an unrolled group, and -0 + 0 is
-// +0 — the plane of a stored -0 then depended on the element's position (tests/test_hip_planes.py).
-__device__ __forceinline__ _Float16 f16_plane(float v, int shift) { return (_Float16)__builtin_ldexpf(v, shift); }
-
 // float -> unsigned whose order is the float order, and back.  The raw map: -0 below +0, a NaN by its bits (above +inf
 // with the sign clear, below -inf with it set).  Who wants what:
 //   voc_eval.hip    raw, and the inverse: only the largest and smallest score come back out, for evaluate()'s range

@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "planes.h"
 
 namespace jtsm {
 namespace {
@@ -116,10 +117,10 @@ __device__ __forceinline__ float pow2i(int k) { return __int_as_float((127 + k) 
 
 // Epilogue::residual_h: four / one element(s) of the fp16 residual plane as floats
 __device__ __forceinline__ float4 res_h4(const Epilogue& e, size_t o) {
-  typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-  const f16x4_t h = *reinterpret_cast<const f16x4_t*>(e.residual_h + o);
+  float h[4];
+  get_planes<4>(e.residual_h, (const unsigned short*)nullptr, o, h);
   const float a = pow2i(-e.res_shift);
-  return make_float4((float)h[0] * a, (float)h[1] * a, (float)h[2] * a, (float)h[3] * a);
+  return make_float4(h[0] * a, h[1] * a, h[2] * a, h[3] * a);
 }
 __device__ __forceinline__ float res_h1(const Epilogue& e, size_t o) {
   return (float)reinterpret_cast<const _Float16*>(e.residual_h)[o] * pow2i(-e.res_shift);
@@ -299,32 +300,10 @@ __device__ __forceinline__ void store_tile(const Params& p, f32x16 (&acc)[TM][TN
   }
 }
 
-// hi/lo bf16 planes of four finished outputs (what jtsm_split_bf16_f32 would produce from them); with lo == null,
-// one fp16 plane of v * 2^shift (what jtsm_split_f16_f32 would produce).  Pinned word for word against the fp32 result
-// of the same launch by tests/test_hip_planes.py (test_contraction_epilogue_planes).
-__device__ __forceinline__ void emit_planes4(unsigned short* hi, unsigned short* lo, size_t o, const float4& v,
-                                             int shift = 0) {
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-  const float x[4] = {v.x, v.y, v.z, v.w};
-  if (!lo) {
-    typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-    f16x4_t h;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) h[e] = f16_plane(x[e], shift);
-    *reinterpret_cast<f16x4_t*>(hi + o) = h;
-    return;
-  }
-  bf16x4_t h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const __bf16 hh = (__bf16)x[e];
-    h[e] = hh;
-    l[e] = (__bf16)(x[e] - (float)hh);
-  }
-  *reinterpret_cast<bf16x4_t*>(hi + o) = h;
-  *reinterpret_cast<bf16x4_t*>(lo + o) = l;
-}
-
+// (Planes of four finished outputs, Params::out_hi / out_lo: put_planes, planes.h — what jtsm_split_bf16_f32 /
+// jtsm_split_f16_f32 would produce from them, pinned word for word against the fp32 result of the same launch by
+// tests/test_hip_planes.py, test_contraction_epilogue_planes.)
+//
 // The same epilogue with 16-byte global accesses: the workgroup's BM x BN accumulator tile is parked in LDS
 // (free once the K loop is over; BM*BN*4 = 64 KiB), then every thread streams float4 pieces of whole output
 // rows — 512 contiguous bytes per 32 lanes — through the scale / bias / residual / ReLU / gate chain.
@@ -537,7 +516,7 @@ __device__ __forceinline__ void store_tile_wide(const Params& p, f32x16 (&acc)[T
     if (p.mask_plane) mp = *reinterpret_cast<const short4*>(p.mask_plane + o);
     v = chain(v, e.scale != nullptr, sc, bi, rr, mk, mp);
     if (p.C) *reinterpret_cast<float4*>(p.C + o) = v;
-    if (p.out_hi) emit_planes4(p.out_hi, p.out_lo, o, v, p.out_shift);
+    if (p.out_hi) put_planes(v, p.out_hi, p.out_lo, o, p.out_shift);
   };
   // ---- the streaming loop.  A thread's pieces all sit in the SAME four columns (NT is a multiple of the pieces per
   // row), so the per-column operands are fetched once; the per-piece operands (residual, gate) of U pieces travel
@@ -621,7 +600,7 @@ __device__ __forceinline__ void store_tile_wide(const Params& p, f32x16 (&acc)[T
         int nb;
         const size_t o = locate(m, n, nb);
         if (p.C) *reinterpret_cast<float4*>(p.C + o) = v;
-        if (p.out_hi) emit_planes4(p.out_hi, p.out_lo, o, v, p.out_shift);
+        if (p.out_hi) put_planes(v, p.out_hi, p.out_lo, o, p.out_shift);
         csum.x += v.x; csum.y += v.y; csum.z += v.z; csum.w += v.w;
       }
       continue;
@@ -662,7 +641,7 @@ __device__ __forceinline__ void store_tile_wide(const Params& p, f32x16 (&acc)[T
         int nb;
         const size_t o = locate(om[u], n, nb);
         if (p.C) *reinterpret_cast<float4*>(p.C + o) = out[u];
-        if (p.out_hi) emit_planes4(p.out_hi, p.out_lo, o, out[u], p.out_shift);
+        if (p.out_hi) put_planes(out[u], p.out_hi, p.out_lo, o, p.out_shift);
         csum.x += out[u].x; csum.y += out[u].y; csum.z += out[u].z; csum.w += out[u].w;
       }
     }
@@ -1235,7 +1214,7 @@ __global__ __launch_bounds__(256) void splitk_finish_shared(const Params p, int 
     if (VEC == 4) {
       const float4 out = make_float4(v[0], v[1 % VEC], v[2 % VEC], v[3 % VEC]);
       if (p.C) *reinterpret_cast<float4*>(p.C + o) = out;
-      if (p.out_hi) emit_planes4(p.out_hi, p.out_lo, o, out, p.out_shift);
+      if (p.out_hi) put_planes(out, p.out_hi, p.out_lo, o, p.out_shift);
     } else {
       p.C[o] = v[0];
     }
@@ -1382,7 +1361,7 @@ __device__ __forceinline__ void splitk_finish_body(const Params& p, int splits, 
     if (VEC == 4) {
       const float4 out = make_float4(v[0], v[1 % VEC], v[2 % VEC], v[3 % VEC]);
       if (p.C) *reinterpret_cast<float4*>(p.C + o) = out;
-      if (p.out_hi) emit_planes4(p.out_hi, p.out_lo, o, out, p.out_shift);
+      if (p.out_hi) put_planes(out, p.out_hi, p.out_lo, o, p.out_shift);
     } else {
       p.C[o] = v[0];
     }

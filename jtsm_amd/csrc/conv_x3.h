@@ -16,14 +16,11 @@
 // the ds_read_b128, which is then conflict-free for the b128 lane groups of MI355X_MICROARCH.md §LDS.
 // A 32x32x16 step takes k = 8h .. 8h+7 from half-wave h, i.e. chunk 2s+h in step s: no k permutation.
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int XBK = 32;   // k per stage (and the unit of split-K bookkeeping)
 
 // NP = planes per operand.  2: split-bf16 (hi + lo, three bf16 products per fp32 product).  1: ONE IEEE fp16 plane
 // (BASELINE configs[4]: fp16 operands, fp32 accumulate) — a single v_mfma_f32_32x32x16_f16 per sixteen k, half the
 // operand bytes; the kernels are otherwise the same, X3Planes' lo pointers are unused.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 template <int NP>
 __device__ __forceinline__ void x3_mma(f32x16& acc, const bf16x8& ah, const bf16x8& al, const bf16x8& bh,
                                        const bf16x8& bl) {
@@ -637,8 +634,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_x3_halo_kernel(const Pa
 // swizzle again), and the MFMA operands (8 consecutive k of one channel per lane) come out of two
 // ds_read_b64_tr_b16 each — the hardware transpose, conflict-free on this image (bank rule of
 // cdna_hip_programming.md §2: a 32-lane half touches 16 distinct chunks x 2 halves of a chunk).
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ bf16x8 lds_tr8(const char* lo_rows, const char* hi_rows) {
   const bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)lo_rows);
   const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)hi_rows);
@@ -1069,31 +1064,36 @@ __global__ __launch_bounds__(256, 2) void igemm_x3_wgrad_halo_group_kernel(const
 }
 
 // ---- the splitting pre-passes ---------------------------------------------------------------------
-__device__ __forceinline__ void split1(float v, __bf16& h, __bf16& l) {
-  h = (__bf16)v;
-  l = (__bf16)(v - (float)h);
+// (the split itself, the fp16 word and the plane writer: planes.h)
+// Eight consecutive floats at src + 8 i, as the writer takes them.
+struct Float8 { float v[8]; };
+__device__ __forceinline__ Float8 ldg8(const float* __restrict__ src, long i) {
+  const float4 a = reinterpret_cast<const float4*>(src)[2 * i], b = reinterpret_cast<const float4*>(src)[2 * i + 1];
+  return {{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
+}
+// The bf16 pair of eight values into PAIRED planes (x3_paired_index): element k of row `row`, lo 32 words after hi.
+__device__ __forceinline__ void put_paired8(const float (&v)[8], __bf16* dst, long row, long k, long K) {
+  bf16x8 h, l;
+  split_planes<8>(v, h, l);
+  __bf16* o = dst + x3_paired_index(row, k, K);
+  *reinterpret_cast<bf16x8*>(o) = h;
+  *reinterpret_cast<bf16x8*>(o + 32) = l;
+}
+// One WEIGHT word (shift 0) of a plane pair, or (lo == nullptr) of the fp16 plane in `hi`.
+__device__ __forceinline__ void put_plane1(float v, __bf16* hi, __bf16* lo, size_t o) {
+  if (lo) split_bf16(v, hi[o], lo[o]);
+  else reinterpret_cast<_Float16*>(hi)[o] = f16_plane(v, 0);
 }
 
 // hi[i], lo[i] <- src[i]; eight elements per thread (n8 = n / 8), scalar tail by the last threads.
 __global__ __launch_bounds__(256) void split_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ hi,
                                                          __bf16* __restrict__ lo, long n) {
   const long n8 = n >> 3;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-    const float4 a = reinterpret_cast<const float4*>(src)[2 * i], b = reinterpret_cast<const float4*>(src)[2 * i + 1];
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    bf16x8 h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      __bf16 hh, ll;
-      split1(v[e], hh, ll);
-      h[e] = hh; l[e] = ll;
-    }
-    reinterpret_cast<bf16x8*>(hi)[i] = h;
-    reinterpret_cast<bf16x8*>(lo)[i] = l;
-  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x)
+    put_pair<8>(ldg8(src, i).v, hi, lo, i << 3);
   if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
     const long i = (n8 << 3) + threadIdx.x;
-    split1(src[i], hi[i], lo[i]);
+    split_bf16(src[i], hi[i], lo[i]);
   }
 }
 
@@ -1102,19 +1102,8 @@ __global__ __launch_bounds__(256) void split_bf16_paired_kernel(const float* __r
                                                                 long n, int K) {
   const long n8 = n >> 3;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-    const float4 a = reinterpret_cast<const float4*>(src)[2 * i], b = reinterpret_cast<const float4*>(src)[2 * i + 1];
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    bf16x8 h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      __bf16 hh, ll;
-      split1(v[e], hh, ll);
-      h[e] = hh; l[e] = ll;
-    }
     const long row = (i << 3) / K, k = (i << 3) - row * K;
-    __bf16* o = dst + x3_paired_index(row, k, K);
-    *reinterpret_cast<bf16x8*>(o) = h;
-    *reinterpret_cast<bf16x8*>(o + 32) = l;
+    put_paired8(ldg8(src, i).v, dst, row, k, K);
   }
 }
 
@@ -1123,14 +1112,8 @@ __global__ __launch_bounds__(256) void split_bf16_paired_kernel(const float* __r
 __global__ __launch_bounds__(256) void split_f16_kernel(const float* __restrict__ src, _Float16* __restrict__ h, long n,
                                                         int shift) {
   const long n8 = n >> 3;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-    const float4 a = reinterpret_cast<const float4*>(src)[2 * i], b = reinterpret_cast<const float4*>(src)[2 * i + 1];
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    f16x8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = f16_plane(v[e], shift);
-    reinterpret_cast<f16x8*>(h)[i] = o;
-  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x)
+    *reinterpret_cast<f16x8*>(h + (i << 3)) = f16_planes<8>(ldg8(src, i).v, shift);
   if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
     const long i = (n8 << 3) + threadIdx.x;
     h[i] = f16_plane(src[i], shift);
@@ -1158,8 +1141,7 @@ __global__ __launch_bounds__(256) void split_bf16_transposed_kernel(const float*
     if (ci < Cin && co < Cout) {
       const size_t o = x3_paired(hi, lo, 2) ? x3_paired_index(ci, (size_t)tap * Cout + co, (size_t)taps * Cout)
                                             : ((size_t)ci * taps + tap) * Cout + co;
-      if (lo) split1(tile[tx][r], hi[o], lo[o]);
-      else reinterpret_cast<_Float16*>(hi)[o] = (_Float16)tile[tx][r];
+      put_plane1(tile[tx][r], hi, lo, o);
     }
   }
 }
@@ -1193,36 +1175,15 @@ __global__ __launch_bounds__(256) void split_bf16_multi_kernel(const SplitEntry*
   const SplitEntry t = tab[e];
   const long base = ((long)blockIdx.x - t.first_block) * 2048 + threadIdx.x * 8;
   if (base + 8 <= t.n) {
-    const float4 a = *reinterpret_cast<const float4*>(t.src + base), b = *reinterpret_cast<const float4*>(t.src + base + 4);
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    if (!t.lo) {   // fp16 form: one plane
-      f16x8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (_Float16)v[k];
-      *reinterpret_cast<f16x8*>(t.hi + base) = o;
-      return;
-    }
-    bf16x8 h, l;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      __bf16 hh, ll;
-      split1(v[k], hh, ll);
-      h[k] = hh; l[k] = ll;
-    }
+    const Float8 x = ldg8(t.src + base, 0);
     if (x3_paired(t.hi, t.lo, 2)) {   // paired planes: the record's `cin` word is the row length K (K % 32 == 0)
       const long row = base / t.cin, k = base - row * t.cin;
-      __bf16* o = t.hi + x3_paired_index(row, k, t.cin);
-      *reinterpret_cast<bf16x8*>(o) = h;
-      *reinterpret_cast<bf16x8*>(o + 32) = l;
+      put_paired8(x.v, t.hi, row, k, t.cin);
       return;
     }
-    *reinterpret_cast<bf16x8*>(t.hi + base) = h;
-    *reinterpret_cast<bf16x8*>(t.lo + base) = l;
+    put_planes<8>(x.v, t.hi, t.lo, base, 0);   // (weights: shift 0)
   } else {
-    for (long i = base; i < t.n; ++i) {
-      if (t.lo) split1(t.src[i], t.hi[i], t.lo[i]);
-      else reinterpret_cast<_Float16*>(t.hi)[i] = (_Float16)t.src[i];
-    }
+    for (long i = base; i < t.n; ++i) put_plane1(t.src[i], t.hi, t.lo, i);
   }
 }
 
@@ -1251,8 +1212,7 @@ __global__ __launch_bounds__(256) void split_bf16_transposed_multi_kernel(const 
     if (ci < Cin && co < Cout) {
       const size_t o = x3_paired(t.hi, t.lo, 2) ? x3_paired_index(ci, (size_t)tap * Cout + co, (size_t)taps * Cout)
                                                 : ((size_t)ci * taps + tap) * Cout + co;
-      if (t.lo) split1(tile[tx][rr], t.hi[o], t.lo[o]);
-      else reinterpret_cast<_Float16*>(t.hi)[o] = (_Float16)tile[tx][rr];
+      put_plane1(tile[tx][rr], t.hi, t.lo, o);
     }
   }
 }

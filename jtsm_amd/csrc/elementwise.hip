@@ -2,6 +2,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "planes.h"
 
 namespace jtsm {
 namespace {
@@ -21,46 +22,9 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float4* __restrict_
     g[i] = r;
   }
 }
-// the same, also writing the bf16 hi / lo planes of g (eight elements per thread)
-typedef __bf16 ew_bf16x8 __attribute__((ext_vector_type(8)));
-__global__ __launch_bounds__(256) void relu_bwd_split_kernel(const float4* __restrict__ dy, const float4* __restrict__ y,
-                                                             float4* __restrict__ g, ew_bf16x8* __restrict__ hi,
-                                                             ew_bf16x8* __restrict__ lo, long n8) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-    const float4 a0 = dy[2 * i], a1 = dy[2 * i + 1], b0 = y[2 * i], b1 = y[2 * i + 1];
-    const float v[8] = {b0.x > 0.f ? a0.x : 0.f, b0.y > 0.f ? a0.y : 0.f, b0.z > 0.f ? a0.z : 0.f, b0.w > 0.f ? a0.w : 0.f,
-                        b1.x > 0.f ? a1.x : 0.f, b1.y > 0.f ? a1.y : 0.f, b1.z > 0.f ? a1.z : 0.f, b1.w > 0.f ? a1.w : 0.f};
-    g[2 * i] = make_float4(v[0], v[1], v[2], v[3]);
-    g[2 * i + 1] = make_float4(v[4], v[5], v[6], v[7]);
-    ew_bf16x8 h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 hh = (__bf16)v[e];
-      h[e] = hh;
-      l[e] = (__bf16)(v[e] - (float)hh);
-    }
-    hi[i] = h;
-    lo[i] = l;
-  }
-}
-// fp16 form: ONE plane of g * 2^shift
-typedef _Float16 ew_f16x8 __attribute__((ext_vector_type(8)));
-__global__ __launch_bounds__(256) void relu_bwd_split_f16_kernel(const float4* __restrict__ dy, const float4* __restrict__ y,
-                                                                 float4* __restrict__ g, ew_f16x8* __restrict__ h, long n8,
-                                                                 int shift) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-    const float4 a0 = dy[2 * i], a1 = dy[2 * i + 1], b0 = y[2 * i], b1 = y[2 * i + 1];
-    const float v[8] = {b0.x > 0.f ? a0.x : 0.f, b0.y > 0.f ? a0.y : 0.f, b0.z > 0.f ? a0.z : 0.f, b0.w > 0.f ? a0.w : 0.f,
-                        b1.x > 0.f ? a1.x : 0.f, b1.y > 0.f ? a1.y : 0.f, b1.z > 0.f ? a1.z : 0.f, b1.w > 0.f ? a1.w : 0.f};
-    g[2 * i] = make_float4(v[0], v[1], v[2], v[3]);
-    g[2 * i + 1] = make_float4(v[4], v[5], v[6], v[7]);
-    ew_f16x8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = f16_plane(v[e], shift);
-    h[i] = o;
-  }
-}
-// ---- one streaming pass that ends in operand planes (layers/conv.py), three uses:
+// ---- one streaming pass that ends in operand planes (layers/conv.py), eight elements per thread, four uses:
+//   kGate        v = y > 0 ? dy : 0                  ReLU backward (y is the layer's OUTPUT) with the planes of g; g = v
+//                                                    stored.  dy passes through untouched: no multiply by 1
 //   kGateScaled  v = y > 0 ? dy * scale : 0          the backward of ReLU followed by dropout (y = the dropout's output:
 //                                                    positive exactly where the unit was kept AND active), g = v stored
 //   kRowScale    v = x[r][c] * row_scale[r]          planes of a row-rescaled matrix (the per-roi factor in front of the
@@ -69,7 +33,7 @@ __global__ __launch_bounds__(256) void relu_bwd_split_f16_kernel(const float4* _
 //                                                    counter-based hash of (seed, element index): nothing to remember,
 //                                                    the backward reads the mask off y (kGateScaled)
 // Planes: bf16 hi + lo, or (lo == null) one fp16 plane of v * 2^shift; hi == null: no planes.
-enum PassMode { kGateScaled = 0, kRowScale = 1, kDropout = 2 };
+enum PassMode { kGateScaled = 0, kRowScale = 1, kDropout = 2, kGate = 3 };
 struct PassArgs {
   const float* a;           // dy | x | x
   const float* b;           // y  | - | -
@@ -99,11 +63,11 @@ __global__ __launch_bounds__(256) void planes_pass_kernel(const PassArgs q) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < q.n8; i += (long)gridDim.x * blockDim.x) {
     const float4 a0 = a[2 * i], a1 = a[2 * i + 1];
     float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-    if (MODE == kGateScaled) {
+    if (MODE == kGateScaled || MODE == kGate) {
       const float4 b0 = b[2 * i], b1 = b[2 * i + 1];
       const float y[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = y[e] > 0.f ? v[e] * q.scale : 0.f;
+      for (int e = 0; e < 8; ++e) v[e] = y[e] > 0.f ? (MODE == kGate ? v[e] : v[e] * q.scale) : 0.f;
     } else if (MODE == kRowScale) {
       const float rs = q.row_scale[(i * 8) / q.cols];
 #pragma unroll
@@ -117,23 +81,7 @@ __global__ __launch_bounds__(256) void planes_pass_kernel(const PassArgs q) {
       out[2 * i] = make_float4(v[0], v[1], v[2], v[3]);
       out[2 * i + 1] = make_float4(v[4], v[5], v[6], v[7]);
     }
-    if (!q.hi) continue;
-    if (q.lo) {
-      ew_bf16x8 h, l;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const __bf16 hh = (__bf16)v[e];
-        h[e] = hh;
-        l[e] = (__bf16)(v[e] - (float)hh);
-      }
-      reinterpret_cast<ew_bf16x8*>(q.hi)[i] = h;
-      reinterpret_cast<ew_bf16x8*>(q.lo)[i] = l;
-    } else {
-      ew_f16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = f16_plane(v[e], q.shift);
-      reinterpret_cast<ew_f16x8*>(q.hi)[i] = o;
-    }
+    if (q.hi) put_planes<8>(v, q.hi, q.lo, i * 8, q.shift);
   }
 }
 __global__ __launch_bounds__(256) void relu_bwd_tail(const float* __restrict__ dy,
@@ -196,8 +144,6 @@ __global__ __launch_bounds__(256) void channel_sum4_kernel(const float4* __restr
 }
 // The same from operand PLANES (layers/conv.py): value = hi + lo (split-bf16) or the fp16 plane times 2^-shift.  A lane
 // owns eight channels (16 bytes per plane), slabs and fold as above.  For gradients a chain keeps as planes only.
-typedef __bf16 ew_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ew_h8 __attribute__((ext_vector_type(8)));
 // Up to kCsumMulti gradients of the same width in ONE launch (blockIdx.z = which): the bias gradients of a chain's
 // layers (the mask tower) are summed together when the chain's backward is over, one launch + one fold instead of one
 // pair per layer.
@@ -231,16 +177,10 @@ __global__ __launch_bounds__(256) void channel_sum_planes_kernel(const CsumPlane
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
   auto add_row = [&](long r) {
-    const size_t o = ((size_t)r * C8 + c8) * 8;
-    if (lo) {
-      const ew_bf16x8 a = *reinterpret_cast<const ew_bf16x8*>(hi + o), b = *reinterpret_cast<const ew_bf16x8*>(lo + o);
+    float v[8];
+    get_planes<8>(hi, lo, ((size_t)r * C8 + c8) * 8, v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += (float)a[j] + (float)b[j];
-    } else {
-      const ew_h8 a = *reinterpret_cast<const ew_h8*>(hi + o);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += (float)a[j];
-    }
+    for (int j = 0; j < 8; ++j) acc[j] += v[j];
   };
   if (rg < rpi && c8 < C8) {
     long r = r0 + rg;
@@ -283,12 +223,8 @@ __global__ __launch_bounds__(256) void channel_sum_slab_kernel(const float* __re
 }
 // out[c] = sum_s part[s][c], slabs in a fixed order: a workgroup folds 16 channels, 16 threads per channel each
 // taking every 16th slab, then the 16 partial sums are added in order.
-__global__ __launch_bounds__(256) void channel_sum_fold_multi_kernel(const CsumPlanes q, const float* __restrict__ part_all,
-                                                                     int max_slab, int C) {
+__device__ __forceinline__ void fold_slabs(const float* __restrict__ part, float* __restrict__ out, int C, int slabs) {
   __shared__ float red[16][17];
-  const int which = blockIdx.y, slabs = q.nslab[which];
-  const float* __restrict__ part = part_all + (size_t)which * max_slab * C;
-  float* __restrict__ out = q.out[which];
   const int cl = threadIdx.x & 15, j = threadIdx.x >> 4;
   const int c = blockIdx.x * 16 + cl;
   float a = 0.f;
@@ -305,20 +241,13 @@ __global__ __launch_bounds__(256) void channel_sum_fold_multi_kernel(const CsumP
 }
 __global__ __launch_bounds__(256) void channel_sum_fold_kernel(const float* __restrict__ part, float* __restrict__ out,
                                                                int C, int slabs) {
-  __shared__ float red[16][17];
-  const int cl = threadIdx.x & 15, j = threadIdx.x >> 4;
-  const int c = blockIdx.x * 16 + cl;
-  float a = 0.f;
-  if (c < C)
-    for (int s = j; s < slabs; s += 16) a += part[(size_t)s * C + c];
-  red[j][cl] = a;
-  __syncthreads();
-  if (j == 0 && c < C) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += red[k][cl];
-    out[c] = t;
-  }
+  fold_slabs(part, out, C, slabs);
+}
+// blockIdx.y = which gradient of a channel_sum_planes_kernel launch
+__global__ __launch_bounds__(256) void channel_sum_fold_multi_kernel(const CsumPlanes q, const float* __restrict__ part_all,
+                                                                     int max_slab, int C) {
+  const int which = blockIdx.y;
+  fold_slabs(part_all + (size_t)which * max_slab * C, q.out[which], C, q.nslab[which]);
 }
 
 // ---- NHWC spatial helpers (C % 4 == 0: one float4 = 4 channels of one pixel) ---------------------
@@ -382,23 +311,8 @@ __global__ __launch_bounds__(256) void maxpool3s2_bwd(const float* __restrict__ 
   }
 }
 
-// out = lateral + nearest_upsample_x2(top)      (FPN top-down path, fpn.py:133-136)
-typedef __bf16 ew_bf16x4 __attribute__((ext_vector_type(4)));
-// bf16 hi / lo planes of four values (what jtsm_split_bf16_f32 makes of them: pinned word for word by
-// tests/test_hip_planes.py, upsample2_add / sum_tensors), for a bf16x3 consumer
-__device__ __forceinline__ void ew_planes4(unsigned short* hi, unsigned short* lo, long i4, const float4& v) {
-  const float x[4] = {v.x, v.y, v.z, v.w};
-  ew_bf16x4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const __bf16 hh = (__bf16)x[e];
-    h[e] = hh;
-    l[e] = (__bf16)(x[e] - (float)hh);
-  }
-  reinterpret_cast<ew_bf16x4*>(hi)[i4] = h;
-  reinterpret_cast<ew_bf16x4*>(lo)[i4] = l;
-}
-
+// out = lateral + nearest_upsample_x2(top)      (FPN top-down path, fpn.py:133-136), optional bf16 planes of it for a
+// bf16x3 consumer (put_pair, planes.h: both planes or neither)
 __global__ __launch_bounds__(256) void upsample2_add_fwd(const float4* __restrict__ top,
                                                          const float4* __restrict__ lat,
                                                          float4* __restrict__ out, unsigned short* __restrict__ out_hi,
@@ -414,7 +328,7 @@ __global__ __launch_bounds__(256) void upsample2_add_fwd(const float4* __restric
     const int n = (int)(t / H);
     const float4 v = f4add(lat[i], top[((long)(n * Ht + h / 2) * Wt + w / 2) * C4 + c]);
     out[i] = v;
-    if (out_hi) ew_planes4(out_hi, out_lo, i, v);
+    if (out_hi) put_pair(v, out_hi, out_lo, i * 4);
   }
 }
 // out = x0 + x1 (+ x2 (+ x3)), summed in that order (the accumulation order of `x = x + y` loops), optional bf16
@@ -427,7 +341,7 @@ __global__ __launch_bounds__(256) void sum_tensors_kernel(SumPtrs in, int n, lon
     float4 v = in.p[0][i];
     for (int k = 1; k < n; ++k) v = f4add(v, in.p[k][i]);
     out[i] = v;
-    if (hi) ew_planes4(hi, lo, i, v);
+    if (hi) put_pair(v, hi, lo, i * 4);
   }
 }
 // d_top[n,h,w] = sum of the 2x2 block of g
@@ -636,6 +550,20 @@ int jtsm_relu_backward_f32(const float* dy, const float* y, float* g, long n, vo
   return JTSM_OK;
 }
 
+static int launch_planes_pass(int mode, const PassArgs& q, const char* what, void* stream) {
+  const int blocks = (int)((q.n8 + 255) / 256 < 8192 ? (q.n8 + 255) / 256 : 8192);
+  hipStream_t st = as_stream(stream);
+  if (mode == kGate) hipLaunchKernelGGL(planes_pass_kernel<kGate>, dim3(blocks), dim3(256), 0, st, q);
+  else if (mode == kGateScaled) hipLaunchKernelGGL(planes_pass_kernel<kGateScaled>, dim3(blocks), dim3(256), 0, st, q);
+  else if (mode == kRowScale) hipLaunchKernelGGL(planes_pass_kernel<kRowScale>, dim3(blocks), dim3(256), 0, st, q);
+  else hipLaunchKernelGGL(planes_pass_kernel<kDropout>, dim3(blocks), dim3(256), 0, st, q);
+  JTSM_CHECK_LAUNCH(what);
+  return JTSM_OK;
+}
+static bool pass_aligned(const void* a, const void* b, const void* c, const void* d, const void* e) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0;
+}
+
 int jtsm_relu_backward_split_f32(const float* dy, const float* y, float* g, uint16_t* g_hi, uint16_t* g_lo, long n,
                                  void* stream) {
   JTSM_REQUIRE(n >= 0 && n % 8 == 0, "relu_backward_split: n must be a non-negative multiple of 8");
@@ -643,13 +571,9 @@ int jtsm_relu_backward_split_f32(const float* dy, const float* y, float* g, uint
   JTSM_REQUIRE(dy && y && g && g_hi && g_lo, "relu_backward_split: null pointer");
   JTSM_REQUIRE((((uintptr_t)dy | (uintptr_t)y | (uintptr_t)g | (uintptr_t)g_hi | (uintptr_t)g_lo) & 15) == 0,
                "relu_backward_split: pointers must be 16-byte aligned");
-  const long n8 = n / 8;
-  const int blocks = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
-  hipLaunchKernelGGL(relu_bwd_split_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), (const float4*)dy,
-                     (const float4*)y, (float4*)g, reinterpret_cast<ew_bf16x8*>(g_hi), reinterpret_cast<ew_bf16x8*>(g_lo),
-                     n8);
-  JTSM_CHECK_LAUNCH("relu_backward_split");
-  return JTSM_OK;
+  PassArgs q = {};
+  q.a = dy; q.b = y; q.out = g; q.hi = g_hi; q.lo = g_lo; q.n8 = n / 8;
+  return launch_planes_pass(kGate, q, "relu_backward_split", stream);
 }
 
 int jtsm_relu_backward_split_f16(const float* dy, const float* y, float* g, uint16_t* g_h, long n, int shift,
@@ -660,25 +584,9 @@ int jtsm_relu_backward_split_f16(const float* dy, const float* y, float* g, uint
   JTSM_REQUIRE(dy && y && g && g_h, "relu_backward_split_f16: null pointer");
   JTSM_REQUIRE((((uintptr_t)dy | (uintptr_t)y | (uintptr_t)g | (uintptr_t)g_h) & 15) == 0,
                "relu_backward_split_f16: pointers must be 16-byte aligned");
-  const long n8 = n / 8;
-  const int blocks = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
-  hipLaunchKernelGGL(relu_bwd_split_f16_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), (const float4*)dy,
-                     (const float4*)y, (float4*)g, reinterpret_cast<ew_f16x8*>(g_h), n8, shift);
-  JTSM_CHECK_LAUNCH("relu_backward_split_f16");
-  return JTSM_OK;
-}
-
-static int launch_planes_pass(int mode, const PassArgs& q, const char* what, void* stream) {
-  const int blocks = (int)((q.n8 + 255) / 256 < 8192 ? (q.n8 + 255) / 256 : 8192);
-  hipStream_t st = as_stream(stream);
-  if (mode == kGateScaled) hipLaunchKernelGGL(planes_pass_kernel<kGateScaled>, dim3(blocks), dim3(256), 0, st, q);
-  else if (mode == kRowScale) hipLaunchKernelGGL(planes_pass_kernel<kRowScale>, dim3(blocks), dim3(256), 0, st, q);
-  else hipLaunchKernelGGL(planes_pass_kernel<kDropout>, dim3(blocks), dim3(256), 0, st, q);
-  JTSM_CHECK_LAUNCH(what);
-  return JTSM_OK;
-}
-static bool pass_aligned(const void* a, const void* b, const void* c, const void* d, const void* e) {
-  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0;
+  PassArgs q = {};
+  q.a = dy; q.b = y; q.out = g; q.hi = g_h; q.n8 = n / 8; q.shift = shift;   // lo == null: the fp16 plane
+  return launch_planes_pass(kGate, q, "relu_backward_split_f16", stream);
 }
 
 int jtsm_relu_backward_split_scaled_f32(const float* dy, const float* y, float scale, float* g, uint16_t* g_hi,

@@ -5,6 +5,8 @@
 // ReLU is folded into the normalisation pass, and every reduction is two-stage with a fixed fold order
 // (no float atomics -> deterministic).
 #include "common.h"
+#include "planes.h"
+#include "reduce.h"
 
 namespace jtsm {
 namespace {
@@ -72,22 +74,6 @@ __global__ void gn_fold_kernel(const float2* __restrict__ part, float* __restric
   if (var < 0.0) var = 0.0;
   mean[n * G + g] = (float)mu;
   rstd[n * G + g] = (float)(1.0 / sqrt(var + (double)eps));
-}
-
-// bf16 hi / lo planes of four values (what jtsm_split_bf16_f32 would make of them: pinned word for word by
-// tests/test_hip_planes.py, upsample_bilinear2x / group_norm backward), for a bf16x3 consumer
-typedef __bf16 ss_bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void put_planes4(unsigned short* hi, unsigned short* lo, long i4, const float4& v) {
-  const float x[4] = {v.x, v.y, v.z, v.w};
-  ss_bf16x4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const __bf16 hh = (__bf16)x[e];
-    h[e] = hh;
-    l[e] = (__bf16)(x[e] - (float)hh);
-  }
-  reinterpret_cast<ss_bf16x4*>(hi)[i4] = h;
-  reinterpret_cast<ss_bf16x4*>(lo)[i4] = l;
 }
 
 // y = relu?((x - mean) * rstd * gamma + beta)
@@ -231,19 +217,21 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
     o.z = rs * (ga.z * d.z - a - h.z * b);
     o.w = rs * (ga.w * d.w - a - h.w * b);
     st4(dx + i * 4, o);
-    if (dx_hi) put_planes4(dx_hi, dx_lo, i, o);
+    if (dx_hi) put_pair(o, dx_hi, dx_lo, i * 4);
   }
 }
 
-// ---- bilinear x2 (align_corners = False): src coordinate of dst o is o/2 - 0.25 clamped at 0 -----------
-struct Lerp { int i0, i1; float l; };
-__device__ __forceinline__ Lerp lerp_of(int o, int n_src) {
-  float s = ((float)o + 0.5f) * 0.5f - 0.5f;
+// ---- bilinear xS (align_corners = False): src coordinate of dst o is (o + 0.5) / S - 0.5 clamped at 0; taps i0, i1
+// with weights l0 = 1 - l1, l1.  x2: inv_scale = 0.5, i.e. o/2 - 0.25 -----------
+struct Lerp { int i0, i1; float l0, l1; };
+__device__ __forceinline__ Lerp lerp_scale(int o, int n_src, float inv_scale) {
+  float s = ((float)o + 0.5f) * inv_scale - 0.5f;
   if (s < 0.f) s = 0.f;
   Lerp r;
   r.i0 = (int)s;
   r.i1 = r.i0 < n_src - 1 ? r.i0 + 1 : r.i0;
-  r.l = s - (float)r.i0;
+  r.l1 = s - (float)r.i0;
+  r.l0 = 1.f - r.l1;
   return r;
 }
 
@@ -284,7 +272,7 @@ __global__ __launch_bounds__(256) void up2_fwd_kernel(const float* __restrict__ 
     const int ow = (int)(t % Wo); t /= Wo;
     const int oh = (int)(t % Ho);
     const int n = (int)(t / Ho);
-    const Lerp a = lerp_of(oh, H), b = lerp_of(ow, W);
+    const Lerp a = lerp_scale(oh, H, 0.5f), b = lerp_scale(ow, W, 0.5f);
     const float* base = x + (size_t)n * H * W * C4 * 4;
     float4 v00 = ld4(base + ((size_t)(a.i0 * W + b.i0) * C4 + c) * 4);
     float4 v01 = ld4(base + ((size_t)(a.i0 * W + b.i1) * C4 + c) * 4);
@@ -301,7 +289,7 @@ __global__ __launch_bounds__(256) void up2_fwd_kernel(const float* __restrict__ 
       v11 = make_float4(t3[0], t3[1], t3[2], t3[3]);
     }
 #endif
-    const float w00 = (1.f - a.l) * (1.f - b.l), w01 = (1.f - a.l) * b.l, w10 = a.l * (1.f - b.l), w11 = a.l * b.l;
+    const float w00 = a.l0 * b.l0, w01 = a.l0 * b.l1, w10 = a.l1 * b.l0, w11 = a.l1 * b.l1;
     float4 o;
     o.x = w00 * v00.x + w01 * v01.x + w10 * v10.x + w11 * v11.x;
     o.y = w00 * v00.y + w01 * v01.y + w10 * v10.y + w11 * v11.y;
@@ -339,7 +327,7 @@ __global__ __launch_bounds__(256) void up2_fwd_kernel(const float* __restrict__ 
 #else
     st4(y + i * 4, o);
 #endif
-    if (y_hi) put_planes4(y_hi, y_lo, i, o);
+    if (y_hi) put_pair(o, y_hi, y_lo, i * 4);
 #ifdef JTSM_DIAG_UP2
     {
       const float4 r00 = ld4_system(base + ((size_t)(a.i0 * W + b.i0) * C4 + c) * 4);
@@ -388,8 +376,8 @@ __global__ __launch_bounds__(256) void up2_fwd_kernel(const float* __restrict__ 
 
 // backward as a gather: source pixel (h,w) collects from the <= 4x4 destination pixels that sample it.
 __device__ __forceinline__ float weight_on(int o, int n_src, int i) {
-  const Lerp r = lerp_of(o, n_src);
-  return (r.i0 == i ? 1.f - r.l : 0.f) + (r.i1 == i ? r.l : 0.f);
+  const Lerp r = lerp_scale(o, n_src, 0.5f);
+  return (r.i0 == i ? r.l0 : 0.f) + (r.i1 == i ? r.l1 : 0.f);
 }
 __global__ __launch_bounds__(256) void up2_bwd_kernel(const float* __restrict__ gy, float* __restrict__ gx, int N,
                                                       int H, int W, int C4, long total4) {
@@ -425,29 +413,8 @@ __global__ __launch_bounds__(256) void up2_bwd_kernel(const float* __restrict__ 
 // (wavefront per pixel, lanes = classes, C <= 64), reduced to a log-sum-exp with wavefront shuffles, and
 // only lse (4 B per pixel) is kept for the backward, which is a GATHER over the <= (2S)^2 output pixels
 // that touch each source pixel (no atomics, deterministic).
-struct LerpS { int i0, i1; float l0, l1; };
-__device__ __forceinline__ LerpS lerp_scale(int o, int n_src, float inv_scale) {
-  float s = ((float)o + 0.5f) * inv_scale - 0.5f;
-  if (s < 0.f) s = 0.f;
-  LerpS r;
-  r.i0 = (int)s;
-  r.i1 = r.i0 < n_src - 1 ? r.i0 + 1 : r.i0;
-  r.l1 = s - (float)r.i0;
-  r.l0 = 1.f - r.l1;
-  return r;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float interp_logit(const float* __restrict__ zn, int Ws, int ldc, const LerpS& a,
-                                              const LerpS& b, int c) {
+__device__ __forceinline__ float interp_logit(const float* __restrict__ zn, int Ws, int ldc, const Lerp& a,
+                                              const Lerp& b, int c) {
   const float v00 = zn[((size_t)a.i0 * Ws + b.i0) * ldc + c], v01 = zn[((size_t)a.i0 * Ws + b.i1) * ldc + c];
   const float v10 = zn[((size_t)a.i1 * Ws + b.i0) * ldc + c], v11 = zn[((size_t)a.i1 * Ws + b.i1) * ldc + c];
   return a.l0 * (b.l0 * v00 + b.l1 * v01) + a.l1 * (b.l0 * v10 + b.l1 * v11);   // ATen's association
@@ -471,7 +438,7 @@ __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const float* __restrict_
     const int ow = (int)(p % W);
     const long q = p / W;
     const int oh = (int)(q % H), n = (int)(q / H);
-    const LerpS a = lerp_scale(oh, Hs, inv), b = lerp_scale(ow, Ws, inv);
+    const Lerp a = lerp_scale(oh, Hs, inv), b = lerp_scale(ow, Ws, inv);
     const float* zn = z + (size_t)n * Hs * Ws * ldc;
     const float4* p00 = reinterpret_cast<const float4*>(zn + ((size_t)a.i0 * Ws + b.i0) * ldc);
     const float4* p01 = reinterpret_cast<const float4*>(zn + ((size_t)a.i0 * Ws + b.i1) * ldc);
@@ -513,8 +480,8 @@ __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const float* __restrict_
       cnt += 1.f;
     }
   }
-  loss = wsum(loss);
-  cnt = wsum(cnt);
+  loss = wave_sum(loss);
+  cnt = wave_sum(cnt);
   if (lane == 0) { red[wv][0] = loss; red[wv][1] = cnt; }
   __syncthreads();
   if (threadIdx.x < 2)
@@ -570,7 +537,7 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const float* __restrict_
     const int oh0 = max(S * h - (S + 1) / 2, 0), oh1 = min(S * h + S + (S + 1) / 2, H);
     const int ow0 = max(S * w - (S + 1) / 2, 0), ow1 = min(S * w + S + (S + 1) / 2, W);
     for (int ow = ow0; ow < ow1; ++ow) {
-      const LerpS b = lerp_scale(ow, Ws, inv);
+      const Lerp b = lerp_scale(ow, Ws, inv);
       const float wx = (b.i0 == w ? b.l0 : 0.f) + (b.i1 == w ? b.l1 : 0.f);
       if (wx == 0.f) continue;
       float r[3][4];   // x-interpolated logits of source rows h-1, h, h+1 at this output column
@@ -583,7 +550,7 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const float* __restrict_
         r[i][2] = mix2(b.l0, u0.z, b.l1, u1.z); r[i][3] = mix2(b.l0, u0.w, b.l1, u1.w);
       }
       for (int oh = oh0; oh < oh1; ++oh) {
-        const LerpS a = lerp_scale(oh, Hs, inv);
+        const Lerp a = lerp_scale(oh, Hs, inv);
         const float wy = (a.i0 == h ? a.l0 : 0.f) + (a.i1 == h ? a.l1 : 0.f);
         if (wy == 0.f) continue;
         const long o = ((long)n * H + oh) * W + ow;
@@ -712,7 +679,7 @@ __global__ __launch_bounds__(512) void ce_up_bwd_tiled_kernel(const float* __res
       float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
       if (tg >= 0) {
         const float l = ls[o];
-        const LerpS a = lerp_scale(oh, Hs, inv), b = lerp_scale(ow, Ws, inv);
+        const Lerp a = lerp_scale(oh, Hs, inv), b = lerp_scale(ow, Ws, inv);
         const float4 u00 = *reinterpret_cast<const float4*>(zs + ((a.i0 - g.zr0) * CE_ZT + (b.i0 - g.zc0)) * ldc + 4 * q);
         const float4 u01 = *reinterpret_cast<const float4*>(zs + ((a.i0 - g.zr0) * CE_ZT + (b.i1 - g.zc0)) * ldc + 4 * q);
         const float4 u10 = *reinterpret_cast<const float4*>(zs + ((a.i1 - g.zr0) * CE_ZT + (b.i0 - g.zc0)) * ldc + 4 * q);
@@ -745,7 +712,7 @@ __global__ __launch_bounds__(512) void ce_up_bwd_tiled_kernel(const float* __res
 #pragma unroll
         for (int i = 0; i < R; ++i) {
           const int oh = S * h - S / 2 + i, ow = S * w - S / 2 + i;
-          const LerpS a = lerp_scale(oh, Hs, inv), bb = lerp_scale(ow, Ws, inv);
+          const Lerp a = lerp_scale(oh, Hs, inv), bb = lerp_scale(ow, Ws, inv);
           const bool yin = oh >= 0 && oh < H, xin = ow >= 0 && ow < W;
           wy[i] = yin ? (a.i0 == h ? a.l0 : 0.f) + (a.i1 == h ? a.l1 : 0.f) : 0.f;
           wx[i] = xin ? (bb.i0 == w ? bb.l0 : 0.f) + (bb.i1 == w ? bb.l1 : 0.f) : 0.f;

@@ -1,4 +1,4 @@
-"""The operand-plane definition (csrc/conv_x3.h `split1`, DESIGN.md "Operand planes"), restated in numpy on bit
+"""The operand-plane definition (csrc/planes.h `split_bf16`, DESIGN.md "Operand planes"), restated in numpy on bit
 patterns: uint32 / uint64 integer arithmetic for every rounding, so no library's fp32 -> 16-bit converter is trusted.
 The only floating-point operation is the ONE IEEE fp32 subtraction (and, for `transposed`, the one fp32 product) the
 definition itself contains.

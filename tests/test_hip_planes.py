@@ -330,6 +330,20 @@ def test_relu_backward_scaled_planes(cuda, math, scale):
         check_buf(buf, g, "relu_backward_scaled scale=%r n=%d" % (scale, m), grad=True)
 
 
+# one element group, one wavefront's worth, and one element group past a full grid stride of the 8192-workgroup launch
+@pytest.mark.parametrize("n", [8, 64, 8 * 256 * 8192 + 8])
+def test_relu_backward_is_the_gate_at_scale_one(cuda, math, n):
+    """kGate (dy passes through, no multiply) and kGateScaled at scale 1.0 are the same pass: the same g and the same
+    plane words, bit for bit (-0, subnormals and huge values included), the sentinel words past the tensor too."""
+    dy, y = dev(vals(n, 40, K.GRAD_SHIFT), cuda), dev(_gate(n, 7), cuda)
+    g = E.relu_backward(dy, y, emit_planes=True)
+    e = K._PLANES.get((g.data_ptr(), g.numel()))
+    assert e is not None and e[1] == g._version, "relu_backward n=%d: no planes were registered" % n
+    g1, buf1 = E.relu_backward_scaled(dy, y, 1.0)
+    assert torch.equal(g.view(torch.int32), g1.view(torch.int32)), "n=%d: g differs" % n
+    assert e[2].shape == buf1.shape and torch.equal(e[2], buf1), "n=%d: plane words differ" % n
+
+
 @pytest.mark.parametrize("cols", [8, 16, 264])
 def test_split_rowscale_planes(cuda, math, cols):
     """kRowScale stores no fp32 value: the expected operand is the one fp32 product, computed on the CPU.  cols = 8: the
@@ -465,7 +479,7 @@ def finish(request):
 
 @pytest.mark.parametrize("case", EPILOGUE_CASES, ids=[c[0] for c in EPILOGUE_CASES])
 def test_contraction_epilogue_planes(cuda, math, finish, case):
-    """Planes written by a contraction's epilogue (emit_planes4: narrow / wide stores, the finishing pass, the in-kernel
+    """Planes written by a contraction's epilogue (put_planes: narrow / wide stores, the finishing pass, the in-kernel
     finish, the halo row map) = the split of the fp32 result of the SAME launch."""
     name, n, c, h, w, o, k, s, p, d = case
     pl = K._plan((n, c, h, w), (o, c, k, k), s, p, d)
