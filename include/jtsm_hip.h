@@ -1221,6 +1221,82 @@ int jtsm_keypoint_upsample_forward_f32(const float* z, int R, int K, int H, int 
 int jtsm_keypoint_upsample_backward_f32(const float* grad_logits, int R, int K, int H, int W, int Cp, float* grad_z,
                                         void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * RetinaNet.  Built without floating-point contraction.  Nothing is allocated and nothing
+ * synchronises with the host; data-dependent counts stay on the device.
+ *
+ * The level table.  The head's outputs are read where the convolutions wrote them: `logits` / `deltas` are HOST arrays
+ * of L (<= 8) device pointers, one per level, and `geom` is a HOST array of L rows of six int64:
+ *   cells (= H * W), anchor_offset (first row of the level in R), logits image stride, logits cell stride,
+ *   deltas image stride, deltas cell stride                                                    (strides in floats).
+ * A cell holds A rows of K logits (4 deltas) back to back; the floats of a cell beyond A * K (4 A) are padding, as
+ * conv2d_padded leaves behind bbox_pred's 36 channels.  Row cell * A + a of level l is anchor anchor_offset[l] + it:
+ * `permute_to_N_HWA_K` (retinanet.py:27-36) as a view.  A plain (N, HWA, K) tensor with a row stride is A = 1.
+ * 16-byte accesses are used where K % 4 == 0 and every pointer, cell stride and image stride is a multiple of four
+ * floats; one float at a time otherwise.
+ *
+ * jtsm_retinanet_label_anchors_f32 — `RetinaNet.label_anchors` (retinanet.py:353-397) with `Matcher.__call__` and
+ *   `set_low_quality_matches_` (modeling/matcher.py:61-126) for the whole batch.  anchors (R, 4); gt_boxes (G, 4) and
+ *   gt_classes (G) int64 concatenated over images, gt_offsets (N + 1) int32 ON THE DEVICE; `thresholds`
+ *   (num_thresholds, ascending, without the matcher's -inf / +inf ends) and `interval_labels` (num_thresholds + 1, each
+ *   -1 / 0 / 1) are HOST arrays.  labels (N, R) int32 <- -1 ignore, 0 .. K - 1, K background; matched (N, R) int32 <-
+ *   the gt row within the image with the largest IoU, the LOWEST among equals (0 without gt); *num_pos (device) <-
+ *   anchors with 0 <= label < K over the batch.  IoU = pairwise_iou (box_iou, box_math.h).  An anchor whose IoU with
+ *   some gt equals that gt's maximum over all anchors is positive whatever its interval, with its own arg-max as
+ *   `matched` — so a gt that overlaps no anchor (maximum 0, e.g. zero area) turns every anchor that overlaps none
+ *   positive, as the reference does.  The per-gt maximum is an integer atomic max over the bits of non-negative
+ *   floats; no G x R matrix is stored (the IoUs are formed twice); gt boxes go through LDS 256 at a time.
+ *   workspace: jtsm_retinanet_label_workspace_bytes(G).
+ *
+ * jtsm_retinanet_loss_forward_f32 / _backward_f32 — `RetinaNet.losses` (retinanet.py:287-351):
+ *   loss_cls <- sum over anchors with label >= 0 and all K classes of fvcore's sigmoid_focal_loss (target 1 at the
+ *   label's class; alpha < 0: no alpha term; gamma 0 and 2 without pow), loss_box_reg <- sum over positive anchors of
+ *   smooth_l1(deltas, Box2BoxTransform(weights).get_deltas(anchor, gt_boxes[gt_offsets[n] + matched]), beta)
+ *   (beta < 1e-5: L1), both divided by the fp32 value of *normalizer (one double on the device).  training != 0 first
+ *   updates *normalizer <- momentum * *normalizer + (1 - momentum) * max(*num_pos, 1), in fp64.  Sums: fp64
+ *   per-workgroup partials and one fixed-order final pass — the same inputs give the same bits.  workspace:
+ *   jtsm_retinanet_loss_workspace_bytes(), carried to the backward (it keeps the divisor the forward used).
+ *   Backward: grad_logits / grad_deltas are HOST arrays of L device pointers to maps laid out as `grad_geom` says
+ *   (the inputs' cells and cell strides; image strides that hold whole cells); EVERY float of every cell is written — the closed-form derivative times
+ *   *grad_cls (*grad_box_reg, device scalars) / the saved divisor, zeros for ignored anchors, for the deltas of
+ *   non-positive anchors and in the padding.  weights: HOST array of 4.
+ *
+ * jtsm_retinanet_candidates_f32 — the per-level part of `inference_single_image` (retinanet.py:453-481) for every
+ *   image and level: keep sigmoid(x) > score_thresh (a NaN never passes), the `topk` best of each (image, level) by
+ *   score, EQUAL fp32 SCORES BY LOWER FLAT INDEX anchor * K + class FIRST (the reference's sort leaves that order
+ *   open), decoded by apply_deltas(weights, scale_clamp) in decode_box's order.  Outputs have N * L * topk slots,
+ *   slot (n * L + l) * topk + place: boxes (.., 4), scores, classes int64 (-1 in unused slots, which
+ *   jtsm_batched_nms_f32 drops), rows int32 (optional: the anchor's row within its level, -1 unused), counts (N * L) int32.  The cut is found by a radix select over 16-bit digits of the
+ *   key (score bits, inverted flat index): the workspace, jtsm_retinanet_candidates_workspace_bytes(N, L, topk), is
+ *   one 65536-bin histogram and topk keys per (image, level) whatever passes the threshold.
+ * ------------------------------------------------------------------------------------------------------------------ */
+size_t jtsm_retinanet_label_workspace_bytes(int total_gt);
+int jtsm_retinanet_label_anchors_f32(const float* anchors, int R, const float* gt_boxes, const int32_t* gt_offsets,
+                                     const int64_t* gt_classes, int N, int total_gt, const float* thresholds,
+                                     const int32_t* interval_labels, int num_thresholds, int num_classes,
+                                     int32_t* labels, int32_t* matched, int32_t* num_pos, void* workspace,
+                                     void* stream);
+size_t jtsm_retinanet_loss_workspace_bytes(void);
+int jtsm_retinanet_loss_forward_f32(const float* const* logits, const float* const* deltas, const int64_t* geom,
+                                    int L, int N, int A, int K, int R, const int32_t* labels, const int32_t* matched,
+                                    const float* anchors, const float* gt_boxes, const int32_t* gt_offsets,
+                                    float alpha, float gamma, float beta, const float* weights,
+                                    const int32_t* num_pos, double* normalizer, double momentum, int training,
+                                    float* loss_cls, float* loss_box_reg, void* workspace, void* stream);
+int jtsm_retinanet_loss_backward_f32(const float* const* logits, const float* const* deltas, const int64_t* geom,
+                                     int L, int N, int A, int K, int R, const int32_t* labels, const int32_t* matched,
+                                     const float* anchors, const float* gt_boxes, const int32_t* gt_offsets,
+                                     float alpha, float gamma, float beta, const float* weights,
+                                     const float* grad_cls, const float* grad_box_reg, const void* workspace,
+                                     float* const* grad_logits, float* const* grad_deltas, const int64_t* grad_geom,
+                                     void* stream);
+size_t jtsm_retinanet_candidates_workspace_bytes(int N, int L, int topk);
+int jtsm_retinanet_candidates_f32(const float* const* logits, const float* const* deltas, const int64_t* geom, int L,
+                                  int N, int A, int K, int R, const float* anchors, const float* weights,
+                                  float scale_clamp, float score_thresh, int topk, float* boxes, float* scores,
+                                  int64_t* classes, int32_t* rows, int32_t* counts, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* Model input boundary: GeneralizedMCNNWSL.preprocess_image
  * (projects/WSL/wsl/modeling/meta_arch/mcnn.py:303-318) + ImageList.from_tensors
  * (detectron2/structures/image_list.py:71-125) in one launch: images[b] is the mapper's uint8 (C, h_b, w_b) planar

@@ -13,6 +13,85 @@ import os
 import yaml
 
 BASE_KEY = "_BASE_"
+EVAL_TAG = "tag:yaml.org,2002:python/object/apply:eval"
+
+_BINARY = {ast.Add: lambda a, b: a + b, ast.Sub: lambda a, b: a - b, ast.Mult: lambda a, b: a * b,
+           ast.Div: lambda a, b: a / b, ast.Pow: lambda a, b: a ** b}
+
+
+def eval_arithmetic(text):
+    """The value of a `!!python/object/apply:eval` string (Base-RetinaNet.yaml writes its anchor sizes as one), without
+    eval: the expression's AST may hold numeric literals, lists and tuples, + - * / **, unary minus, and ONE list
+    comprehension over a literal list with the name(s) it binds.  The operators are Python's own on Python's own
+    numbers, so the doubles are the ones eval gives.  Anything else — a call, an attribute, a subscript, a string, a
+    name that was not bound — raises ValueError."""
+    if not isinstance(text, str) or len(text) > 1000:
+        raise ValueError("config: the eval tag takes one short string")
+    try:
+        tree = ast.parse(text.strip(), mode="eval")
+    except SyntaxError as e:
+        raise ValueError("config: cannot parse %r: %s" % (text, e)) from None
+    state = {"comprehensions": 0}
+
+    def number(v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError("config: %r is not a number" % (v,))
+        return v
+
+    def walk(node, names):
+        if isinstance(node, ast.Constant):
+            return number(node.value)
+        if isinstance(node, (ast.List, ast.Tuple)) and isinstance(node.ctx, ast.Load):
+            items = [walk(e, names) for e in node.elts]
+            return items if isinstance(node, ast.List) else tuple(items)
+        if isinstance(node, ast.Name) and isinstance(node.ctx, ast.Load) and node.id in names:
+            return names[node.id]
+        if isinstance(node, ast.UnaryOp) and isinstance(node.op, ast.USub):
+            return -number(walk(node.operand, names))
+        if isinstance(node, ast.BinOp) and type(node.op) in _BINARY:
+            a, b = number(walk(node.left, names)), number(walk(node.right, names))
+            if isinstance(node.op, ast.Pow) and (abs(b) > 64 or abs(a) > 1e6):
+                raise ValueError("config: %r ** %r is out of the range an anchor size needs" % (a, b))
+            return _BINARY[type(node.op)](a, b)
+        if isinstance(node, ast.ListComp):
+            state["comprehensions"] += 1
+            gen = node.generators[0]
+            if state["comprehensions"] > 1 or len(node.generators) != 1 or gen.ifs or gen.is_async \
+                    or not isinstance(gen.iter, (ast.List, ast.Tuple)):
+                raise ValueError("config: one list comprehension over a literal list, no conditions")
+            targets = [gen.target] if isinstance(gen.target, ast.Name) else getattr(gen.target, "elts", [None])
+            if not all(isinstance(t, ast.Name) for t in targets):
+                raise ValueError("config: a comprehension binds plain names")
+            out = []
+            for item in walk(gen.iter, {}):                       # (a literal: it sees no names)
+                bound = dict(names)
+                if isinstance(gen.target, ast.Name):
+                    bound[gen.target.id] = item
+                else:
+                    if not isinstance(item, (list, tuple)) or len(item) != len(targets):
+                        raise ValueError("config: cannot unpack %r" % (item,))
+                    bound.update({t.id: v for t, v in zip(targets, item)})
+                out.append(walk(node.elt, bound))
+            return out
+        raise ValueError("config: %s is not allowed in an eval tag (%r)" % (type(node).__name__, text))
+
+    return walk(tree.body, {})
+
+
+class _Loader(yaml.SafeLoader):
+    """yaml.SafeLoader plus the one python tag the reference's configs use."""
+
+
+def _construct_eval(loader, node):
+    if not isinstance(node, yaml.SequenceNode) or len(node.value) != 1 or not isinstance(node.value[0], yaml.ScalarNode):
+        raise yaml.constructor.ConstructorError(None, None, "the eval tag takes a list of one string", node.start_mark)
+    try:
+        return eval_arithmetic(loader.construct_scalar(node.value[0]))
+    except ValueError as e:
+        raise yaml.constructor.ConstructorError(None, None, str(e), node.start_mark) from None
+
+
+_Loader.add_constructor(EVAL_TAG, _construct_eval)
 
 
 class CfgNode(dict):
@@ -116,7 +195,7 @@ class CfgNode(dict):
         with open(filename, "r") as f:
             text = f.read()
         # yacs configs write tuples as python literals, e.g. STEPS: (60000, 80000)
-        cfg = yaml.safe_load(text) or {}
+        cfg = yaml.load(text, Loader=_Loader) or {}       # (the safe loader + `!!python/object/apply:eval`, whitelisted)
         if BASE_KEY in cfg:
             base_file = cfg.pop(BASE_KEY)
             if base_file.startswith("~"):

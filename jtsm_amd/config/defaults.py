@@ -57,6 +57,12 @@ _DEFAULTS = {
         "SEM_SEG_HEAD": {"NAME": "SemSegFPNHead", "IN_FEATURES": ["p2", "p3", "p4", "p5"], "IGNORE_VALUE": 255,
                          "NUM_CLASSES": 54, "CONVS_DIM": 128, "COMMON_STRIDE": 4, "NORM": "GN", "LOSS_WEIGHT": 1.0},
         # detectron2/config/defaults.py:398-406 (combine_semantic_and_instance_outputs thresholds)
+        # detectron2/config/defaults.py:412-454
+        "RETINANET": {"NUM_CLASSES": 80, "IN_FEATURES": ["p3", "p4", "p5", "p6", "p7"], "NUM_CONVS": 4,
+                      "IOU_THRESHOLDS": [0.4, 0.5], "IOU_LABELS": [0, -1, 1], "PRIOR_PROB": 0.01,
+                      "SCORE_THRESH_TEST": 0.05, "TOPK_CANDIDATES_TEST": 1000, "NMS_THRESH_TEST": 0.5,
+                      "BBOX_REG_WEIGHTS": (1.0, 1.0, 1.0, 1.0), "FOCAL_LOSS_GAMMA": 2.0, "FOCAL_LOSS_ALPHA": 0.25,
+                      "SMOOTH_L1_LOSS_BETA": 0.1, "BBOX_REG_LOSS_TYPE": "smooth_l1", "NORM": ""},
         "PANOPTIC_FPN": {"INSTANCE_LOSS_WEIGHT": 1.0,
                          "COMBINE": {"ENABLED": True, "OVERLAP_THRESH": 0.5, "STUFF_AREA_LIMIT": 4096,
                                      "INSTANCES_CONFIDENCE_THRESH": 0.5}},

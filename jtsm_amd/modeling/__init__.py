@@ -4,7 +4,7 @@ from .backbone import BACKBONE_REGISTRY, FPN, Backbone, ResNet, build_backbone, 
 from .anchor_generator import (ANCHOR_GENERATOR_REGISTRY, DefaultAnchorGenerator, RotatedAnchorGenerator,
                                build_anchor_generator)
 from .meta_arch import (META_ARCH_REGISTRY, SEM_SEG_HEADS_REGISTRY, GeneralizedMCNNWSL, GeneralizedRCNN, PanopticFPN,
-                        SemSegFPNHead, build_model, build_sem_seg_head)
+                        RetinaNet, RetinaNetHead, SemSegFPNHead, build_model, build_sem_seg_head)
 from .proposal_generator import PROPOSAL_GENERATOR_REGISTRY, RPN, RPN_HEAD_REGISTRY, RRPN, build_proposal_generator
 from .poolers import ROIPooler
 from .roi_heads import (ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY, ROI_MASK_HEAD_REGISTRY, JTSMROIHeads,

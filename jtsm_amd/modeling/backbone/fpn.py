@@ -1,5 +1,6 @@
 """Feature pyramid behind the reference's names — API surface of detectron2/modeling/backbone/fpn.py (:16-160 FPN,
-:173-185 LastLevelMaxPool, :209-229 build_resnet_fpn_backbone): same constructor, module names
+:173-185 LastLevelMaxPool, :188-206 LastLevelP6P7, :209-253 build_resnet_fpn_backbone /
+build_retinanet_resnet_fpn_backbone): same constructor, module names
 (fpn_lateral{L}, fpn_output{L}) and output names (p{L}); the construction is this repo's own.
 
 MI355X mapping: lateral 1x1 and output 3x3 convolutions are MFMA launches with the bias in the epilogue; the
@@ -10,6 +11,7 @@ the coarsest level down.
 import math
 
 from torch import nn
+from torch.nn import functional as F
 
 from ...layers.batch_norm import get_norm
 from ...layers.elementwise import subsample2, upsample2_add
@@ -67,7 +69,8 @@ class FPN(Backbone):
                 names.append("p%d" % (top + extra))
                 strides[names[-1]] = 2 ** (top + extra)
         self._declare_outputs(names, {n: out_channels for n in names}, strides)
-        self._size_divisibility = 2 ** self.levels[-1][0]
+        # (a top block that convolves with stride 2 needs the input divisible by its levels' strides too)
+        self._size_divisibility = 2 ** (self.levels[-1][0] + getattr(top_block, "strided_levels", 0))
 
     @property
     def size_divisibility(self):
@@ -117,6 +120,25 @@ class LastLevelMaxPool(nn.Module):
         return [subsample2(x)]
 
 
+class LastLevelP6P7(nn.Module):
+    """P6 = conv3x3 / stride 2 of C5, P7 = conv3x3 / stride 2 of relu(P6) (fpn.py:188-206), RetinaNet's two extra
+    levels.  Both are MFMA launches; with them the pyramid reaches stride 128, which the input is padded to."""
+
+    def __init__(self, in_channels, out_channels, in_feature="res5"):
+        super().__init__()
+        self.num_levels = 2
+        self.strided_levels = 2
+        self.in_feature = in_feature
+        self.p6 = Conv2d(in_channels, out_channels, kernel_size=3, stride=2, padding=1)
+        self.p7 = Conv2d(out_channels, out_channels, kernel_size=3, stride=2, padding=1)
+        for conv in (self.p6, self.p7):
+            _xavier(conv)
+
+    def forward(self, c5):
+        p6 = self.p6(c5)
+        return [p6, self.p7(F.relu(p6))]
+
+
 def fpn_from_cfg(cfg, bottom_up):
     f = cfg.MODEL.FPN
     return FPN(bottom_up=bottom_up, in_features=f.IN_FEATURES, out_channels=f.OUT_CHANNELS, norm=f.NORM,
@@ -133,3 +155,13 @@ def build_wsl_resnet_v2_fpn_backbone(cfg, input_shape: ShapeSpec):
     """projects/WSL/wsl/modeling/backbone/resnet_wsl_v2.py:729-750."""
     from .resnet_wsl_v2 import build_wsl_resnet_v2_backbone
     return fpn_from_cfg(cfg, build_wsl_resnet_v2_backbone(cfg, input_shape))
+
+
+@BACKBONE_REGISTRY.register()
+def build_retinanet_resnet_fpn_backbone(cfg, input_shape: ShapeSpec):
+    """fpn.py:232-253: the ResNet pyramid with P6 / P7 convolved from res5."""
+    bottom_up = build_resnet_backbone(cfg, input_shape)
+    f = cfg.MODEL.FPN
+    return FPN(bottom_up=bottom_up, in_features=f.IN_FEATURES, out_channels=f.OUT_CHANNELS, norm=f.NORM,
+               top_block=LastLevelP6P7(bottom_up.output_shape()["res5"].channels, f.OUT_CHANNELS),
+               fuse_type=f.FUSE_TYPE)
