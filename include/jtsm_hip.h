@@ -1297,6 +1297,85 @@ int jtsm_retinanet_candidates_f32(const float* const* logits, const float* const
                                   int64_t* classes, int32_t* rows, int32_t* counts, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * PointRend.  Built without floating-point contraction.  Nothing is allocated and nothing synchronises
+ * with the host.  Every bilinear read is ATen's grid_sample with align_corners = False and zero padding, in fp32 in
+ * its order: source = ((2 p - 1 + 1) * size - 1) / 2, weights (x1 - x)(y1 - y) ..., taps added nw, ne, sw, se.
+ *
+ * The source table.  `maps` is a HOST array of L (<= 8) device pointers, `scales` a HOST array of L floats and `geom` a
+ * HOST array of L rows of nine int64:  H, W, C, first output column, kind, and the strides in floats of the map's
+ * image (or roi), channel, row and column.  kind 0 is a feature map shared by the rois of an image: it is indexed by
+ * roi_image[r] (0 .. num_images - 1; any other value reads zeros) and read at the image-space point divided by (W, H) / scale.  kind 1 is a map per roi (the coarse
+ * logits): it is indexed by r and read at the box-normalised point; its scale is ignored.
+ *
+ * The points.  grid_side == 0: `points` (R, P, 2), box-normalised.  grid_side > 0: P == grid_side^2 and point q of
+ * every roi is cell q of `generate_regular_grid_point_coords` (point_features.py:54-69), row-major or, with
+ * space_to_depth != 0 (even sides), in the order ((by * side/2 + bx) * 2 + dy) * 2 + dx of cell (2 by + dy, 2 bx + dx).
+ *
+ * jtsm_point_gather_forward_f32 — `point_sample_fine_grained_features` + `point_sample` (point_features.py:28-51,
+ *   155-225) for all rois, images and sources in one launch: row r * P + q of `rows` (row_stride floats apart) gets
+ *   the C channels of source l in columns col_l .. col_l + C_l; other columns are not touched.  coords_wrt_image
+ *   (R, P, 2, optional) <- `get_point_coords_wrt_image`.
+ * jtsm_point_gather_backward_roi_f32 — the gradient of a kind-1 source: one workgroup per roi, every cell of the
+ *   roi's (C, H, W) map walks the roi's points in order.  Every cell is written, at the given strides.
+ * jtsm_point_gather_backward_map_f32 — the gradient of a kind-0 source into a dense channels-last (N, H, W, C) map:
+ *   tap records keyed by (image, cell), sorted stably, each cell summed in record order.  Every float is written,
+ *   or with accumulate != 0 added to (layers/grad_fan.py: the map has other readers).
+ *   workspace: jtsm_point_gather_backward_map_workspace_bytes(R, P, N, H, W).
+ *
+ * jtsm_point_select_f32 — `get_uncertain_point_coords_with_randomness` with `calculate_uncertainty`
+ *   (point_features.py:72-125, mask_head.py:23-45).  coarse_logits (R, C, S, S) plain; classes (R) int64 (unused when
+ *   C == 1); candidates (R, K, 2) and randoms (R, P - num_uncertain, 2) are the two torch.rand draws.  point_coords
+ *   (R, P, 2) <- the num_uncertain candidates with the largest -|logit|, most uncertain first, EQUAL UNCERTAINTIES BY
+ *   LOWER CANDIDATE INDEX, then the randoms.  chosen (R, num_uncertain) int32, optional: the candidates' indices.
+ *
+ * jtsm_point_loss_forward_f32 / _backward_f32 — `roi_mask_point_loss` (point_head.py:22-96).  logits (R * P, ld);
+ *   `masks` is a HOST array of N (<= 64) device pointers to (count, h, w) uint8 / bool bitmasks and mask_geom a HOST
+ *   array of N rows (h, w, count) int32; roi r reads mask matched[r] of image roi_image[r] at coords_wrt_image / (w, h).
+ *   *loss <- mean over R * P of BCE-with-logits of the class column (column 0 when C == 1) against the soft target;
+ *   stats[0] <- rows with (logit > 0) == uint8(target), stats[1] <- R * P.  R == 0 gives 0.  Sums are fp64 partials per
+ *   workgroup folded in a fixed order.  workspace: jtsm_point_loss_workspace_bytes(R, P); it starts with the R * P soft
+ *   targets and is carried to the backward, which writes every float of grad_logits (R * P, C; grad_ld apart).
+ *
+ * jtsm_point_subdivide_f32 — one step of `_forward_mask_point`'s loop (mask_head.py:245-261) on ONE channel: map
+ *   (R, H, W) -> upsampled_map (R, 2H, 2W) by F.interpolate(scale_factor = 2, "bilinear"), and, when num_points > 0,
+ *   `get_uncertain_point_coords_on_grid`: indices (R, n) int64 and point_coords (R, n, 2), n = min(4 H W, num_points),
+ *   most uncertain first, EQUAL UNCERTAINTIES BY LOWER CELL INDEX.  H * W <= 12544, num_points <= 1024.
+ * jtsm_point_topk_grid_f32 — `get_uncertain_point_coords_on_grid` (point_features.py:128-152) on a given (R, H, W)
+ *   uncertainty map, read from memory: the num_points (<= min(H W, 1024)) largest values, same order and tie rule.
+ * jtsm_point_scatter_f32 — map[r, indices[r, j]] <- point_logits[r * n + j, classes[r]] (column 0 when C == 1).
+ * ------------------------------------------------------------------------------------------------------------------ */
+int jtsm_point_gather_forward_f32(const float* const* maps, const int64_t* geom, const float* scales, int L,
+                                  int num_images, const float* boxes, const int32_t* roi_image, const float* points,
+                                  int R, int P, int grid_side, int space_to_depth, float* rows, int64_t row_stride,
+                                  float* coords_wrt_image, void* stream);
+int jtsm_point_gather_backward_roi_f32(const float* grad_rows, int64_t row_stride, int col, const float* points, int R,
+                                       int P, int grid_side, int space_to_depth, int C, int H, int W, float* grad_map,
+                                       int64_t stride_n, int64_t stride_c, int64_t stride_y, int64_t stride_x,
+                                       void* stream);
+size_t jtsm_point_gather_backward_map_workspace_bytes(int R, int P, int N, int H, int W);
+int jtsm_point_gather_backward_map_f32(const float* grad_rows, int64_t row_stride, int col, const float* boxes,
+                                       const int32_t* roi_image, const float* points, int R, int P, int grid_side,
+                                       int space_to_depth, int N, int H, int W, int C, float scale, float* grad_map,
+                                       int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+int jtsm_point_select_f32(const float* coarse_logits, int R, int C, int S, const int64_t* classes,
+                          const float* candidates, int num_candidates, const float* randoms, int num_uncertain,
+                          int P, float* point_coords, int32_t* chosen, void* stream);
+size_t jtsm_point_loss_workspace_bytes(int R, int P);
+int jtsm_point_loss_forward_f32(const float* logits, int64_t ld, int R, int P, int C, const int64_t* classes,
+                                const uint8_t* const* masks, const int32_t* mask_geom, int N, const int32_t* roi_image,
+                                const int32_t* matched, const float* coords_wrt_image, float* loss, int32_t* stats,
+                                void* workspace, void* stream);
+int jtsm_point_loss_backward_f32(const float* logits, int64_t ld, int R, int P, int C, const int64_t* classes,
+                                 const float* grad_loss, const void* workspace, float* grad_logits, int64_t grad_ld,
+                                 void* stream);
+int jtsm_point_subdivide_f32(const float* map, int R, int H, int W, float* upsampled_map, int num_points,
+                             int64_t* indices, float* point_coords, void* stream);
+int jtsm_point_topk_grid_f32(const float* uncertainty_map, int R, int H, int W, int num_points, int64_t* indices,
+                             float* point_coords, void* stream);
+int jtsm_point_scatter_f32(const float* point_logits, int64_t ld, int R, int num_points, int C, const int64_t* classes,
+                           const int64_t* indices, int cells, float* map, void* stream);
+
 /* Model input boundary: GeneralizedMCNNWSL.preprocess_image
  * (projects/WSL/wsl/modeling/meta_arch/mcnn.py:303-318) + ImageList.from_tensors
  * (detectron2/structures/image_list.py:71-125) in one launch: images[b] is the mapper's uint8 (C, h_b, w_b) planar

@@ -9,8 +9,11 @@ _DEFAULTS = {
     "VIS_PERIOD": 0,
     "SEED": -1,
     # detectron2/config/defaults.py:40-60 (INPUT), :84-96 (DATASETS), :607-620 (TEST.AUG)
+    # (COLOR_AUG_SSD, CROP.SINGLE_CATEGORY_MAX_AREA: projects/PointRend/point_rend/config.py:11-15; read by the
+    # semantic-segmentation PointRend only, which is not built)
     "INPUT": {"FORMAT": "BGR", "MASK_FORMAT": "polygon", "MIN_SIZE_TRAIN": (800,), "MIN_SIZE_TRAIN_SAMPLING": "choice",
-              "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333},
+              "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "COLOR_AUG_SSD": False,
+              "CROP": {"SINGLE_CATEGORY_MAX_AREA": 1.0}},
     "DATASETS": {"PRECOMPUTED_PROPOSAL_TOPK_TRAIN": 2000, "PRECOMPUTED_PROPOSAL_TOPK_TEST": 1000},
     "TEST": {"DETECTIONS_PER_IMAGE": 100, "KEYPOINT_OKS_SIGMAS": [],
              "AUG": {"ENABLED": False, "MIN_SIZES": (400, 500, 600, 700, 800, 900, 1000, 1100, 1200), "MAX_SIZE": 4000,
@@ -47,7 +50,16 @@ _DEFAULTS = {
                          "TRAIN_ON_PRED_BOXES": False},
         "ROI_MASK_HEAD": {"NAME": "MaskRCNNConvUpsampleHead", "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0,
                           "NUM_CONV": 0, "CONV_DIM": 256, "NORM": "", "CLS_AGNOSTIC_MASK": False,
-                          "POOLER_TYPE": "ROIAlignV2"},
+                          "POOLER_TYPE": "ROIAlignV2",
+                          # projects/PointRend/point_rend/config.py:17-24 (the coarse head of PointRendMaskHead)
+                          "IN_FEATURES": ("p2",), "FC_DIM": 1024, "NUM_FC": 2, "OUTPUT_SIDE_RESOLUTION": 7,
+                          "POINT_HEAD_ON": False},
+        # projects/PointRend/point_rend/config.py:26-48
+        "POINT_HEAD": {"NAME": "StandardPointHead", "NUM_CLASSES": 80, "IN_FEATURES": ("p2",),
+                       "TRAIN_NUM_POINTS": 14 * 14, "OVERSAMPLE_RATIO": 3, "IMPORTANCE_SAMPLE_RATIO": 0.75,
+                       "SUBDIVISION_STEPS": 5, "SUBDIVISION_NUM_POINTS": 28 * 28, "FC_DIM": 256, "NUM_FC": 3,
+                       "CLS_AGNOSTIC_MASK": False, "COARSE_PRED_EACH_LAYER": True,
+                       "COARSE_SEM_SEG_HEAD_NAME": "SemSegFPNHead"},
         # detectron2/config/defaults.py:347-377 (and :584, TEST.KEYPOINT_OKS_SIGMAS)
         "ROI_KEYPOINT_HEAD": {"NAME": "KRCNNConvDeconvUpsampleHead", "POOLER_RESOLUTION": 14,
                               "POOLER_SAMPLING_RATIO": 0, "POOLER_TYPE": "ROIAlignV2",

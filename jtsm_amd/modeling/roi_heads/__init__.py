@@ -6,6 +6,8 @@ from .mask_head import (ROI_MASK_HEAD_REGISTRY, MaskRCNNConvUpsampleHead, MaskRC
                         mask_rcnn_loss)
 from .roi_heads import (ROI_HEADS_REGISTRY, ROIHeads, StandardROIHeads, build_roi_heads, select_foreground_proposals,
                         select_proposals_with_visible_keypoints)
+from .point_head import POINT_HEAD_REGISTRY, StandardPointHead, build_point_head
+from .point_rend_mask_head import CoarseMaskHead, PointRendMaskHead, PointRendROIHeads
 from .roi_heads_jtsm import JTSMROIHeads
 from .roi_heads_contextlocnet import ContextLocNetROIHeads
 from .fast_rcnn_wsddn import WSDDNOutputLayers

@@ -64,6 +64,22 @@ class FastRCNNOutputLayers(nn.Module):
         return {k: v * self.loss_weight.get(k, 1.0) for k, v in out.items()}
 
     @torch.no_grad()
+    def predict_boxes_for_gt_classes(self, predictions, proposals: List[Instances]):
+        """fast_rcnn.py:519-553: per image the (Ri, B) boxes the deltas of each proposal's gt class predict (the gt
+        class clamped into range where the proposal is background or ignored).  ROI_BOX_HEAD.TRAIN_ON_PRED_BOXES."""
+        if not len(proposals):
+            return []
+        _, deltas = predictions
+        boxes = cat([p.proposal_boxes.tensor for p in proposals], dim=0)
+        n, b = boxes.shape
+        predicted = self.box2box_transform.apply_deltas(deltas, boxes)
+        k = predicted.shape[1] // b
+        if k > 1:
+            gt_classes = cat([p.gt_classes for p in proposals], dim=0).clamp(0, k - 1)
+            predicted = predicted.view(n, k, b)[torch.arange(n, dtype=torch.long, device=predicted.device), gt_classes]
+        return predicted.split([len(p) for p in proposals])
+
+    @torch.no_grad()
     def inference(self, predictions: Tuple[torch.Tensor, torch.Tensor], proposals: List[Instances]):
         scores, deltas = predictions
         counts = [len(p) for p in proposals]

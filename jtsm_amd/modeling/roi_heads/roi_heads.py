@@ -63,6 +63,26 @@ def bag_offsets(counts, device):
     return torch.tensor([0] + list(torch.tensor(counts).cumsum(0)), dtype=torch.int32).to(device, non_blocking=True)
 
 
+def cropped_mask_targets(fg, targets, side):
+    """Per foreground roi its matched instance's bitmask cropped to the roi at side x side (crop_and_resize =
+    ROIAlign(1.0, sampling 0, aligned) >= 0.5): (R, side, side) bool, concatenated over the images."""
+    from ...layers.roi_align import roi_align
+
+    tgt = []
+    for p, t in zip(fg, targets):
+        if len(p) == 0:
+            continue
+        if not isinstance(t.gt_masks, torch.Tensor) or t.gt_masks.dim() != 3:
+            # (the reference's default INPUT.MASK_FORMAT is "polygon": PolygonMasks rasterised per roi by
+            # pycocotools — outside the HIP scope; BitMasks users pass `.tensor`)
+            raise TypeError("StandardROIHeads mask branch: gt_masks must be a (G, H, W) bitmask tensor "
+                            "(INPUT.MASK_FORMAT = 'bitmask'), got %r" % type(t.gt_masks).__name__)
+        masks = t.gt_masks.to(torch.float32)[:, None]                         # (G, 1, H, W) bitmasks
+        rois = torch.cat([p.matched_gt_idx.to(torch.float32)[:, None], p.proposal_boxes.tensor], dim=1)
+        tgt.append(roi_align(masks, rois, (side, side), 1.0, 0, True)[:, 0] >= 0.5)
+    return torch.cat(tgt) if tgt else None
+
+
 class ROIHeads(torch.nn.Module):
     def __init__(self, *, num_classes, batch_size_per_image, positive_fraction, proposal_matcher,
                  proposal_append_gt=True):
@@ -151,12 +171,19 @@ class StandardROIHeads(torch.nn.Module):
         self.box_head = build_box_head(cfg, ShapeSpec(channels=c, height=b.POOLER_RESOLUTION, width=b.POOLER_RESOLUTION))
         self.box_predictor = self._box_predictor(cfg, self.box_head.output_shape)
         self.mask_on = cfg.MODEL.MASK_ON
+        self.train_on_pred_boxes = b.TRAIN_ON_PRED_BOXES
         if self.mask_on:
             m = cfg.MODEL.ROI_MASK_HEAD
-            self.mask_pooler = ROIPooler(output_size=m.POOLER_RESOLUTION, scales=scales,
-                                         sampling_ratio=m.POOLER_SAMPLING_RATIO, pooler_type=m.POOLER_TYPE)
-            self.mask_head = build_mask_head(cfg, ShapeSpec(channels=c, width=m.POOLER_RESOLUTION,
-                                                            height=m.POOLER_RESOLUTION))
+            if m.POOLER_TYPE:
+                self.mask_pooler = ROIPooler(output_size=m.POOLER_RESOLUTION, scales=scales,
+                                             sampling_ratio=m.POOLER_SAMPLING_RATIO, pooler_type=m.POOLER_TYPE)
+                self.mask_head = build_mask_head(cfg, ShapeSpec(channels=c, width=m.POOLER_RESOLUTION,
+                                                                height=m.POOLER_RESOLUTION))
+            else:
+                # detectron2/modeling/roi_heads/roi_heads.py:630-641: no roi pooling, the head (PointRendMaskHead)
+                # reads the image-level features itself and is given their shapes
+                self.mask_pooler = None
+                self.mask_head = build_mask_head(cfg, {f: input_shape[f] for f in self.in_features})
         self.keypoint_on = cfg.MODEL.KEYPOINT_ON
         if self.keypoint_on:
             # detectron2/modeling/roi_heads/roi_heads.py:669-697 (_init_keypoint_head); imported only here, so a model
@@ -220,12 +247,19 @@ class StandardROIHeads(torch.nn.Module):
         x = self.box_head(self.box_pooler(feats, [p.proposal_boxes for p in proposals]))
         predictions = self.box_predictor(x)
         if self.training:
-            return self.box_predictor.losses(predictions, proposals)
+            losses = self.box_predictor.losses(predictions, proposals)
+            if self.train_on_pred_boxes:
+                # roi_heads.py:739-746: the later heads train on the boxes this one predicts, detached
+                for prop, boxes in zip(proposals, self.box_predictor.predict_boxes_for_gt_classes(predictions, proposals)):
+                    prop.proposal_boxes = Boxes(boxes)
+            return losses
         return self.box_predictor.inference(predictions, proposals)[0]
 
     @torch.no_grad()
     def forward_with_given_boxes(self, features, instances):
-        if self.mask_on:
+        if self.mask_on and self.mask_pooler is None:
+            instances = self.mask_head({f: features[f] for f in self.in_features}, instances)
+        elif self.mask_on:
             from .mask_head import mask_rcnn_inference
             feats = [features[f] for f in self.in_features]
             x = self.mask_pooler(feats, [i.pred_boxes for i in instances])
@@ -250,26 +284,16 @@ class StandardROIHeads(torch.nn.Module):
     def _forward_mask(self, features, proposals, targets):
         """Foreground rois only; the target of a roi is its matched instance's bitmask cropped to the roi at
         2 x POOLER_RESOLUTION (crop_and_resize = ROIAlign(1.0, sampling 0, aligned) >= 0.5)."""
-        from ...layers.roi_align import roi_align
         from .mask_head import mask_rcnn_loss
 
         fg, _ = select_foreground_proposals(proposals, self.num_classes)
+        if self.mask_pooler is None:
+            return self.mask_head({f: features[f] for f in self.in_features}, fg, targets)
         feats = [features[f] for f in self.in_features]
         logits, _ = self.mask_head.layers(self.mask_pooler(feats, [p.proposal_boxes for p in fg]))
         side = logits.shape[-1] if logits.shape[0] else 2 * self.mask_pooler.output_size[0]
-        tgt, base = [], 0
-        for p, t in zip(fg, targets):
-            if len(p) == 0:
-                continue
-            if not isinstance(t.gt_masks, torch.Tensor) or t.gt_masks.dim() != 3:
-                # (the reference's default INPUT.MASK_FORMAT is "polygon": PolygonMasks rasterised per roi by
-                # pycocotools — outside the HIP scope; BitMasks users pass `.tensor`)
-                raise TypeError("StandardROIHeads mask branch: gt_masks must be a (G, H, W) bitmask tensor "
-                                "(INPUT.MASK_FORMAT = 'bitmask'), got %r" % type(t.gt_masks).__name__)
-            masks = t.gt_masks.to(torch.float32)[:, None]                         # (G, 1, H, W) bitmasks
-            rois = torch.cat([p.matched_gt_idx.to(torch.float32)[:, None], p.proposal_boxes.tensor], dim=1)
-            tgt.append(roi_align(masks, rois, (side, side), 1.0, 0, True)[:, 0] >= 0.5)
+        tgt = cropped_mask_targets(fg, targets, side)
         classes = torch.cat([p.gt_classes for p in fg]) if fg else logits.new_zeros(0, dtype=torch.long)
-        if not tgt:
+        if tgt is None:
             return {"loss_mask": logits.sum() * 0}
-        return {"loss_mask": mask_rcnn_loss(logits, classes.to(torch.int64), torch.cat(tgt))}
+        return {"loss_mask": mask_rcnn_loss(logits, classes.to(torch.int64), tgt)}
