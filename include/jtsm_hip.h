@@ -526,7 +526,8 @@ int jtsm_sgd_momentum_multi_f32(const void* table, int entries, long blocks, int
  * detectron2/modeling/backbone/resnet.py:358 (max_pool2d 3,2,1), fpn.py:133-136
  * (interpolate nearest x2 + add), fpn.py:173-185 (max_pool2d 1,2,0)). */
 int jtsm_maxpool3x3s2_forward_f32(const float* x, float* y, int N, int H, int W, int C, void* stream);
-/* gx is zero-filled by the call; the gradient goes to the first maximum of each window. */
+/* Every element of gx is written; the gradient goes to the first maximum of each window, gathered per input pixel over
+ * the <= 2 x 2 windows that hold it, in window order (no float atomics: the same bits on every run). */
 int jtsm_maxpool3x3s2_backward_f32(const float* x, const float* gy, float* gx, int N, int H, int W,
                                    int C, void* stream);
 /* 2x2 max pooling of the WSL ResNet-v2 backbone (projects/WSL/wsl/modeling/backbone/resnet_wsl_v2.py:157-165,413):
@@ -792,6 +793,13 @@ int jtsm_upsample_bilinear2x_backward_f32(const float* gy, float* gx, int N, int
                                           void* stream);
 
 
+/* The same up-sampling for any integer scale S >= 1 (the DeepLab v3+ decoder's F.interpolate(y, size=..., mode=
+ * "bilinear", align_corners=False), projects/DeepLab/deeplab/semantic_seg.py:248, from stride 16 to stride 4):
+ * y (N,S*H,S*W,C) <- x (N,H,W,C), C % 4 == 0, ATen's association of the four taps; the backward is a gather over the
+ * <= 2S x 2S outputs that sample a source pixel (no atomics: the same bits on every run). */
+int jtsm_upsample_bilinear_forward_f32(const float* x, float* y, int N, int H, int W, int C, int S, void* stream);
+int jtsm_upsample_bilinear_backward_f32(const float* gy, float* gx, int N, int H, int W, int C, int S, void* stream);
+
 /* Fused "bilinear xS up-sampling (align_corners=False) + cross_entropy(mean, ignore_index)" of
  * SemSegFPNHead.losses (detectron2/modeling/meta_arch/semantic_seg.py:179-188): the full-resolution
  * logits are never materialised.  logits: (N,Hs,Ws,ld) NHWC, 16-byte aligned, with C <= ld <= 64 classes and
@@ -806,6 +814,67 @@ int jtsm_semseg_ce_backward_f32(const float* logits, int ld, int C, const int64_
                                 const float* fwd_out, const float* upstream, float* dlogits,
                                 const void* workspace, int N, int Hs, int Ws, int S, long ignore_index,
                                 void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Trainable batch norm behind a convolution (replaces torch.nn.BatchNorm2d / nn.SyncBatchNorm / NaiveSyncBatchNorm as
+ * get_norm hands them out, detectron2/layers/batch_norm.py:128-153, applied by Conv2d.forward, wrappers.py:79-82, and
+ * the bottleneck's `out += shortcut; relu`, resnet.py:203-210).  Maps are channels-last fp32: R = N*H*W rows of C
+ * channels; x has a leading dimension ld >= C (a [:, :C] slice of a wider map), every other map is dense.  float4
+ * accesses are used where C, ld and the pointers allow, scalar ones otherwise: any C works.
+ *   stats           mean[c] and m2[c] = sum (x - mean)^2 over the R rows.  Each workgroup forms (count, mean, M2) of its
+ *                   rows from sums shifted by a value of the data and the partials are combined by the pairwise update in
+ *                   fp64 in a fixed order: no cancellation on a map whose mean is large against its spread, no
+ *                   floating-point atomics, the same bits on every run.  With invstd given (single-process form) the
+ *                   call also does what `finalize` does with count = R.
+ *   finalize        invstd = 1 / sqrt(m2 / count + eps); running_mean / running_var (nullable) <- (1 - momentum) * old
+ *                   + momentum * (mean | m2 / (count - 1)), as torch.nn.BatchNorm2d updates them.  A multi-process run
+ *                   all-reduces (count, mean, m2) between `stats` and this call.
+ *   apply           y = relu?((x - mean) * invstd * gamma + beta (+ residual)), one pass; residual nullable.
+ *   backward_reduce sum_dy[c] = sum g, sum_dy_xhat[c] = sum g * xhat with g = dy, gated by y > 0 where relu != 0 (y may
+ *                   be NULL otherwise): dbeta and dgamma.  A multi-process run all-reduces the two vectors here.
+ *   backward_apply  dx = gamma * invstd * (g - sum_dy / count - xhat * sum_dy_xhat / count); dresidual (nullable) = g.
+ * workspace: jtsm_batch_norm_workspace_bytes(R, C) for stats and backward_reduce.
+ * ------------------------------------------------------------------------- */
+size_t jtsm_batch_norm_workspace_bytes(long R, int C);
+int jtsm_batch_norm_stats_f32(const float* x, long ld, long R, int C, float* mean, float* m2, float eps, float momentum,
+                              float* invstd, float* running_mean, float* running_var, void* workspace, void* stream);
+int jtsm_batch_norm_finalize_f32(const float* mean, const float* m2, double count, int C, float eps, float momentum,
+                                 float* invstd, float* running_mean, float* running_var, void* stream);
+int jtsm_batch_norm_apply_f32(const float* x, long ld, const float* residual, const float* mean, const float* invstd,
+                              const float* gamma, const float* beta, float* y, long R, int C, int relu, void* stream);
+int jtsm_batch_norm_backward_reduce_f32(const float* x, long ld, const float* dy, const float* y, const float* mean,
+                                        const float* invstd, float* sum_dy, float* sum_dy_xhat, void* workspace, long R,
+                                        int C, int relu, void* stream);
+int jtsm_batch_norm_backward_apply_f32(const float* x, long ld, const float* dy, const float* y, const float* mean,
+                                       const float* invstd, const float* gamma, const float* sum_dy,
+                                       const float* sum_dy_xhat, double count, float* dx, float* dresidual, long R, int C,
+                                       int relu, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * DeepLabCE, hard-pixel-mining cross-entropy (projects/DeepLab/deeplab/loss.py:6-40) of the bilinearly xS up-sampled
+ * logits (F.interpolate(..., scale_factor=common_stride, mode="bilinear", align_corners=False) in the losses() of
+ * projects/DeepLab/deeplab/semantic_seg.py), the full-resolution logits never materialised.  Limits and layout of
+ * jtsm_semseg_ce_*: logits (N,Hs,Ws,ld) NHWC, 16-byte aligned, C <= ld <= 64, ld % 4 == 0; target (N,Hs*S,Ws*S) int64.
+ * forward: lse and pixel_loss (one float per output pixel; the loss is 0 where the target is ignored and is multiplied
+ * by weights[pixel] where weights != NULL); out[0] = mean of the k largest pixel losses = (sum of the losses above the
+ * cut t + (k - their number) * t) / k with fp64 sums in a fixed order, out[1] = t.  k is the caller's
+ * int(top_k_percent_pixels * pixels), 1 <= k <= pixels, ignored pixels counted; k = pixels is the mean over ALL pixels.
+ * The cut is found by a radix select over 8-bit digits of a key that orders every float (-0 = +0, NaN largest: a NaN
+ * loss gives a NaN result, as torch.topk), with per-workgroup LDS histograms; the workspace,
+ * jtsm_deeplab_ce_workspace_bytes(), does not depend on the sizes.
+ * TIES AT THE CUT: among the pixels whose loss equals t, those with the LOWER FLAT INDEX (n, h, w) are chosen first (the
+ * reference's topk leaves this open; the same rule as jtsm_retinanet_candidates_f32).
+ * coef (one float per output pixel) = chosen * weight / k, 0 for ignored pixels: the backward's per-pixel factor.
+ * backward: the deterministic gather of jtsm_semseg_ce_backward_f32 with coef in place of the one upstream scalar;
+ * dlogits (N,Hs,Ws,ld) = *upstream (1 if NULL) * d out[0] / d logits, pad lanes zero.
+ * ------------------------------------------------------------------------- */
+size_t jtsm_deeplab_ce_workspace_bytes(void);
+int jtsm_deeplab_ce_forward_f32(const float* logits, int ld, int C, const int64_t* target, const float* weights, long k,
+                                float* lse, float* pixel_loss, float* coef, float* out, void* workspace, int N, int Hs,
+                                int Ws, int S, long ignore_index, void* stream);
+int jtsm_deeplab_ce_backward_f32(const float* logits, int ld, int C, const int64_t* target, const float* lse,
+                                 const float* coef, const float* upstream, float* dlogits, int N, int Hs, int Ws, int S,
+                                 long ignore_index, void* stream);
 
 
 /* ---------------------------------------------------------------------------

@@ -236,9 +236,11 @@ class CfgNode(dict):
 
 def get_cfg():
     """A fresh copy of the defaults (detectron2/config/config.py:76-86), with the WSL keys added
-    (projects/WSL/wsl/config/defaults.py:7-73) since this package exists for that project."""
-    from .defaults import _C, add_wsl_config
+    (projects/WSL/wsl/config/defaults.py:7-73) since this package exists for that project, and the DeepLab keys
+    (projects/DeepLab/deeplab/config.py:5-28), which add to the defaults and change none."""
+    from .defaults import _C, add_deeplab_config, add_wsl_config
 
     cfg = _C.clone()
     add_wsl_config(cfg)
+    add_deeplab_config(cfg)
     return cfg

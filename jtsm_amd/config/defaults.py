@@ -94,9 +94,26 @@ _WSL_DEFAULTS = {
               "SEM_SEG_HEAD": {"MASK_SOFTMAX": False, "CONSTRAINT": False}},
 }
 
+# projects/DeepLab/deeplab/config.py:5-28 (add_deeplab_config), plus the keys of detectron2/config/defaults.py the
+# DeepLab configs set and the heads read: INPUT.CROP (:62-72) and SOLVER.LR_SCHEDULER_NAME (:513; there is no LR scheduler
+# here: "WarmupPolyLR" is accepted as a value and nothing reads it)
+_DEEPLAB_DEFAULTS = {
+    "INPUT": {"CROP": {"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9], "SINGLE_CATEGORY_MAX_AREA": 1.0}},
+    "SOLVER": {"LR_SCHEDULER_NAME": "WarmupMultiStepLR", "POLY_LR_POWER": 0.9, "POLY_LR_CONSTANT_ENDING": 0.0},
+    "MODEL": {"SEM_SEG_HEAD": {"LOSS_TYPE": "hard_pixel_mining", "PROJECT_FEATURES": ["res2"], "PROJECT_CHANNELS": [48],
+                               "ASPP_CHANNELS": 256, "ASPP_DILATIONS": [6, 12, 18], "ASPP_DROPOUT": 0.1,
+                               "USE_DEPTHWISE_SEPARABLE_CONV": False},
+              "RESNETS": {"RES4_DILATION": 1, "RES5_MULTI_GRID": [1, 2, 4], "STEM_TYPE": "deeplab"}},
+}
+
 _C = CN(_DEFAULTS)
 
 
 def add_wsl_config(cfg):
     """Add the project keys of projects/WSL (add_wsl_config there) to a config node in place."""
     cfg.merge_from_other_cfg(CN(_WSL_DEFAULTS))
+
+
+def add_deeplab_config(cfg):
+    """Add the project keys of projects/DeepLab (add_deeplab_config there) to a config node in place: new keys only."""
+    cfg.merge_from_other_cfg(CN(_DEEPLAB_DEFAULTS))

@@ -282,32 +282,55 @@ __global__ __launch_bounds__(256) void maxpool3s2_fwd(const float4* __restrict__
     y[i] = m;
   }
 }
-// backward: recompute the first maximum of each window and add the gradient there
+// backward as a gather: an input pixel lies in at most 2 x 2 windows (rows 2*oh - 1 .. 2*oh + 1); for each of them the
+// first maximum is recomputed, and where it is this pixel the window's gradient is added — in window order, so the sum
+// is the same bits on every run (a scatter with float atomics is not: a backbone trained from its first layer runs this).
+// V channels per thread (4 as one float4 where C % 4 == 0).
+template <int V>
 __global__ __launch_bounds__(256) void maxpool3s2_bwd(const float* __restrict__ x,
                                                       const float* __restrict__ gy,
                                                       float* __restrict__ gx, int N, int H, int W,
                                                       int C, int Ho, int Wo) {
-  const long total = (long)N * Ho * Wo * C;
+  const int CV = C / V;
+  const long total = (long)N * H * W * CV;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C);
-    long t = i / C;
-    const int ow = (int)(t % Wo); t /= Wo;
-    const int oh = (int)(t % Ho);
-    const int n = (int)(t / Ho);
-    float m = -FLT_MAX;
-    long at = -1;
-    for (int kh = 0; kh < 3; ++kh) {
-      const int ih = oh * 2 - 1 + kh;
-      if ((unsigned)ih >= (unsigned)H) continue;
-      for (int kw = 0; kw < 3; ++kw) {
-        const int iw = ow * 2 - 1 + kw;
-        if ((unsigned)iw >= (unsigned)W) continue;
-        const long o = ((long)(n * H + ih) * W + iw) * C + c;
-        const float v = x[o];
-        if (v > m || at < 0) { m = v; at = o; }
+    const int c = (int)(i % CV) * V;
+    long t = i / CV;
+    const int w = (int)(t % W); t /= W;
+    const int h = (int)(t % H);
+    const int n = (int)(t / H);
+    float acc[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    for (int oh = h / 2; oh <= (h + 1) / 2 && oh < Ho; ++oh)
+      for (int ow = w / 2; ow <= (w + 1) / 2 && ow < Wo; ++ow) {
+        float m[V];
+        int at[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) { m[e] = -FLT_MAX; at[e] = -1; }
+        for (int kh = 0; kh < 3; ++kh) {
+          const int ih = oh * 2 - 1 + kh;
+          if ((unsigned)ih >= (unsigned)H) continue;
+          for (int kw = 0; kw < 3; ++kw) {
+            const int iw = ow * 2 - 1 + kw;
+            if ((unsigned)iw >= (unsigned)W) continue;
+            const float* p = x + ((long)(n * H + ih) * W + iw) * C + c;
+            float v[V];
+            if (V == 4) { const float4 q = *reinterpret_cast<const float4*>(p); v[0] = q.x; v[1 % V] = q.y; v[2 % V] = q.z; v[3 % V] = q.w; }
+            else v[0] = *p;
+#pragma unroll
+            for (int e = 0; e < V; ++e)
+              if (v[e] > m[e] || at[e] < 0) { m[e] = v[e]; at[e] = kh * 3 + kw; }
+          }
+        }
+        const int mine = (h - (oh * 2 - 1)) * 3 + (w - (ow * 2 - 1));
+        const float* g = gy + ((long)(n * Ho + oh) * Wo + ow) * C + c;
+#pragma unroll
+        for (int e = 0; e < V; ++e)
+          if (at[e] == mine) acc[e] += g[e];
       }
-    }
-    if (at >= 0) atomicAdd(gx + at, gy[i]);
+#pragma unroll
+    for (int e = 0; e < V; ++e) gx[i * V + e] = acc[e];
   }
 }
 
@@ -761,9 +784,13 @@ int jtsm_maxpool3x3s2_backward_f32(const float* x, const float* gy, float* gx, i
   hipStream_t st = as_stream(stream);
   if ((long)N * H * W * C == 0) return JTSM_OK;
   JTSM_REQUIRE(x && gy && gx, "maxpool backward: null pointer");
-  JTSM_CHECK_HIP(hipMemsetAsync(gx, 0, (size_t)N * H * W * C * sizeof(float), st));
-  const long total = (long)N * Ho * Wo * C;
-  hipLaunchKernelGGL(maxpool3s2_bwd, dim3(grid_for(total)), dim3(256), 0, st, x, gy, gx, N, H, W, C, Ho, Wo);
+  if (C % 4 == 0 && ((uintptr_t)x & 15) == 0) {
+    const long total = (long)N * H * W * (C / 4);
+    hipLaunchKernelGGL(maxpool3s2_bwd<4>, dim3(grid_for(total)), dim3(256), 0, st, x, gy, gx, N, H, W, C, Ho, Wo);
+  } else {
+    const long total = (long)N * H * W * C;
+    hipLaunchKernelGGL(maxpool3s2_bwd<1>, dim3(grid_for(total)), dim3(256), 0, st, x, gy, gx, N, H, W, C, Ho, Wo);
+  }
   JTSM_CHECK_LAUNCH("maxpool backward");
   return JTSM_OK;
 }

@@ -4,6 +4,7 @@
 // them as ATen ops on NCHW tensors; here they stay channels-last (one float4 = 4 channels of a pixel),
 // ReLU is folded into the normalisation pass, and every reduction is two-stage with a fixed fold order
 // (no float atomics -> deterministic).
+#include "bilinear_ce.h"
 #include "common.h"
 #include "planes.h"
 #include "reduce.h"
@@ -221,20 +222,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
   }
 }
 
-// ---- bilinear xS (align_corners = False): src coordinate of dst o is (o + 0.5) / S - 0.5 clamped at 0; taps i0, i1
-// with weights l0 = 1 - l1, l1.  x2: inv_scale = 0.5, i.e. o/2 - 0.25 -----------
-struct Lerp { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Lerp lerp_scale(int o, int n_src, float inv_scale) {
-  float s = ((float)o + 0.5f) * inv_scale - 0.5f;
-  if (s < 0.f) s = 0.f;
-  Lerp r;
-  r.i0 = (int)s;
-  r.i1 = r.i0 < n_src - 1 ? r.i0 + 1 : r.i0;
-  r.l1 = s - (float)r.i0;
-  r.l0 = 1.f - r.l1;
-  return r;
-}
-
+// ---- bilinear xS (align_corners = False): lerp_scale, bilinear_ce.h -----------
 #ifdef JTSM_DIAG_UP2   // diagnostic build: the kernel checks itself (second look at its operands past the caches,
                        // second evaluation one product at a time) and books what it finds
 __device__ unsigned int g_up2_diag[8 + 64 * 40];
@@ -406,6 +394,70 @@ __global__ __launch_bounds__(256) void up2_bwd_kernel(const float* __restrict__ 
 }
 
 
+// ---- bilinear xS for any integer S (the DeepLab v3+ decoder brings the ASPP map from stride 16 to stride 4:
+// F.interpolate(y, size=proj_x.size()[2:], mode="bilinear", align_corners=False), projects/DeepLab/deeplab/
+// semantic_seg.py:248).  Forward as up2_fwd_kernel without the planes; backward as a gather over the <= 2S x 2S
+// destination pixels that sample a source pixel (ATen's backward scatters with atomics: not reproducible).
+__global__ __launch_bounds__(256) void ups_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H,
+                                                      int W, int C4, int S, long total4) {
+  const int Ho = S * H, Wo = S * W;
+  const float inv = 1.f / (float)S;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C4);
+    long t = i / C4;
+    const int ow = (int)(t % Wo); t /= Wo;
+    const int oh = (int)(t % Ho);
+    const int n = (int)(t / Ho);
+    const Lerp a = lerp_scale(oh, H, inv), b = lerp_scale(ow, W, inv);
+    const float* base = x + (size_t)n * H * W * C4 * 4;
+    const float4 v00 = ld4(base + ((size_t)(a.i0 * W + b.i0) * C4 + c) * 4);
+    const float4 v01 = ld4(base + ((size_t)(a.i0 * W + b.i1) * C4 + c) * 4);
+    const float4 v10 = ld4(base + ((size_t)(a.i1 * W + b.i0) * C4 + c) * 4);
+    const float4 v11 = ld4(base + ((size_t)(a.i1 * W + b.i1) * C4 + c) * 4);
+    float4 o;   // ATen's association
+    o.x = a.l0 * (b.l0 * v00.x + b.l1 * v01.x) + a.l1 * (b.l0 * v10.x + b.l1 * v11.x);
+    o.y = a.l0 * (b.l0 * v00.y + b.l1 * v01.y) + a.l1 * (b.l0 * v10.y + b.l1 * v11.y);
+    o.z = a.l0 * (b.l0 * v00.z + b.l1 * v01.z) + a.l1 * (b.l0 * v10.z + b.l1 * v11.z);
+    o.w = a.l0 * (b.l0 * v00.w + b.l1 * v01.w) + a.l1 * (b.l0 * v10.w + b.l1 * v11.w);
+    st4(y + i * 4, o);
+  }
+}
+
+__device__ __forceinline__ float weight_at(int o, int n_src, int i, float inv) {
+  const Lerp r = lerp_scale(o, n_src, inv);
+  return (r.i0 == i ? r.l0 : 0.f) + (r.i1 == i ? r.l1 : 0.f);
+}
+__global__ __launch_bounds__(256) void ups_bwd_kernel(const float* __restrict__ gy, float* __restrict__ gx, int N,
+                                                      int H, int W, int C4, int S, long total4) {
+  const int Ho = S * H, Wo = S * W;
+  const float inv = 1.f / (float)S;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C4);
+    long t = i / C4;
+    const int w = (int)(t % W); t /= W;
+    const int h = (int)(t % H);
+    const int n = (int)(t / H);
+    const float* base = gy + (size_t)n * Ho * Wo * C4 * 4;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    // rows / columns of the output that can put weight on (h, w): exact for even S, one spare each side for odd S
+    const int oh0 = max(S * h - (S + 1) / 2, 0), oh1 = min(S * h + S + (S + 1) / 2, Ho);
+    const int ow0 = max(S * w - (S + 1) / 2, 0), ow1 = min(S * w + S + (S + 1) / 2, Wo);
+    for (int oh = oh0; oh < oh1; ++oh) {
+      const float wy = weight_at(oh, H, h, inv);
+      if (wy == 0.f) continue;
+      for (int ow = ow0; ow < ow1; ++ow) {
+        const float wx = weight_at(ow, W, w, inv);
+        if (wx == 0.f) continue;
+        const float4 g = ld4(base + ((size_t)(oh * Wo + ow) * C4 + c) * 4);
+        const float ww = wy * wx;
+        acc.x += ww * g.x; acc.y += ww * g.y; acc.z += ww * g.z; acc.w += ww * g.w;
+      }
+    }
+    st4(gx + i * 4, acc);
+  }
+}
+
+
 // ---- fused bilinear xS up-sampling + softmax cross-entropy (semantic_seg.py:179-188) ------------------
 // The reference materialises the (N, 54, H, W) up-sampled logits (226 MB per 1024^2 image), then
 // log_softmax, then nll_loss — ~0.7 GB of HBM traffic per image forward+backward.  Here the full-resolution
@@ -431,49 +483,14 @@ __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const float* __restrict_
   const int H = Hs * S, W = Ws * S;
   const long npix = (long)N * H * W;
   const float inv = 1.f / (float)S;
-  const int nch = ldc >> 2;   // float4 chunks per pixel row (ldc % 4 == 0, <= 16)
   float loss = 0.f, cnt = 0.f;
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long)gridDim.x * blockDim.x) {
     const long t = target[p];
     const int ow = (int)(p % W);
     const long q = p / W;
     const int oh = (int)(q % H), n = (int)(q / H);
-    const Lerp a = lerp_scale(oh, Hs, inv), b = lerp_scale(ow, Ws, inv);
-    const float* zn = z + (size_t)n * Hs * Ws * ldc;
-    const float4* p00 = reinterpret_cast<const float4*>(zn + ((size_t)a.i0 * Ws + b.i0) * ldc);
-    const float4* p01 = reinterpret_cast<const float4*>(zn + ((size_t)a.i0 * Ws + b.i1) * ldc);
-    const float4* p10 = reinterpret_cast<const float4*>(zn + ((size_t)a.i1 * Ws + b.i0) * ldc);
-    const float4* p11 = reinterpret_cast<const float4*>(zn + ((size_t)a.i1 * Ws + b.i1) * ldc);
-    float v[64];
-    float mx = -3.0e38f, vt = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      if (j < nch) {
-        const float4 v00 = p00[j], v01 = p01[j], v10 = p10[j], v11 = p11[j];
-        const float x00[4] = {v00.x, v00.y, v00.z, v00.w}, x01[4] = {v01.x, v01.y, v01.z, v01.w};
-        const float x10[4] = {v10.x, v10.y, v10.z, v10.w}, x11[4] = {v11.x, v11.y, v11.z, v11.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = 4 * j + e;
-          float x = a.l0 * (b.l0 * x00[e] + b.l1 * x01[e]) + a.l1 * (b.l0 * x10[e] + b.l1 * x11[e]);   // ATen's association
-          if (c >= C) x = -3.0e38f;
-          v[c] = x;
-          mx = fmaxf(mx, x);
-          vt = (long)c == t ? x : vt;
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[4 * j + e] = -3.0e38f;
-      }
-    }
-    float sm = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-      if (j < nch) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sm += __expf(v[4 * j + e] - mx);
-      }
-    const float l = mx + __logf(sm);
+    float vt;
+    const float l = ce_pixel_lse(z, ldc, C, n, oh, ow, Hs, Ws, inv, t, vt);
     lse[p] = l;
     if (t != ignore) {
       loss += l - vt;
@@ -506,9 +523,6 @@ __global__ __launch_bounds__(256) void ce_finish_kernel(const float* __restrict_
   }
 }
 
-// l0 * a + l1 * b with the contraction spelled out: the two backward forms below must round alike
-__device__ __forceinline__ float mix2(float l0, float a, float l1, float b) { return __fmaf_rn(l0, a, l1 * b); }
-
 // dz[n,h,w,c] = up/count * sum over output pixels o touching (h,w) of weight(o -> (h,w)) * (softmax_o[c] - [c == t_o])
 // A gather (no atomics, deterministic): 16 lanes per source pixel, one float4 of channels per lane.  For one
 // output column the three source rows h-1, h, h+1 are interpolated along x once and reused by all of that
@@ -519,7 +533,6 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const float* __restrict_
                                                         const float* __restrict__ upstream, float* __restrict__ dz,
                                                         int N, int Hs, int Ws, int S, long ignore) {
   const int j = threadIdx.x & 15;
-  const int H = Hs * S, W = Ws * S;
   const long nsrc = (long)N * Hs * Ws;
   const float inv = 1.f / (float)S;
   const float k = (upstream ? *upstream : 1.f) / fin[1];
@@ -530,44 +543,8 @@ __global__ __launch_bounds__(256) void ce_up_bwd_kernel(const float* __restrict_
     const int w = (int)(p % Ws);
     const long q = p / Ws;
     const int h = (int)(q % Hs), n = (int)(q / Hs);
-    const float* zn = z + (size_t)n * Hs * Ws * ldc + c0;
-    const int hm = max(h - 1, 0), hp = min(h + 1, Hs - 1);
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    // rows / columns of the output that can put weight on (h, w): exact for even S, one spare each side for odd S
-    const int oh0 = max(S * h - (S + 1) / 2, 0), oh1 = min(S * h + S + (S + 1) / 2, H);
-    const int ow0 = max(S * w - (S + 1) / 2, 0), ow1 = min(S * w + S + (S + 1) / 2, W);
-    for (int ow = ow0; ow < ow1; ++ow) {
-      const Lerp b = lerp_scale(ow, Ws, inv);
-      const float wx = (b.i0 == w ? b.l0 : 0.f) + (b.i1 == w ? b.l1 : 0.f);
-      if (wx == 0.f) continue;
-      float r[3][4];   // x-interpolated logits of source rows h-1, h, h+1 at this output column
-      const int rows[3] = {hm, h, hp};
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const float4 u0 = *reinterpret_cast<const float4*>(zn + ((size_t)rows[i] * Ws + b.i0) * ldc);
-        const float4 u1 = *reinterpret_cast<const float4*>(zn + ((size_t)rows[i] * Ws + b.i1) * ldc);
-        r[i][0] = mix2(b.l0, u0.x, b.l1, u1.x); r[i][1] = mix2(b.l0, u0.y, b.l1, u1.y);
-        r[i][2] = mix2(b.l0, u0.z, b.l1, u1.z); r[i][3] = mix2(b.l0, u0.w, b.l1, u1.w);
-      }
-      for (int oh = oh0; oh < oh1; ++oh) {
-        const Lerp a = lerp_scale(oh, Hs, inv);
-        const float wy = (a.i0 == h ? a.l0 : 0.f) + (a.i1 == h ? a.l1 : 0.f);
-        if (wy == 0.f) continue;
-        const long o = ((long)n * H + oh) * W + ow;
-        const long t = target[o];
-        if (t == ignore) continue;
-        const float l = lse[o], wgt = wy * wx;
-        const bool lo0 = a.i0 < h, hi0 = a.i0 > h, lo1 = a.i1 < h, hi1 = a.i1 > h;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float t0 = lo0 ? r[0][e] : (hi0 ? r[2][e] : r[1][e]);
-          const float t1 = lo1 ? r[0][e] : (hi1 ? r[2][e] : r[1][e]);
-          const float v = mix2(a.l0, t0, a.l1, t1);
-          const float pr = c0 + e < C ? __expf(v - l) : 0.f;
-          acc[e] = __fmaf_rn(wgt, pr - ((long)(c0 + e) == t ? 1.f : 0.f), acc[e]);
-        }
-      }
-    }
+    float acc[4];
+    ce_gather_source<false>(z, ldc, C, target, lse, nullptr, n, h, w, c0, Hs, Ws, S, inv, ignore, acc);
     *reinterpret_cast<float4*>(dz + (size_t)p * ldc + c0) =
         make_float4(c0 + 0 < C ? acc[0] * k : 0.f, c0 + 1 < C ? acc[1] * k : 0.f, c0 + 2 < C ? acc[2] * k : 0.f,
                     c0 + 3 < C ? acc[3] * k : 0.f);
@@ -833,6 +810,30 @@ int jtsm_upsample_bilinear2x_backward_f32(const float* gy, float* gx, int N, int
   hipLaunchKernelGGL(up2_bwd_kernel, dim3(grid_for(total4)), dim3(256), 0, as_stream(stream), gy, gx, N, H, W,
                      C / 4, total4);
   JTSM_CHECK_LAUNCH("upsample2x backward");
+  return JTSM_OK;
+}
+
+int jtsm_upsample_bilinear_forward_f32(const float* x, float* y, int N, int H, int W, int C, int S, void* stream) {
+  JTSM_REQUIRE(N >= 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && S >= 1 && (long)S * H < (1L << 30) &&
+               (long)S * W < (1L << 30), "upsample_bilinear: bad sizes (C %% 4 == 0, integer scale >= 1)");
+  const long total4 = (long)N * S * H * S * W * (C / 4);
+  if (total4 == 0) return JTSM_OK;
+  JTSM_REQUIRE(x && y, "upsample_bilinear: null pointer");
+  hipLaunchKernelGGL(ups_fwd_kernel, dim3(grid_for(total4)), dim3(256), 0, as_stream(stream), x, y, N, H, W, C / 4, S,
+                     total4);
+  JTSM_CHECK_LAUNCH("upsample_bilinear forward");
+  return JTSM_OK;
+}
+
+int jtsm_upsample_bilinear_backward_f32(const float* gy, float* gx, int N, int H, int W, int C, int S, void* stream) {
+  JTSM_REQUIRE(N >= 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && S >= 1 && (long)S * H < (1L << 30) &&
+               (long)S * W < (1L << 30), "upsample_bilinear backward: bad sizes (C %% 4 == 0, integer scale >= 1)");
+  const long total4 = (long)N * H * W * (C / 4);
+  if (total4 == 0) return JTSM_OK;
+  JTSM_REQUIRE(gy && gx, "upsample_bilinear backward: null pointer");
+  hipLaunchKernelGGL(ups_bwd_kernel, dim3(grid_for(total4)), dim3(256), 0, as_stream(stream), gy, gx, N, H, W, C / 4, S,
+                     total4);
+  JTSM_CHECK_LAUNCH("upsample_bilinear backward");
   return JTSM_OK;
 }
 

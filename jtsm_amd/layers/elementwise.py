@@ -347,26 +347,63 @@ def upsample_bilinear2x(x):
     return _UpBilinear2x.apply(x)
 
 
+class _UpBilinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale):
+        x = _cl4(x)
+        n, c, h, w = x.shape
+        y = torch.empty((n, c, scale * h, scale * w), dtype=x.dtype, device=x.device, memory_format=CL)
+        L.note_bytes(4.0 * (x.numel() + y.numel()))
+        L.check(L.lib().jtsm_upsample_bilinear_forward_f32(L.ptr(x), L.ptr(y), n, h, w, c, scale, L.stream()),
+                "upsample_bilinear")
+        ctx.cfg = (n, c, h, w, scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        n, c, h, w, scale = ctx.cfg
+        gy = gy.contiguous(memory_format=CL)
+        gx = torch.empty((n, c, h, w), dtype=gy.dtype, device=gy.device, memory_format=CL)
+        L.note_bytes(4.0 * (gx.numel() + gy.numel()))
+        L.check(L.lib().jtsm_upsample_bilinear_backward_f32(L.ptr(gy), L.ptr(gx), n, h, w, c, scale, L.stream()),
+                "upsample_bilinear backward")
+        return gx, None
+
+
+def upsample_bilinear(x, scale):
+    """F.interpolate(x, scale_factor=scale, mode="bilinear", align_corners=False) for an integer scale, channels_last,
+    with a deterministic (gather) backward."""
+    if int(scale) != scale or scale < 1:
+        raise ValueError("upsample_bilinear: integer scale >= 1, got %r" % (scale,))
+    return x if scale == 1 else _UpBilinear.apply(x, int(scale))
+
+
+def _ce_operands(logits, target, scale):
+    """(logits as pitched channels-last rows the fused CE kernels can read, their pitch, int64 target)."""
+    L.require_gpu(logits, target)
+    n, c, hs, ws = logits.shape
+    # channels-last storage with an arbitrary channel pitch (a [:, :54] slice of a 56-wide map is fine)
+    if not (logits.stride(1) == 1 and logits.stride(3) >= c and logits.stride(2) == ws * logits.stride(3)
+            and logits.stride(0) == hs * logits.stride(2)):
+        logits = logits.contiguous(memory_format=CL)
+    if logits.stride(3) % 4 or logits.data_ptr() % 16:
+        # the kernels read float4 rows: re-pitch to a multiple of 4 channels (padding is never read as a class)
+        ld4 = (c + 3) // 4 * 4
+        padded = torch.zeros((n, hs, ws, ld4), dtype=logits.dtype, device=logits.device)
+        padded[..., :c] = logits.permute(0, 2, 3, 1)
+        logits = padded.permute(0, 3, 1, 2)[:, :c]
+    target = target.to(torch.int64).contiguous()
+    if tuple(target.shape) != (n, hs * scale, ws * scale):
+        raise RuntimeError("semseg_ce: target %s is not %dx the logits %s" % (tuple(target.shape), scale,
+                                                                               tuple(logits.shape)))
+    return logits, logits.stride(3), target
+
+
 class _SemSegCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, scale, ignore_index):
-        L.require_gpu(logits, target)
+        logits, ld, target = _ce_operands(logits, target, scale)
         n, c, hs, ws = logits.shape
-        # channels-last storage with an arbitrary channel pitch (a [:, :54] slice of a 56-wide map is fine)
-        if not (logits.stride(1) == 1 and logits.stride(3) >= c and logits.stride(2) == ws * logits.stride(3)
-                and logits.stride(0) == hs * logits.stride(2)):
-            logits = logits.contiguous(memory_format=CL)
-        if logits.stride(3) % 4 or logits.data_ptr() % 16:
-            # the kernels read float4 rows: re-pitch to a multiple of 4 channels (padding is never read as a class)
-            ld4 = (c + 3) // 4 * 4
-            padded = torch.zeros((n, hs, ws, ld4), dtype=logits.dtype, device=logits.device)
-            padded[..., :c] = logits.permute(0, 2, 3, 1)
-            logits = padded.permute(0, 3, 1, 2)[:, :c]
-        ld = logits.stride(3)
-        target = target.to(torch.int64).contiguous()
-        if tuple(target.shape) != (n, hs * scale, ws * scale):
-            raise RuntimeError("semseg_ce: target %s is not %dx the logits %s" % (tuple(target.shape), scale,
-                                                                                   tuple(logits.shape)))
         lib = L.lib()
         out = torch.empty(2, dtype=torch.float32, device=logits.device)
         wsb = torch.empty(lib.jtsm_semseg_ce_workspace_bytes(n, hs, ws, scale), dtype=torch.uint8, device=logits.device)
@@ -398,3 +435,55 @@ def semseg_cross_entropy(logits, target, scale=4, ignore_index=255):
     """F.cross_entropy(F.interpolate(logits, scale_factor=scale, mode="bilinear", align_corners=False),
     target, reduction="mean", ignore_index=ignore_index) without materialising the up-sampled logits."""
     return _SemSegCE.apply(logits, target, int(scale), int(ignore_index))
+
+
+class _DeepLabCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, weights, scale, ignore_index, k):
+        logits, ld, target = _ce_operands(logits, target, scale)
+        n, c, hs, ws = logits.shape
+        dev, lib = logits.device, L.lib()
+        if weights is not None:
+            L.require_gpu(weights)
+            weights = weights.to(torch.float32).expand(target.shape).contiguous()
+        maps = torch.empty((3,) + tuple(target.shape), dtype=torch.float32, device=dev)   # lse, pixel loss, coefficient
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        wsb = torch.empty(lib.jtsm_deeplab_ce_workspace_bytes(), dtype=torch.uint8, device=dev)
+        L.note_bytes(4.0 * n * hs * ws * c + (8.0 + 12.0 + 4.0 * 5) * target.numel())
+        L.check(lib.jtsm_deeplab_ce_forward_f32(L.ptr(logits), ld, c, L.ptr(target), L.ptr(weights), k, L.ptr(maps[0]),
+                                                L.ptr(maps[1]), L.ptr(maps[2]), L.ptr(out), L.ptr(wsb), n, hs, ws, scale,
+                                                ignore_index, L.stream()), "deeplab_ce_forward")
+        ctx.save_for_backward(logits, target, maps)
+        ctx.cfg = (ld, scale, ignore_index)
+        ctx.mark_non_differentiable(maps)
+        return out[0], maps
+
+    @staticmethod
+    def backward(ctx, g, _maps):
+        logits, target, maps = ctx.saved_tensors
+        ld, scale, ignore_index = ctx.cfg
+        n, c, hs, ws = logits.shape
+        dfull = torch.empty((n, hs, ws, ld), dtype=torch.float32, device=logits.device)
+        g = g.to(torch.float32).contiguous()
+        L.note_bytes(4.0 * n * hs * ws * c + 16.0 * target.numel() + 4.0 * dfull.numel())
+        L.check(L.lib().jtsm_deeplab_ce_backward_f32(L.ptr(logits), ld, c, L.ptr(target), L.ptr(maps[0]), L.ptr(maps[2]),
+                                                     L.ptr(g), L.ptr(dfull), n, hs, ws, scale, ignore_index,
+                                                     L.stream()), "deeplab_ce_backward")
+        if ld != c:
+            from .conv import ZERO_PADDED
+            setattr(dfull, ZERO_PADDED, True)   # (the kernel wrote zeros into channels c .. ld - 1)
+        return dfull.permute(0, 3, 1, 2)[:, :c], None, None, None, None, None
+
+
+def deeplab_cross_entropy(logits, target, scale, ignore_index, top_k_percent_pixels, weights=None, return_maps=False):
+    """DeepLabCE(ignore_index, top_k_percent_pixels)(F.interpolate(logits, scale_factor=scale, mode="bilinear",
+    align_corners=False), target, weights): the mean of the top k = int(top_k_percent_pixels * numel) per-pixel
+    cross-entropies (numel counts ignored pixels, whose loss is 0; 1.0: the mean over ALL pixels), without
+    materialising the up-sampled logits or sorting.  Equal losses at the cut: the lower flat index (n, h, w) first.
+    return_maps: also the (3, N, H, W) [log-sum-exp, per-pixel loss, selected * weight / k] maps of the forward."""
+    k = int(top_k_percent_pixels * target.numel())      # host doubles, as the reference forms it
+    if not 1 <= k <= target.numel():
+        raise ValueError("deeplab_cross_entropy: top_k_percent_pixels=%r of %d pixels selects %d"
+                         % (top_k_percent_pixels, target.numel(), k))
+    loss, maps = _DeepLabCE.apply(logits, target, weights, int(scale), int(ignore_index), k)
+    return (loss, maps) if return_maps else loss

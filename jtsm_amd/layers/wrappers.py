@@ -2,14 +2,15 @@
 
 ``Conv2d(*args, norm=None, activation=None)`` keeps the reference's constructor and parameter
 names (weight, bias, norm.*), but its forward is ONE launch of the fp32-MFMA implicit GEMM with the
-norm (FrozenBatchNorm2d), bias and ReLU folded into the epilogue.  Norms/activations the epilogue
-cannot express (GroupNorm, non-ReLU) run after it as separate modules, like in the reference.
+norm (FrozenBatchNorm2d, or a BatchNorm2d in evaluation mode), bias and ReLU folded into the epilogue.
+GroupNorm and a BatchNorm2d in training mode run behind it as one fused norm (+ residual) + ReLU pass; other
+norms/activations the epilogue cannot express run after it as separate modules, like in the reference.
 """
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .batch_norm import FrozenBatchNorm2d
+from .batch_norm import BatchNorm2d, FrozenBatchNorm2d
 from .conv import conv2d_fused, conv_transpose2x2_fused, conv_transpose2x2_ok, linear_fused
 
 CL = torch.channels_last
@@ -51,7 +52,10 @@ class Conv2d(nn.Conv2d):
     def forward(self, x, residual=None):
         """residual (same shape as the output) is added before the activation — the bottleneck's
         `out += shortcut; relu` (resnet.py:203-210) in the same launch."""
-        fuse_norm = isinstance(self.norm, FrozenBatchNorm2d)
+        live_bn = isinstance(self.norm, BatchNorm2d) and self.norm.training and x.is_cuda and x.dtype == torch.float32
+        # a frozen norm, or a live one in evaluation mode: the affine map of its running statistics, in the epilogue
+        fuse_norm = isinstance(self.norm, FrozenBatchNorm2d) or (isinstance(self.norm, BatchNorm2d) and
+                                                                 not self.norm.training)
         relu = _is_relu(self.activation) and (self.norm is None or fuse_norm)
         scale = bias = None
         bias_grad = False
@@ -61,14 +65,26 @@ class Conv2d(nn.Conv2d):
                 bias = bias + self.bias * scale
         elif self.bias is not None:
             bias, bias_grad = self.bias, True
-        if x.shape[1] % 4:  # RGB stem: zero-pad channels to a multiple of 4 (kernel requirement)
-            padc = 4 - x.shape[1] % 4
+        # RGB stem: zero-pad channels to a multiple of 4 (kernel requirement); of 8 where the layer trains under a live
+        # norm (a backbone trained from its first layer): from 8 input channels on the weight gradient runs on the plane
+        # kernels, which add their K slices in a fixed order — the same bits on every run
+        mult = 8 if live_bn else 4
+        if x.shape[1] % mult:
+            padc = mult - x.shape[1] % mult
             x = F.pad(x, (0, 0, 0, 0, 0, padc))
             w = F.pad(self.weight, (0, 0, 0, 0, 0, padc))
         else:
             w = self.weight
-        y = conv2d_fused(x, w, scale, bias, residual, self.stride[0], self.padding[0], self.dilation[0], relu,
-                         bias_grad, emit_dx_planes=getattr(self, "emit_dx_planes", False))
+        y = conv2d_fused(x, w, scale, bias, None if live_bn else residual, self.stride[0], self.padding[0],
+                         self.dilation[0], relu, bias_grad, emit_planes=not live_bn,   # (nothing contracts the un-normed map)
+                         emit_dx_planes=getattr(self, "emit_dx_planes", False))
+        if live_bn:
+            # a plain contraction, then batch norm over the batch (+ residual) (+ ReLU) as one pass (csrc/batch_norm.hip)
+            act_relu = _is_relu(self.activation)
+            y = self.norm.fused(y, act_relu, residual)
+            if self.activation is not None and not act_relu:
+                y = self.activation(y)
+            return y
         if isinstance(self.norm, nn.GroupNorm) and self.norm.affine and y.is_cuda and y.dtype == torch.float32:
             # GroupNorm (+ the following ReLU) as one channels-last pass (jtsm_amd/csrc/semseg_ops.hip)
             from .elementwise import group_norm_relu

@@ -3,4 +3,5 @@ from .mcnn import GeneralizedMCNNWSL
 from .rcnn import GeneralizedRCNN, PanopticFPN
 from .rcnn_wsl import GeneralizedRCNNWSL
 from .retinanet import RetinaNet, RetinaNetHead
-from .semantic_seg import SEM_SEG_HEADS_REGISTRY, SemSegFPNHead, build_sem_seg_head
+from .semantic_seg import SEM_SEG_HEADS_REGISTRY, SemanticSegmentor, SemSegFPNHead, build_sem_seg_head
+from .deeplab import DeepLabV3Head, DeepLabV3PlusHead

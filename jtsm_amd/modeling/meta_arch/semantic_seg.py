@@ -1,4 +1,6 @@
-"""SemSegFPNHead — surface of detectron2/modeling/meta_arch/semantic_seg.py:95-188.
+"""SemanticSegmentor and SemSegFPNHead — surface of detectron2/modeling/meta_arch/semantic_seg.py:27-92, 95-188.
+SemanticSegmentor: backbone -> semantic head; the loss dict in training, [{"sem_seg": C x H x W logits}] through
+sem_seg_postprocess in inference (what evaluation.SemSegEvaluator.process takes).
 Per FPN level: [conv3x3 -> GroupNorm(32) -> ReLU (-> bilinear x2)] x log2(stride/4), summed, 1x1
 predictor; loss = CE(bilinear x4 of the logits, target, ignore 255) * LOSS_WEIGHT.
 The 3x3 / 1x1 convolutions are MFMA launches, GroupNorm+ReLU and the x2 bilinear up-sampling are
@@ -14,8 +16,47 @@ from torch import nn
 from ...layers.shape_spec import ShapeSpec
 from ...layers.wrappers import Conv2d
 from ...utils.registry import Registry
+from .build import META_ARCH_REGISTRY
 
 SEM_SEG_HEADS_REGISTRY = Registry("SEM_SEG_HEADS")
+
+
+@META_ARCH_REGISTRY.register()
+class SemanticSegmentor(nn.Module):
+    def __init__(self, cfg):
+        super().__init__()
+        from ..backbone import build_backbone
+        self.backbone = build_backbone(cfg)
+        self.sem_seg_head = build_sem_seg_head(cfg, self.backbone.output_shape())
+        self.register_buffer("pixel_mean", torch.Tensor(cfg.MODEL.PIXEL_MEAN).view(-1, 1, 1))
+        self.register_buffer("pixel_std", torch.Tensor(cfg.MODEL.PIXEL_STD).view(-1, 1, 1))
+
+    @property
+    def device(self):
+        return self.pixel_mean.device
+
+    def forward(self, batched_inputs):
+        """batched_inputs: dicts with "image" (C, H, W), in training "sem_seg" (H, W), optionally the output "height" /
+        "width"."""
+        from ...layers.conv import planes_clear
+        from ...structures import ImageList
+        from ..postprocessing import sem_seg_postprocess
+        planes_clear()
+        images = [(x["image"].to(self.device) - self.pixel_mean) / self.pixel_std for x in batched_inputs]
+        images = ImageList.from_tensors(images, self.backbone.size_divisibility, channels_last=True)
+        features = self.backbone(images.tensor)
+        targets = None
+        if "sem_seg" in batched_inputs[0]:
+            targets = ImageList.from_tensors([x["sem_seg"].to(self.device) for x in batched_inputs],
+                                             self.backbone.size_divisibility, self.sem_seg_head.ignore_value).tensor
+        results, losses = self.sem_seg_head(features, targets)
+        if self.training:
+            return losses
+        out = []
+        for result, inp, size in zip(results, batched_inputs, images.image_sizes):
+            out.append({"sem_seg": sem_seg_postprocess(result, size, inp.get("height", size[0]),
+                                                       inp.get("width", size[1]))})
+        return out
 
 
 class UpsampleBilinear2x(nn.Module):
