@@ -1458,6 +1458,63 @@ int jtsm_preprocess_images_f32(const float* const* images, const int32_t* height
                                int C, const float* mean, const float* stdv, float pad_value, int Hp, int Wp,
                                float* out, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Panoptic-DeepLab (projects/Panoptic-DeepLab/panoptic_deeplab/panoptic_seg.py:536-561 center_losses / offset_losses,
+ * post_processing.py:9-234 find_instance_center / group_pixels / merge_semantic_and_instance /
+ * get_panoptic_segmentation, panoptic_seg.py:163-207 the instance rows; train_net.py:100-124 Adam).  DESIGN §4o.
+ *
+ * Losses: pred (N,Hs,Ws,ld) NHWC rows of which channels 0 .. C-1 are read (C = 1 centre, C = 2 offset), target
+ * (N,C,Hs*S,Ws*S) planar, weights (N,Hs*S,Ws*S); up = bilinear xS, align_corners = False, never materialised.
+ * kind 0: out[0] = sum((up - t)^2 * w) / sum(w); kind 1: out[0] = sum(|S * up - t| * w) / sum(w), the sum over both
+ * channels and sum(w) counting a pixel once.  out[1] = 1 / sum(w).  sum(w) <= 0: out = {0, 0} and a zero gradient.  fp64
+ * sums in a fixed order.  backward: dpred (N,Hs,Ws,ld) = *upstream (1 if NULL) * d out[0] / d pred, pad lanes zero; a
+ * gather per source pixel; coefficients 2 (up - t) w / sum(w) and S sign(S up - t) w / sum(w), sign(0) = 0. */
+size_t jtsm_pdl_loss_workspace_bytes(void);
+int jtsm_pdl_loss_forward_f32(const float* pred, int ld, int C, const float* target, const float* weights, int kind,
+                              float* out, void* workspace, int N, int Hs, int Ws, int S, void* stream);
+int jtsm_pdl_loss_backward_f32(const float* pred, int ld, int C, const float* target, const float* weights, int kind,
+                               const float* out, const float* upstream, float* dpred, int N, int Hs, int Ws, int S,
+                               void* stream);
+/* find_instance_center: x > threshold else -1; pixels that differ from their nms_kernel x nms_kernel maximum (odd,
+ * <= 31, padded as F.max_pool2d) become -1; v = the top_k-th largest value of that map over all H*W pixels; centers
+ * (top_k,2) int32 (y, x) <- the pixels strictly above max(v, 0) in row-major order (at most top_k - 1; unused rows -1),
+ * *count <- their number.  1 <= top_k <= H*W. */
+size_t jtsm_pdl_centers_workspace_bytes(int H, int W);
+int jtsm_pdl_find_centers_f32(const float* heat, int H, int W, float threshold, int nms_kernel, int top_k,
+                              int32_t* centers, int32_t* count, void* workspace, void* stream);
+/* sem (H,W) int32 <- arg-max over the C planes of logits (C,H,W), the first maximum. */
+int jtsm_pdl_argmax_f32(const float* logits, int C, int H, int W, int32_t* sem, void* stream);
+/* group_pixels: ins (H,W) int32 <- 1 + arg-min over the first min(*count, max_centers) centres of
+ * sqrtf(dy*dy + dx*dx), dy = cy - (y + offsets[0,y,x]), dx = cx - (x + offsets[1,y,x]) in fp32, the lowest index on
+ * equal distances; 0 where sem != NULL and thing_lut[sem] == 0 (thing_lut: num_classes bytes), and everywhere when
+ * there is no centre.  max_centers <= 1024. */
+int jtsm_pdl_group_pixels_f32(const int32_t* centers, const int32_t* count, int max_centers, const float* offsets,
+                              const int32_t* sem, const uint8_t* thing_lut, int num_classes, int32_t* ins, int H, int W,
+                              void* stream);
+/* merge_semantic_and_instance with the segment table.  sem, ins (H,W) int32, ins in [0, max_instances]; a pixel is a
+ * thing pixel where ins > 0 and (thing_seg != NULL ? thing_seg[p] : thing_lut[sem[p]]).  Per instance the majority
+ * class (the smallest on equal counts); ids per class from 1 in ascending instance order, instances without a pixel
+ * skipped; pan (H,W) int32 <- class * label_divisor + id on thing pixels, class * label_divisor on pixels with ins == 0
+ * of a class with thing_lut == 0 and at least max(stuff_area, 1) such pixels, void_label elsewhere; id_offset is added
+ * to every value; a class with label_divisor or more instances runs into the next class's ids, as in the reference.
+ * table (max_instances + num_classes, 5) int32 rows {id, isthing, category, instance_id (-1: stuff),
+ * area}: things in ascending instance order, then stuff in ascending class order; num[0] = rows, num[1] = thing rows.
+ * logits (C,H,W), heat (H,W), inst (max_instances, 8) float, all three or none: per thing row {x0, y0, x1 + 1, y1 + 1,
+ * mean soft-max probability of its class, heat at the truncated mean pixel, that pixel's y, x}. */
+size_t jtsm_pdl_merge_workspace_bytes(int max_instances, int num_classes);
+int jtsm_pdl_merge_f32(const int32_t* sem, const int32_t* ins, const uint8_t* thing_seg, const uint8_t* thing_lut,
+                       const float* logits, const float* heat, int max_instances, int num_classes, int H, int W,
+                       int label_divisor, int stuff_area, int void_label, int id_offset, int32_t* pan, int32_t* table,
+                       int32_t* num, float* inst, void* workspace, void* stream);
+/* torch.optim.Adam (weight decay added to the gradient, no amsgrad) over many tensors in ONE launch:
+ * g += wd * p; m += (1 - b1) (g - m); v = b2 v + (1 - b2) g g; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps).
+ * table: `entries` records of ten 64-bit words {param, grad, exp_avg, exp_avg_sq, n, first_block, and four words of
+ * two float bit patterns (low, high): (weight_decay, 1 - beta1), (beta2, 1 - beta2), (eps, lr / bias_correction1),
+ * (sqrt(bias_correction2), 0)}; a record owns ceil(n / jtsm_adam_block_elements()) consecutive workgroups,
+ * first_block is the running sum, `blocks` the total. */
+int jtsm_adam_block_elements(void);
+int jtsm_adam_multi_f32(const void* table, int entries, long blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

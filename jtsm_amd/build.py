@@ -36,9 +36,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # deform_conv.hip likewise: the bilinear sample is `w1*v1 + w2*v2 + w3*v3 + w4*v4` product by product, as tests/deform_conv_ref.py.
 # keypoint.hip likewise: target cells are `floor((x - x1) * scale)` and decoded points `(i + 0.5) * corr + x1` as the reference rounds them.
 # retinanet.hip likewise: an anchor's label is an integer decided by an IoU compared with 0.4 / 0.5 and with a per-gt maximum, so the IoU is pairwise_iou's, every step rounded.
+# panoptic_deeplab.hip likewise: which centre a pixel joins is an arg-min of `sqrtf(dy*dy + dx*dx)` with exact ties, formed as the reference's fp32 ops round it.
 # point_rend.hip likewise: which points are chosen hangs on -|logit| of a bilinear sample, formed as ATen's grid_sample rounds it.
 FILE_FLAGS = {"semseg_ops.hip": ["-fno-slp-vectorize"], "voc_eval.hip": ["-ffp-contract=off"],
-              "point_rend.hip": ["-ffp-contract=off"],
+              "point_rend.hip": ["-ffp-contract=off"], "panoptic_deeplab.hip": ["-ffp-contract=off"],
               "keypoint.hip": ["-ffp-contract=off"], "retinanet.hip": ["-ffp-contract=off"],
               "coco_eval.hip": ["-ffp-contract=off"], "cmil.hip": ["-ffp-contract=off"],
               "rotated_boxes.hip": ["-ffp-contract=off"], "deform_conv.hip": ["-ffp-contract=off"]}

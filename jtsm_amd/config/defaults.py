@@ -106,6 +106,21 @@ _DEEPLAB_DEFAULTS = {
               "RESNETS": {"RES4_DILATION": 1, "RES5_MULTI_GRID": [1, 2, 4], "STEM_TYPE": "deeplab"}},
 }
 
+# projects/Panoptic-DeepLab/panoptic_deeplab/config.py:8-51 (add_panoptic_deeplab_config)
+_PANOPTIC_DEEPLAB_DEFAULTS = {
+    "INPUT": {"GAUSSIAN_SIGMA": 10, "IGNORE_STUFF_IN_OFFSET": True, "SMALL_INSTANCE_AREA": 4096,
+              "SMALL_INSTANCE_WEIGHT": 3, "IGNORE_CROWD_IN_SEMANTIC": False},
+    "SOLVER": {"OPTIMIZER": "ADAM"},
+    "MODEL": {"SEM_SEG_HEAD": {"HEAD_CHANNELS": 256, "LOSS_TOP_K": 0.2},
+              "INS_EMBED_HEAD": {"NAME": "PanopticDeepLabInsEmbedHead", "IN_FEATURES": ["res2", "res3", "res5"],
+                                 "PROJECT_FEATURES": ["res2", "res3"], "PROJECT_CHANNELS": [32, 64],
+                                 "ASPP_CHANNELS": 256, "ASPP_DILATIONS": [6, 12, 18], "ASPP_DROPOUT": 0.1,
+                                 "HEAD_CHANNELS": 32, "CONVS_DIM": 128, "COMMON_STRIDE": 4, "NORM": "SyncBN",
+                                 "CENTER_LOSS_WEIGHT": 200.0, "OFFSET_LOSS_WEIGHT": 0.01},
+              "PANOPTIC_DEEPLAB": {"STUFF_AREA": 2048, "CENTER_THRESHOLD": 0.1, "NMS_KERNEL": 7, "TOP_K_INSTANCE": 200,
+                                   "PREDICT_INSTANCES": True, "USE_DEPTHWISE_SEPARABLE_CONV": False}},
+}
+
 _C = CN(_DEFAULTS)
 
 
@@ -117,3 +132,11 @@ def add_wsl_config(cfg):
 def add_deeplab_config(cfg):
     """Add the project keys of projects/DeepLab (add_deeplab_config there) to a config node in place: new keys only."""
     cfg.merge_from_other_cfg(CN(_DEEPLAB_DEFAULTS))
+
+
+def add_panoptic_deeplab_config(cfg):
+    """Add the project keys of projects/Panoptic-DeepLab (add_panoptic_deeplab_config there) on top of the DeepLab keys:
+    new keys only.  Not part of get_cfg(): SOLVER.OPTIMIZER = "ADAM" is this project's default, not the package's."""
+    if "LOSS_TYPE" not in cfg.MODEL.SEM_SEG_HEAD:          # (get_cfg() has added the DeepLab keys already)
+        add_deeplab_config(cfg)
+    cfg.merge_from_other_cfg(CN(_PANOPTIC_DEEPLAB_DEFAULTS))

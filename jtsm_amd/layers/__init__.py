@@ -6,6 +6,8 @@ from .deform_conv import DeformConv, ModulatedDeformConv, deform_conv, modulated
 from .mist import mine_top_p
 from .moi_pool import MOIPool, moi_pool
 from .nms import batched_nms, batched_nms_rotated, nms_rotated
+from .panoptic_deeplab import (center_loss, find_instance_center, get_instance_segmentation, get_panoptic_segmentation,
+                               group_pixels, merge_semantic_and_instance, offset_loss, panoptic_deeplab_postprocess)
 from .point_rend import (calculate_uncertainty, generate_regular_grid_point_coords, get_point_coords_wrt_image,
                          get_uncertain_point_coords_on_grid, get_uncertain_point_coords_with_randomness, point_sample,
                          point_sample_fine_grained_features, roi_mask_point_loss)

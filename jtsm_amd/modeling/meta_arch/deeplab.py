@@ -40,15 +40,20 @@ def _upsample_to(y, size):
     return resize_bilinear(y, size).contiguous(memory_format=CL)
 
 
-def _segmentation_loss(predictions, targets, common_stride, ignore_value, loss_type, loss_weight):
-    """`loss(F.interpolate(predictions, scale_factor=common_stride, "bilinear"), targets) * loss_weight`."""
+def _segmentation_loss(predictions, targets, common_stride, ignore_value, loss_type, loss_weight, top_k=0.2,
+                       weights=None):
+    """`loss(F.interpolate(predictions, scale_factor=common_stride, "bilinear"), targets) * loss_weight`; `top_k` and the
+    per-pixel `weights` are hard_pixel_mining's (DeepLabCE's top_k_percent_pixels and third argument)."""
     from ...layers.elementwise import deeplab_cross_entropy, semseg_cross_entropy
     if not (predictions.is_cuda and predictions.shape[1] <= 64 and common_stride == int(common_stride)):
         raise NotImplementedError("semantic loss: <= 64 classes, an integer stride, on the HIP device only")
     if loss_type == "cross_entropy":
+        if weights is not None:            # (the reference's nn.CrossEntropyLoss takes no third argument either)
+            raise ValueError("semantic loss: per-pixel weights need loss_type 'hard_pixel_mining', not 'cross_entropy'")
         loss = semseg_cross_entropy(predictions.float(), targets, int(common_stride), ignore_value)
     else:
-        loss = deeplab_cross_entropy(predictions.float(), targets, int(common_stride), ignore_value, 0.2)
+        loss = deeplab_cross_entropy(predictions.float(), targets, int(common_stride), ignore_value, top_k,
+                                     weights=weights)
     return {"loss_sem_seg": loss * loss_weight}
 
 

@@ -1,1 +1,1 @@
-from .build import SGD, build_optimizer  # noqa: F401
+from .build import SGD, Adam, build_optimizer  # noqa: F401

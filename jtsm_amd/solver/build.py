@@ -13,6 +13,29 @@ def _f32_bits(x):
     return struct.unpack("<I", struct.pack("<f", float(x)))[0]
 
 
+def _upload_rows(owner, staging, rows, device):
+    """The row table on the device, uploaded without stalling the host: two alternating pinned staging buffers and an
+    asynchronous copy on the launch stream; a buffer is rewritten only after the copy that last read it has finished
+    (event).  The buffers live in `owner.__dict__[staging]`."""
+    nwords = len(rows) * len(rows[0])
+    st = owner.__dict__.setdefault(staging, {"host": [None, None], "dev": None, "turn": 0, "copied": [None, None]})
+    if st["dev"] is None or st["dev"].numel() < nwords or st["dev"].device != device:
+        st["host"] = [torch.empty(nwords, dtype=torch.int64).pin_memory() for _ in range(2)]
+        st["dev"] = torch.empty(nwords, dtype=torch.int64, device=device)
+        st["copied"] = [None, None]
+    st["turn"] ^= 1
+    host = st["host"][st["turn"]]
+    if st["copied"][st["turn"]] is not None:
+        st["copied"][st["turn"]].synchronize()
+    host[:nwords].copy_(torch.tensor(rows, dtype=torch.int64).view(-1))
+    table = st["dev"][:nwords]
+    table.copy_(host[:nwords], non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    st["copied"][st["turn"]] = ev
+    return table
+
+
 class SGD(torch.optim.Optimizer):
     """torch.optim.SGD(params, lr, momentum, weight_decay) semantics (dampening 0, nesterov False); state_dict
     compatible (`momentum_buffer` per parameter)."""
@@ -126,34 +149,89 @@ class SGD(torch.optim.Optimizer):
                 blocks += (n + 1023) // 1024
                 device = p.device
         if rows:
-            # table upload without stalling the host: two alternating pinned staging buffers and an asynchronous copy on
-            # the launch stream; a buffer is rewritten only after the copy that last read it has finished (event)
-            nwords = len(rows) * 8
-            st = self.__dict__.setdefault(staging, {"host": [None, None], "dev": None, "turn": 0,
-                                                    "copied": [None, None]})
-            if st["dev"] is None or st["dev"].numel() < nwords or st["dev"].device != device:
-                st["host"] = [torch.empty(nwords, dtype=torch.int64).pin_memory() for _ in range(2)]
-                st["dev"] = torch.empty(nwords, dtype=torch.int64, device=device)
-                st["copied"] = [None, None]
-            st["turn"] ^= 1
-            host = st["host"][st["turn"]]
-            if st["copied"][st["turn"]] is not None:
-                st["copied"][st["turn"]].synchronize()
-            host[:nwords].copy_(torch.tensor(rows, dtype=torch.int64).view(-1))
-            table = st["dev"][:nwords]
-            table.copy_(host[:nwords], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            st["copied"][st["turn"]] = ev
+            table = _upload_rows(self, staging, rows, device)
             L.note_bytes(20.0 * sum(r[3] for r in rows))   # param, grad, momentum read; param, momentum written
             L.check(L.lib().jtsm_sgd_momentum_multi_f32(L.ptr(table), len(rows), blocks, 0, L.stream()),
                     "sgd_momentum_multi")
             torch.autograd.graph.increment_version(touched)   # updated behind autograd's back: say so
 
 
+class Adam(torch.optim.Optimizer):
+    """torch.optim.Adam(params, lr, betas, eps, weight_decay) semantics (L2 decay added to the gradient, amsgrad False,
+    maximize False), as projects/Panoptic-DeepLab/train_net.py:100-124 builds it; state_dict compatible (`step`,
+    `exp_avg`, `exp_avg_sq` per parameter).  Every parameter is updated in ONE launch (csrc/panoptic_deeplab.hip:
+    adam_multi_kernel); the bias corrections are formed on the host in Python doubles, as torch forms them."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay:
+            raise ValueError("Invalid Adam hyper-parameter: lr=%r eps=%r weight_decay=%r" % (lr, eps, weight_decay))
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError("Invalid beta parameters: %r" % (betas,))
+        # the keys torch.optim.Adam keeps in a group (those a newer torch adds it fills in itself when it loads a state dict)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
+                                      maximize=False, foreach=None, capturable=False, differentiable=False, fused=None))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        rows, blocks, device, keep, touched = [], 0, None, [], []
+        per_block = L.lib().jtsm_adam_block_elements()
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise NotImplementedError("jtsm_amd Adam: amsgrad and maximize are not built")
+            lr, (beta1, beta2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if not p.is_cuda or p.dtype != torch.float32:
+                    raise RuntimeError("jtsm_amd Adam updates float32 parameters on the HIP device only")
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if not isinstance(st["step"], torch.Tensor) or st["step"].is_cuda:
+                    # a loaded state may carry `step` as a number or on the device (capturable / fused checkpoints):
+                    # brought to the host once, so that no later step waits for the device
+                    st["step"] = torch.as_tensor(st["step"], dtype=torch.float32).cpu()
+                st["step"] += 1
+                step = float(st["step"])
+                m, v = st["exp_avg"], st["exp_avg_sq"]
+                if g.stride() != p.stride() or m.stride() != p.stride() or v.stride() != p.stride():
+                    if m.stride() != p.stride() or v.stride() != p.stride():
+                        raise RuntimeError("jtsm_amd Adam: the moments must be laid out as their parameter")
+                    g = torch.empty_like(p, memory_format=torch.preserve_format).copy_(g)
+                    keep.append(g)
+                bias_correction1 = 1 - beta1 ** step
+                bias_correction2 = 1 - beta2 ** step
+                pair = lambda lo, hi: _f32_bits(lo) | (_f32_bits(hi) << 32)   # noqa: E731
+                n = p.numel()
+                rows.append([p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, blocks,
+                             pair(wd, 1 - beta1), pair(beta2, 1 - beta2), pair(eps, lr / bias_correction1),
+                             pair(bias_correction2 ** 0.5, 0.0)])
+                touched += [p, m, v]
+                blocks += (n + per_block - 1) // per_block
+                device = p.device
+        if rows:
+            rows = [[w - (1 << 64) if w >= (1 << 63) else w for w in r] for r in rows]     # as int64 words
+            table = _upload_rows(self, "_staging", rows, device)
+            L.note_bytes(28.0 * sum(r[4] for r in rows))   # param, grad, two moments read; param, two moments written
+            L.check(L.lib().jtsm_adam_multi_f32(L.ptr(table), len(rows), blocks, L.stream()), "adam_multi")
+            torch.autograd.graph.increment_version(touched)   # updated behind autograd's back: say so
+        return loss
+
+
 def build_optimizer(cfg, model):
-    """detectron2/solver/build.py:110-195 for SOLVER.OPTIMIZER-less configs: SGD, bias lr x BIAS_LR_FACTOR,
-    WEIGHT_DECAY_BIAS for biases, WEIGHT_DECAY_NORM for normalisation layers, WEIGHT_DECAY otherwise."""
+    """detectron2/solver/build.py:110-195: bias lr x BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS for biases, WEIGHT_DECAY_NORM for
+    normalisation layers, WEIGHT_DECAY otherwise.  SOLVER.OPTIMIZER (projects/Panoptic-DeepLab/train_net.py:100-124):
+    "SGD", or no such key: SGD with momentum; "ADAM": Adam over the same per-parameter groups."""
+    kind = cfg.SOLVER.get("OPTIMIZER", "SGD")
+    if kind not in ("SGD", "ADAM"):
+        raise NotImplementedError("no optimizer type %s" % kind)
     norm_types = (torch.nn.BatchNorm2d, torch.nn.GroupNorm, torch.nn.LayerNorm, torch.nn.SyncBatchNorm)
     groups, seen = [], set()
     for module in model.modules():
@@ -168,4 +246,6 @@ def build_optimizer(cfg, model):
                 lr = cfg.SOLVER.BASE_LR * cfg.SOLVER.BIAS_LR_FACTOR
                 wd = cfg.SOLVER.WEIGHT_DECAY_BIAS
             groups.append({"params": [p], "lr": lr, "weight_decay": wd})
+    if kind == "ADAM":
+        return Adam(groups, cfg.SOLVER.BASE_LR)
     return SGD(groups, cfg.SOLVER.BASE_LR, momentum=cfg.SOLVER.MOMENTUM)
