@@ -19,6 +19,7 @@
 // Between statistics and apply, and between the backward's reduction and apply, the per-channel vectors are plain
 // device arrays: a multi-process run all-reduces them there (layers/batch_norm.py: combine_statistics).
 #include "common.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
@@ -316,8 +317,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     if (RES) gr.store(dres + r * C + c0);
   }
 }
-
-inline size_t a16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 int bn_check(long R, int C, long ld, const char* what) {
   JTSM_REQUIRE(R >= 0 && C > 0 && ld >= C, "%s: need rows >= 0, C > 0 and a leading dimension >= C (R=%ld C=%d ld=%ld)",

@@ -1,7 +1,12 @@
-// What the fused "bilinear xS up-sampling + soft-max cross-entropy" kernels share (semseg_ops.hip: the mean over the
-// non-ignored pixels; deeplab_loss.hip: the per-pixel loss and the hard-pixel mean): the source coordinate rule, the tap
-// association, one output pixel's log-sum-exp and one source pixel's gradient gather.  One definition each, so that a
-// forward and a backward — and the two losses — interpolate the same logits to the last bit.
+// Bilinear xS up-sampling as the kernels that fuse it form it.  For every one of them (the cross-entropies below, the
+// Panoptic-DeepLab regression losses, the keypoint head's and PointRend's x2): the source coordinate rule (lerp_scale)
+// and the four-tap blend in ATen's association (bilerp).  For the fused "up-sampling + soft-max cross-entropy" kernels
+// (semseg_ops.hip: the mean over the non-ignored pixels; deeplab_loss.hip: the per-pixel loss and the hard-pixel mean):
+// one output pixel's log-sum-exp and one source pixel's gradient gather.  One definition each, so that a forward and a
+// backward — and the losses among themselves — interpolate the same values to the last bit.
+// Everything here is inlined under the INCLUDING file's contraction flag (build.py): bilerp's products and sums fuse
+// in semseg_ops.hip and deeplab_loss.hip (contraction on) and round one by one in panoptic_deeplab.hip, keypoint.hip
+// and point_rend.hip (-ffp-contract=off), as each file's own copy did.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +24,17 @@ __device__ __forceinline__ Lerp lerp_scale(int o, int n_src, float inv_scale) {
   r.l1 = s - (float)r.i0;
   r.l0 = 1.f - r.l1;
   return r;
+}
+
+// the four taps (row a.i0: x00, x01; row a.i1: x10, x11) blended in ATen's association
+__device__ __forceinline__ float blend(const Lerp& a, const Lerp& b, float x00, float x01, float x10, float x11) {
+  return a.l0 * (b.l0 * x00 + b.l1 * x01) + a.l1 * (b.l0 * x10 + b.l1 * x11);
+}
+// the same read from a map of rows of Ws pixels of ld floats; base: the image's first pixel, at the wanted channel
+__device__ __forceinline__ float bilerp(const float* __restrict__ base, int ld, int Ws, const Lerp& a, const Lerp& b) {
+  const float x00 = base[((size_t)a.i0 * Ws + b.i0) * ld], x01 = base[((size_t)a.i0 * Ws + b.i1) * ld];
+  const float x10 = base[((size_t)a.i1 * Ws + b.i0) * ld], x11 = base[((size_t)a.i1 * Ws + b.i1) * ld];
+  return blend(a, b, x00, x01, x10, x11);
 }
 
 // l0 * a + l1 * b with the contraction spelled out: the backward forms must round alike
@@ -48,7 +64,7 @@ __device__ __forceinline__ float ce_pixel_lse(const float* __restrict__ z, int l
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int c = 4 * j + e;
-        float x = a.l0 * (b.l0 * x00[e] + b.l1 * x01[e]) + a.l1 * (b.l0 * x10[e] + b.l1 * x11[e]);   // ATen's association
+        float x = blend(a, b, x00[e], x01[e], x10[e], x11[e]);
         if (c >= C) x = -3.0e38f;
         v[c] = x;
         mx = fmaxf(mx, x);

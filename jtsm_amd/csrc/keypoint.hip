@@ -3,8 +3,10 @@
 // as a 3x3 convolution, plus the x2 bilinear up-sampling).  Logits are plain contiguous (R, K, S, S): one (roi, keypoint)
 // map is one row of S * S floats.  Built with -ffp-contract=off: the target cells and the decoded coordinates are the
 // reference's fp32 expressions, every product and sum rounded.  No float atomics: every reduction has a fixed order.
+#include "bilinear_ce.h"
 #include "common.h"
 #include "reduce.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
@@ -14,8 +16,6 @@ constexpr int kWaves = kThreads / kWave;
 constexpr int kMaxSide = 64;                          // S <= 64: a row is at most 4096 floats, 16 per thread
 constexpr int kPerThread = kMaxSide * kMaxSide / kThreads;
 constexpr int kMaxOut = 16384;                        // decode: a box side is walked up to this many pixels
-
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // (workgroup reductions in a fixed order — wg_reduce: reduce.h)
 
@@ -187,16 +187,7 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(const float* __restric
 }
 
 // ---- d. pixel shuffle + bilinear x2 -------------------------------------------------------------------------------
-// F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) along one axis of length n: the two source
-// indices and weights of destination d.
-__device__ __forceinline__ void bilinear_taps(int d, int n, int& i0, int& i1, float& l0, float& l1) {
-  const float s = fmaxf(0.5f * ((float)d + 0.5f) - 0.5f, 0.f);
-  i0 = (int)s;
-  i1 = min(i0 + 1, n - 1);
-  l1 = s - (float)i0;
-  l0 = 1.f - l1;
-}
-
+// F.interpolate(scale_factor=2, mode="bilinear", align_corners=False): lerp_scale at 1 / 2 along each axis
 // z (R, H, W, Cp) channels-last, channel (py * 2 + px) * K + k holds pixel (2 i + py, 2 j + px) of keypoint k
 __device__ __forceinline__ float shuffled(const float* __restrict__ z, int H, int W, int Cp, int K, int k, int a,
                                           int b) {
@@ -211,12 +202,9 @@ __global__ __launch_bounds__(kThreads) void upsample_forward_kernel(const float*
   const int X = (int)(i % OW), Y = (int)((i / OW) % OH), k = (int)((i / ((long)OW * OH)) % K);
   const long r = i / ((long)OW * OH * K);
   const float* __restrict__ zr = z + r * (long)H * W * Cp;
-  int a0, a1, b0, b1;
-  float la0, la1, lb0, lb1;
-  bilinear_taps(Y, 2 * H, a0, a1, la0, la1);
-  bilinear_taps(X, 2 * W, b0, b1, lb0, lb1);
-  out[i] = la0 * (lb0 * shuffled(zr, H, W, Cp, K, k, a0, b0) + lb1 * shuffled(zr, H, W, Cp, K, k, a0, b1)) +
-           la1 * (lb0 * shuffled(zr, H, W, Cp, K, k, a1, b0) + lb1 * shuffled(zr, H, W, Cp, K, k, a1, b1));
+  const Lerp a = lerp_scale(Y, 2 * H, 0.5f), b = lerp_scale(X, 2 * W, 0.5f);
+  out[i] = blend(a, b, shuffled(zr, H, W, Cp, K, k, a.i0, b.i0), shuffled(zr, H, W, Cp, K, k, a.i0, b.i1),
+                 shuffled(zr, H, W, Cp, K, k, a.i1, b.i0), shuffled(zr, H, W, Cp, K, k, a.i1, b.i1));
 }
 
 // The adjoint as a gather: element (r, i, j, c) of dz collects every output pixel whose taps name its shuffled pixel.
@@ -233,20 +221,28 @@ __global__ __launch_bounds__(kThreads) void upsample_backward_kernel(const float
   const float* __restrict__ gr = g + (r * K + k) * (long)OH * OW;
   float acc = 0.f;
   for (int Y = max(2 * a - 1, 0); Y <= min(2 * a + 2, OH - 1); ++Y) {
-    int a0, a1, b0, b1;
-    float la0, la1, lb0, lb1;
-    bilinear_taps(Y, 2 * H, a0, a1, la0, la1);
-    const float wy = (a0 == a ? la0 : 0.f) + (a1 == a ? la1 : 0.f);
+    const Lerp ty = lerp_scale(Y, 2 * H, 0.5f);
+    const float wy = (ty.i0 == a ? ty.l0 : 0.f) + (ty.i1 == a ? ty.l1 : 0.f);
     if (wy == 0.f) continue;
     float line = 0.f;
     for (int X = max(2 * b - 1, 0); X <= min(2 * b + 2, OW - 1); ++X) {
-      bilinear_taps(X, 2 * W, b0, b1, lb0, lb1);
-      const float wx = (b0 == b ? lb0 : 0.f) + (b1 == b ? lb1 : 0.f);
+      const Lerp tx = lerp_scale(X, 2 * W, 0.5f);
+      const float wx = (tx.i0 == b ? tx.l0 : 0.f) + (tx.i1 == b ? tx.l1 : 0.f);
       line += wx * gr[(long)Y * OW + X];
     }
     acc += wy * line;
   }
   dz[i] = acc;
+}
+
+// lse[rows] | row_loss[rows] | the denominator: one float, the last 256 bytes of the published size
+struct LossWs { float* lse; float* row_loss; float* denom; };
+LossWs carve_loss(Arena& a, size_t rows) {
+  LossWs w;
+  w.lse = a.take<float>(rows);
+  w.row_loss = a.take<float>(rows);
+  w.denom = a.take<float>(1);
+  return w;
 }
 
 }  // namespace
@@ -269,7 +265,9 @@ int jtsm_keypoint_targets_f32(const float* keypoints, const float* rois, int N, 
 
 size_t jtsm_keypoint_loss_workspace_bytes(int N, int K) {
   const size_t rows = (size_t)(N > 0 ? N : 0) * (size_t)(K > 0 ? K : 0);
-  return align256(rows * sizeof(float)) * 2 + 256;
+  Arena a{nullptr};
+  carve_loss(a, rows);
+  return a.off;
 }
 
 int jtsm_keypoint_loss_forward_f32(const float* logits, const int32_t* targets, const uint8_t* valid, int N, int K,
@@ -278,17 +276,16 @@ int jtsm_keypoint_loss_forward_f32(const float* logits, const int32_t* targets, 
   JTSM_REQUIRE(loss && workspace, "keypoint_loss: null pointer");
   const long rows = (long)N * K;
   JTSM_REQUIRE(rows < (1L << 24), "keypoint_loss: %ld rows (the valid count is kept in fp32)", rows);
-  float* lse = (float*)workspace;
-  float* row_loss = (float*)((char*)workspace + align256(rows * sizeof(float)));
-  float* denom = (float*)((char*)workspace + 2 * align256(rows * sizeof(float)));
+  Arena arena{static_cast<char*>(workspace)};
+  const LossWs w = carve_loss(arena, (size_t)rows);
   if (rows) {
     JTSM_REQUIRE(logits && targets && valid, "keypoint_loss: null pointer");
     hipLaunchKernelGGL(loss_rows_kernel, dim3((unsigned)rows), dim3(kThreads), 0, as_stream(stream), logits, targets,
-                       valid, S * S, lse, row_loss);
+                       valid, S * S, w.lse, w.row_loss);
     JTSM_CHECK_LAUNCH("keypoint_loss rows");
   }
-  hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(kThreads), 0, as_stream(stream), row_loss, valid, rows,
-                     normalizer, loss, denom);
+  hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(kThreads), 0, as_stream(stream), w.row_loss, valid, rows,
+                     normalizer, loss, w.denom);
   JTSM_CHECK_LAUNCH("keypoint_loss total");
   return JTSM_OK;
 }
@@ -300,10 +297,10 @@ int jtsm_keypoint_loss_backward_f32(const float* logits, const int32_t* targets,
   const long rows = (long)N * K;
   if (rows == 0) return JTSM_OK;
   JTSM_REQUIRE(logits && targets && valid && grad_loss && workspace && grad_logits, "keypoint_loss: null pointer");
-  const float* lse = (const float*)workspace;
-  const float* denom = (const float*)((const char*)workspace + 2 * align256(rows * sizeof(float)));
+  Arena arena{static_cast<char*>(const_cast<void*>(workspace))};
+  const LossWs w = carve_loss(arena, (size_t)rows);
   hipLaunchKernelGGL(loss_backward_kernel, dim3((unsigned)rows), dim3(kThreads), 0, as_stream(stream), logits, targets,
-                     valid, S * S, lse, denom, grad_loss, grad_logits);
+                     valid, S * S, w.lse, w.denom, grad_loss, grad_logits);
   JTSM_CHECK_LAUNCH("keypoint_loss backward");
   return JTSM_OK;
 }

@@ -1,13 +1,14 @@
 // Panoptic-DeepLab (projects/Panoptic-DeepLab/panoptic_deeplab/{panoptic_seg,post_processing}.py, train_net.py:100-124):
 //   losses    centre (MSE) and offset (L1) regression of the bilinearly xS up-sampled stride-S predictions against
 //             full-resolution targets, weighted per pixel and divided by the weights' sum.  One thread per output pixel
-//             interpolates its one or two channels on the fly (bilinear_ce.h: lerp_scale, ATen's tap association); fp64
-//             sums over fixed chunks in a fixed order; the backward is a gather per source pixel that forms the same
-//             interpolated value again.  sum(w) == 0 is decided on the device: loss and gradient exactly 0.
+//             interpolates its one or two channels on the fly (bilinear_ce.h: lerp_scale, bilerp); fp64 sums over fixed
+//             chunks in a fixed order (reduce.h: wg_tree_sum, fold_chunks); the backward is a gather per source pixel
+//             that forms the same interpolated value again.  sum(w) == 0 is decided on the device: loss and gradient
+//             exactly 0.
 //   centres   find_instance_center: threshold, k x k max-pool NMS (separable, one LDS tile per workgroup), the top_k-th
-//             largest value of the suppressed map by a radix select with per-workgroup LDS histograms (the select of
-//             deeplab_loss.hip), then an ordered compaction of the pixels STRICTLY above max(that value, 0): row-major
-//             order, at most top_k - 1 of them, none of those tied with the cut.
+//             largest value of the suppressed map by the chunked radix select of select.h (key order: its header), then
+//             an ordered compaction of the pixels STRICTLY above max(that value, 0): row-major order, at most
+//             top_k - 1 of them, none of those tied with the cut.
 //   grouping  group_pixels: per pixel the arg-min over the centres (in LDS) of sqrtf(dy*dy + dx*dx); the lowest centre
 //             index wins equal distances.  No K x HW intermediate.
 //   merge     merge_semantic_and_instance: K x C class histogram (integer atomics), majority class per instance (the
@@ -22,14 +23,13 @@
 #include "bilinear_ce.h"
 #include "common.h"
 #include "reduce.h"
+#include "select.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
 
-constexpr int PD_THREADS = 256;
-constexpr int PD_MAX_WG = 512;          // workgroups of the chunked passes (fixed-order sums, select, compaction)
-constexpr int PD_BINS = 256;            // 8-bit digits
-constexpr int PD_SEL_SLICES = 4;
+constexpr int PD_THREADS = kChunkThreads;     // the chunked passes (select.h) and every other kernel alike
 constexpr int PD_MAX_CENTERS = 1024;    // centres held in LDS by the grouping kernel (the reference's top_k is 200)
 constexpr int PD_MAX_CLASSES = 64;
 constexpr int PD_TILE_H = 16, PD_TILE_W = 64, PD_MAX_PAD = 15;     // NMS tile; nms_kernel <= 31
@@ -37,30 +37,9 @@ constexpr int PD_HIST_LDS_CELLS = 16000;                           // K x C + C 
 
 struct Min2 { __device__ int operator()(int a, int b) const { return a < b ? a : b; } };
 
-inline size_t a16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-struct PdChunks { int wgs; long chunk; };
-inline PdChunks pd_chunks(long npix) {
-  PdChunks c;
-  long tiles = (npix + PD_THREADS - 1) / PD_THREADS;
-  long per = (tiles + PD_MAX_WG - 1) / PD_MAX_WG;
-  if (per < 1) per = 1;
-  c.chunk = per * PD_THREADS;
-  c.wgs = (int)((npix + c.chunk - 1) / c.chunk);
-  if (c.wgs < 1) c.wgs = 1;
-  return c;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // losses
 // ---------------------------------------------------------------------------------------------------------------------
-// channel c of the up-sampled prediction at an output pixel whose taps are (a, b); zc = image base + c
-__device__ __forceinline__ float pd_up(const float* __restrict__ zc, int ld, int Ws, const Lerp& a, const Lerp& b) {
-  const float x00 = zc[((size_t)a.i0 * Ws + b.i0) * ld], x01 = zc[((size_t)a.i0 * Ws + b.i1) * ld];
-  const float x10 = zc[((size_t)a.i1 * Ws + b.i0) * ld], x11 = zc[((size_t)a.i1 * Ws + b.i1) * ld];
-  return a.l0 * (b.l0 * x00 + b.l1 * x01) + a.l1 * (b.l0 * x10 + b.l1 * x11);   // ATen's association
-}
-
 // part[b] = {sum of loss * w, sum of w} of chunk b in fp64.  kind 0: (up - t)^2, kind 1: |S * up - t| summed over C.
 __global__ __launch_bounds__(PD_THREADS) void pd_loss_fwd_kernel(const float* __restrict__ pred, int ld, int C,
                                                                  const float* __restrict__ target,
@@ -72,9 +51,9 @@ __global__ __launch_bounds__(PD_THREADS) void pd_loss_fwd_kernel(const float* __
   const int H = Hs * S, W = Ws * S;
   const long HW = (long)H * W;
   const float inv = 1.f / (float)S, mult = (float)S;
-  const long p0 = (long)blockIdx.x * chunk, p1 = p0 + chunk < npix ? p0 + chunk : npix;
+  const ChunkSpan ch = chunk_of_wg(npix, chunk);
   double accl = 0.0, accw = 0.0;
-  for (long p = p0 + t; p < p1; p += PD_THREADS) {
+  for (long p = ch.p0 + t; p < ch.p1; p += PD_THREADS) {
     const int ow = (int)(p % W);
     const long q = p / W;
     const int oh = (int)(q % H), n = (int)(q / H);
@@ -84,7 +63,7 @@ __global__ __launch_bounds__(PD_THREADS) void pd_loss_fwd_kernel(const float* __
     const float* zn = pred + (size_t)n * Hs * Ws * ld;
     const long o = (long)oh * W + ow;
     for (int c = 0; c < C; ++c) {
-      const float up = pd_up(zn + c, ld, Ws, a, b);
+      const float up = bilerp(zn + c, ld, Ws, a, b);
       const float tv = target[((long)n * C + c) * HW + o];
       float l;
       if (kind == 0) { const float d = up - tv; l = d * d; }
@@ -92,29 +71,18 @@ __global__ __launch_bounds__(PD_THREADS) void pd_loss_fwd_kernel(const float* __
       accl += (double)(l * w);
     }
   }
-  sl[t] = accl; sw[t] = accw;
-  __syncthreads();
-  for (int o = PD_THREADS / 2; o > 0; o >>= 1) {
-    if (t < o) { sl[t] += sl[t + o]; sw[t] += sw[t + o]; }
-    __syncthreads();
-  }
-  if (t == 0) { part[2 * blockIdx.x] = sl[0]; part[2 * blockIdx.x + 1] = sw[0]; }
+  wg_tree_sum<PD_THREADS>(accl, sl, accw, sw);
+  if (t == 0) { part[2 * blockIdx.x] = accl; part[2 * blockIdx.x + 1] = accw; }
 }
 
-// out[0] = sum(loss * w) / sum(w), out[1] = 1 / sum(w); both 0 where sum(w) is not positive.  Thread t owns consecutive
-// chunks, the threads' sums are added in thread order.
+// out[0] = sum(loss * w) / sum(w), out[1] = 1 / sum(w); both 0 where sum(w) is not positive.  The fixed-order fold of
+// reduce.h over the pairs.
 __global__ __launch_bounds__(PD_THREADS) void pd_loss_finish_kernel(const double* __restrict__ part, int wgs,
                                                                     float* __restrict__ out) {
   __shared__ double sl[PD_THREADS], sw[PD_THREADS];
-  const int t = threadIdx.x, per = (wgs + PD_THREADS - 1) / PD_THREADS;
-  const int b0 = t * per, b1 = min(wgs, b0 + per);
-  double l = 0.0, w = 0.0;
-  for (int b = b0; b < b1; ++b) { l += part[2 * b]; w += part[2 * b + 1]; }
-  sl[t] = l; sw[t] = w;
-  __syncthreads();
-  if (t == 0) {
-    double L = 0.0, Wt = 0.0;
-    for (int i = 0; i < PD_THREADS; ++i) { L += sl[i]; Wt += sw[i]; }
+  double L, Wt;
+  fold_chunks<PD_THREADS>(part, part + 1, 2, wgs, sl, sw, L, Wt);
+  if (threadIdx.x == 0) {
     const bool live = Wt > 0.0;
     out[0] = live ? (float)(L / Wt) : 0.f;
     out[1] = live ? (float)(1.0 / Wt) : 0.f;
@@ -158,7 +126,7 @@ __global__ __launch_bounds__(PD_THREADS) void pd_loss_bwd_kernel(const float* __
         const long o = (long)oh * W + ow;
         const float wt = wn[o];
         if (wt == 0.f) continue;
-        const float up = pd_up(zc, ld, Ws, a, b);
+        const float up = bilerp(zc, ld, Ws, a, b);
         const float tv = tc[o];
         float g;
         if (kind == 0) g = 2.f * (up - tv);
@@ -210,81 +178,26 @@ __global__ __launch_bounds__(PD_THREADS) void pd_nms_kernel(const float* __restr
   }
 }
 
-struct PdSel { unsigned prefix, need, pad0, pad1; };
-
-__global__ void pd_sel_init_kernel(PdSel* __restrict__ st, unsigned k) {
-  if (threadIdx.x == 0) { st->prefix = 0u; st->need = k; st->pad0 = 0u; st->pad1 = 0u; }
-}
-
-__global__ __launch_bounds__(PD_THREADS) void pd_sel_hist_kernel(const float* __restrict__ v, long n, long chunk,
-                                                                 const PdSel* __restrict__ st, int shift,
-                                                                 unsigned* __restrict__ hist) {
-  __shared__ unsigned h[PD_THREADS / 64][PD_BINS];
-  const int t = threadIdx.x, wv = t >> 6;
-  for (int i = t; i < (PD_THREADS / 64) * PD_BINS; i += PD_THREADS) (&h[0][0])[i] = 0u;
-  __syncthreads();
-  const unsigned prefix = st->prefix;
-  const int above = shift + 8;
-  const long p0 = (long)blockIdx.x * chunk, p1 = p0 + chunk < n ? p0 + chunk : n;
-  for (long p = p0 + t; p < p1; p += PD_THREADS) {
-    const unsigned key = ordered_bits(v[p]);
-    const bool match = above >= 32 || (key >> above) == (prefix >> above);
-    if (match) atomicAdd(&h[wv][(key >> shift) & (PD_BINS - 1)], 1u);
-  }
-  __syncthreads();
-  for (int d = t; d < PD_BINS; d += PD_THREADS) {
-    unsigned s = 0u;
-#pragma unroll
-    for (int w = 0; w < PD_THREADS / 64; ++w) s += h[w][d];
-    hist[(size_t)blockIdx.x * PD_BINS + d] = s;
-  }
-}
-
-__global__ __launch_bounds__(PD_BINS * PD_SEL_SLICES) void pd_sel_pick_kernel(const unsigned* __restrict__ hist, int wgs,
-                                                                              int shift, PdSel* __restrict__ st) {
-  __shared__ unsigned tot[PD_SEL_SLICES][PD_BINS];
-  const int d = threadIdx.x % PD_BINS, j = threadIdx.x / PD_BINS;
-  unsigned s = 0u;
-  for (int b = j; b < wgs; b += PD_SEL_SLICES) s += hist[(size_t)b * PD_BINS + d];
-  tot[j][d] = s;
-  __syncthreads();
-  if (j == 0) {
-    for (int jj = 1; jj < PD_SEL_SLICES; ++jj) s += tot[jj][d];
-    tot[0][d] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned need = st->need, abovec = 0u;
-    int bin = 0;
-    for (int i = PD_BINS - 1; i >= 0; --i) {
-      if (abovec + tot[0][i] >= need) { bin = i; break; }
-      abovec += tot[0][i];
-    }
-    st->prefix |= (unsigned)bin << shift;
-    st->need = need - abovec;
-  }
-}
-
 // kept: strictly above max(the top_k-th value, 0)
-__device__ __forceinline__ unsigned pd_cut_key(const PdSel* __restrict__ st) {
+__device__ __forceinline__ unsigned pd_cut_key(const SelectState* __restrict__ st) {
   const unsigned zero = ordered_bits(0.f);
   return st->prefix > zero ? st->prefix : zero;
 }
 
 __global__ __launch_bounds__(PD_THREADS) void pd_keep_count_kernel(const float* __restrict__ sup, long n, long chunk,
-                                                                   const PdSel* __restrict__ st,
+                                                                   const SelectState* __restrict__ st,
                                                                    unsigned* __restrict__ cnt) {
   __shared__ unsigned slot[PD_THREADS / 64];
   const unsigned cut = pd_cut_key(st);
-  const long p0 = (long)blockIdx.x * chunk, p1 = p0 + chunk < n ? p0 + chunk : n;
+  const ChunkSpan ch = chunk_of_wg(n, chunk);
   unsigned c = 0u;
-  for (long p = p0 + threadIdx.x; p < p1; p += PD_THREADS) c += ordered_bits(sup[p]) > cut ? 1u : 0u;
+  for (long p = ch.p0 + threadIdx.x; p < ch.p1; p += PD_THREADS) c += ordered_bits(sup[p]) > cut ? 1u : 0u;
   c = wg_reduce<PD_THREADS / 64>(c, Add(), slot);
   if (threadIdx.x == 0) cnt[blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(PD_THREADS) void pd_keep_emit_kernel(const float* __restrict__ sup, long n, long chunk, int W,
-                                                                  const PdSel* __restrict__ st,
+                                                                  const SelectState* __restrict__ st,
                                                                   const unsigned* __restrict__ cnt, int wgs, int top_k,
                                                                   int* __restrict__ centers, int* __restrict__ count) {
   __shared__ unsigned slot[PD_THREADS / 64];
@@ -304,10 +217,10 @@ __global__ __launch_bounds__(PD_THREADS) void pd_keep_emit_kernel(const float* _
     if (t == 0) *count = kept;
     for (int r = kept + t; r < top_k; r += PD_THREADS) { centers[2 * r] = -1; centers[2 * r + 1] = -1; }
   }
-  const long p0 = (long)blockIdx.x * chunk, p1 = p0 + chunk < n ? p0 + chunk : n;
-  for (long q = p0; q < p1; q += PD_THREADS) {      // (uniform trip count: the compaction has barriers)
+  const ChunkSpan ch = chunk_of_wg(n, chunk);
+  for (long q = ch.p0; q < ch.p1; q += PD_THREADS) {      // (uniform trip count: the compaction has barriers)
     const long p = q + t;
-    const bool keep = p < p1 && ordered_bits(sup[p]) > cut;
+    const bool keep = p < ch.p1 && ordered_bits(sup[p]) > cut;
     int total;
     const int s = compact_wg<PD_THREADS / 64>(keep, wave_count, total);
     const unsigned row = base + (unsigned)s;
@@ -396,8 +309,8 @@ __global__ __launch_bounds__(PD_THREADS) void pd_hist_kernel(const int* __restri
     for (int i = threadIdx.x; i < ncell; i += PD_THREADS) cells[i] = 0;
     __syncthreads();
   }
-  const long p0 = (long)blockIdx.x * chunk, p1 = p0 + chunk < HW ? p0 + chunk : HW;
-  for (long p = p0 + threadIdx.x; p < p1; p += PD_THREADS) {
+  const ChunkSpan ch = chunk_of_wg(HW, chunk);
+  for (long p = ch.p0 + threadIdx.x; p < ch.p1; p += PD_THREADS) {
     const int s = sem[p], i = ins[p];
     if (s < 0 || s >= C || i < 0 || i > K) continue;
     int cell = -1;
@@ -559,34 +472,26 @@ __global__ __launch_bounds__(PD_THREADS) void pd_inst_kernel(const int* __restri
   o[6] = (float)cy; o[7] = (float)cx;
 }
 
-struct PdMergeWs { int* hist; int* stuff; int* ins_row; int* stuff_ok; PdSegStat* stat; };
-inline size_t pd_merge_ws_bytes(int K, int C) {
-  return a16(sizeof(int) * (size_t)K * C) + a16(sizeof(int) * C) + a16(sizeof(int) * K) + a16(sizeof(int) * C) +
-         a16(sizeof(PdSegStat) * (size_t)K) + 16;
-}
-inline PdMergeWs pd_merge_carve(void* workspace, int K, int C) {
-  char* w = reinterpret_cast<char*>(workspace);
+// (hist | stuff: one memset clears both, up to `cleared`)
+struct PdMergeWs { int* hist; int* stuff; size_t cleared; int* ins_row; int* stuff_ok; PdSegStat* stat; };
+PdMergeWs carve_merge(Arena& a, int K, int C) {
   PdMergeWs M;
-  M.hist = reinterpret_cast<int*>(w); w += a16(sizeof(int) * (size_t)K * C);
-  M.stuff = reinterpret_cast<int*>(w); w += a16(sizeof(int) * C);
-  M.ins_row = reinterpret_cast<int*>(w); w += a16(sizeof(int) * K);
-  M.stuff_ok = reinterpret_cast<int*>(w); w += a16(sizeof(int) * C);
-  M.stat = reinterpret_cast<PdSegStat*>(w);
+  M.hist = a.take<int>((size_t)K * C);
+  M.stuff = a.take<int>(C);
+  M.cleared = a.mark();
+  M.ins_row = a.take<int>(K);
+  M.stuff_ok = a.take<int>(C);
+  M.stat = a.take<PdSegStat>(K);
   return M;
 }
 
-struct PdCenterWs { float* sup; unsigned* hist; PdSel* st; unsigned* cnt; };
-inline size_t pd_center_ws_bytes(long HW) {
-  return a16(sizeof(float) * (size_t)HW) + a16(sizeof(unsigned) * PD_MAX_WG * PD_BINS) + a16(sizeof(PdSel)) +
-         a16(sizeof(unsigned) * PD_MAX_WG) + 16;
-}
-inline PdCenterWs pd_center_carve(void* workspace, long HW) {
-  char* w = reinterpret_cast<char*>(workspace);
+struct PdCenterWs { float* sup; unsigned* hist; SelectState* st; unsigned* cnt; };
+PdCenterWs carve_centers(Arena& a, long HW) {
   PdCenterWs Cw;
-  Cw.sup = reinterpret_cast<float*>(w); w += a16(sizeof(float) * (size_t)HW);
-  Cw.hist = reinterpret_cast<unsigned*>(w); w += a16(sizeof(unsigned) * PD_MAX_WG * PD_BINS);
-  Cw.st = reinterpret_cast<PdSel*>(w); w += a16(sizeof(PdSel));
-  Cw.cnt = reinterpret_cast<unsigned*>(w);
+  Cw.sup = a.take<float>((size_t)HW);
+  Cw.hist = a.take<unsigned>(kMaxChunkWgs * kSelectBins);
+  Cw.st = a.take<SelectState>(1);
+  Cw.cnt = a.take<unsigned>(kMaxChunkWgs);
   return Cw;
 }
 
@@ -658,7 +563,7 @@ extern "C" {
 
 int jtsm_adam_block_elements(void) { return ADAM_WG_ELEMS; }
 
-size_t jtsm_pdl_loss_workspace_bytes(void) { return a16(sizeof(double) * 2 * PD_MAX_WG) + 16; }
+size_t jtsm_pdl_loss_workspace_bytes(void) { return a16(sizeof(double) * 2 * kMaxChunkWgs) + 16; }
 
 static int pd_loss_check(int C, int ld, int kind, int N, int Hs, int Ws, int S, const char* what) {
   JTSM_REQUIRE(N >= 0 && Hs > 0 && Ws > 0 && S > 0 && C >= 1 && C <= 8 && ld >= C && (kind == 0 || kind == 1),
@@ -676,7 +581,7 @@ int jtsm_pdl_loss_forward_f32(const float* pred, int ld, int C, const float* tar
   JTSM_REQUIRE(((uintptr_t)workspace & 7) == 0, "pdl_loss: workspace must be 8-byte aligned");
   hipStream_t st = as_stream(stream);
   const long npix = (long)N * Hs * S * Ws * S;
-  const PdChunks ch = pd_chunks(npix);
+  const Chunks ch = chunks_of(npix);
   double* part = reinterpret_cast<double*>(workspace);
   hipLaunchKernelGGL(pd_loss_fwd_kernel, dim3(ch.wgs), dim3(PD_THREADS), 0, st, pred, ld, C, target, weights, kind, npix,
                      ch.chunk, Hs, Ws, S, part);
@@ -701,7 +606,9 @@ int jtsm_pdl_loss_backward_f32(const float* pred, int ld, int C, const float* ta
 
 size_t jtsm_pdl_centers_workspace_bytes(int H, int W) {
   if (H <= 0 || W <= 0) return 0;
-  return pd_center_ws_bytes((long)H * W);
+  Arena a{nullptr, false, 16};
+  carve_centers(a, (long)H * W);
+  return a.off + 16;
 }
 
 int jtsm_pdl_find_centers_f32(const float* heat, int H, int W, float threshold, int nms_kernel, int top_k, int* centers,
@@ -714,16 +621,12 @@ int jtsm_pdl_find_centers_f32(const float* heat, int H, int W, float threshold, 
   JTSM_REQUIRE(((uintptr_t)workspace & 15) == 0, "pdl_find_centers: workspace must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
   const long HW = (long)H * W;
-  const PdCenterWs Cw = pd_center_carve(workspace, HW);
-  const PdChunks ch = pd_chunks(HW);
+  Arena arena{static_cast<char*>(workspace), false, 16};
+  const PdCenterWs Cw = carve_centers(arena, HW);
+  const Chunks ch = chunks_of(HW);
   hipLaunchKernelGGL(pd_nms_kernel, dim3((W + PD_TILE_W - 1) / PD_TILE_W, (H + PD_TILE_H - 1) / PD_TILE_H),
                      dim3(PD_THREADS), 0, st, heat, H, W, threshold, (nms_kernel - 1) / 2, Cw.sup);
-  hipLaunchKernelGGL(pd_sel_init_kernel, dim3(1), dim3(64), 0, st, Cw.st, (unsigned)top_k);
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    hipLaunchKernelGGL(pd_sel_hist_kernel, dim3(ch.wgs), dim3(PD_THREADS), 0, st, Cw.sup, HW, ch.chunk, Cw.st, shift,
-                       Cw.hist);
-    hipLaunchKernelGGL(pd_sel_pick_kernel, dim3(1), dim3(PD_BINS * PD_SEL_SLICES), 0, st, Cw.hist, ch.wgs, shift, Cw.st);
-  }
+  launch_select(Cw.sup, HW, ch, (unsigned)top_k, Cw.st, Cw.hist, st);
   hipLaunchKernelGGL(pd_keep_count_kernel, dim3(ch.wgs), dim3(PD_THREADS), 0, st, Cw.sup, HW, ch.chunk, Cw.st, Cw.cnt);
   hipLaunchKernelGGL(pd_keep_emit_kernel, dim3(ch.wgs), dim3(PD_THREADS), 0, st, Cw.sup, HW, ch.chunk, W, Cw.st, Cw.cnt,
                      ch.wgs, top_k, centers, count);
@@ -754,7 +657,9 @@ int jtsm_pdl_group_pixels_f32(const int* centers, const int* count, int max_cent
 
 size_t jtsm_pdl_merge_workspace_bytes(int max_instances, int num_classes) {
   if (max_instances < 1 || max_instances > PD_MAX_CENTERS || num_classes < 1 || num_classes > PD_MAX_CLASSES) return 0;
-  return pd_merge_ws_bytes(max_instances, num_classes);
+  Arena a{nullptr, false, 16};
+  carve_merge(a, max_instances, num_classes);
+  return a.off + 16;
 }
 
 int jtsm_pdl_merge_f32(const int* sem, const int* ins, const unsigned char* thing_seg, const unsigned char* thing_lut,
@@ -775,9 +680,10 @@ int jtsm_pdl_merge_f32(const int* sem, const int* ins, const unsigned char* thin
   JTSM_REQUIRE(((uintptr_t)workspace & 15) == 0, "pdl_merge: workspace must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
   const long HW = (long)H * W;
-  const PdMergeWs M = pd_merge_carve(workspace, K, C);
-  JTSM_CHECK_HIP(hipMemsetAsync(M.hist, 0, a16(sizeof(int) * (size_t)K * C) + a16(sizeof(int) * C), st));
-  const PdChunks ch = pd_chunks(HW);
+  Arena arena{static_cast<char*>(workspace), false, 16};
+  const PdMergeWs M = carve_merge(arena, K, C);
+  JTSM_CHECK_HIP(hipMemsetAsync(M.hist, 0, M.cleared, st));
+  const Chunks ch = chunks_of(HW);
   const int ncell = K * C + C;
   const int lds = ncell <= PD_HIST_LDS_CELLS ? 1 : 0;
   hipLaunchKernelGGL(pd_hist_kernel, dim3(ch.wgs), dim3(PD_THREADS), lds ? sizeof(int) * ncell : 0, st, sem, ins,

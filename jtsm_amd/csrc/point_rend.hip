@@ -3,8 +3,10 @@
 // 0.5 a target falls on hang on fp32 expressions written in the reference's order (point_features.py and ATen's
 // grid_sample with align_corners=False and zero padding), every product and sum rounded.  No float atomics: every sum
 // has a fixed order (the histogram of the radix select counts integers).
+#include "bilinear_ce.h"
 #include "common.h"
 #include "reduce.h"
+#include "select.h"
 #include "sorted_segments.h"
 #include "workspace.h"
 
@@ -294,7 +296,18 @@ struct Masks {
   int N;
 };
 
-// workspace: targets[rows] (float) | partial sums (double, one per workgroup) | partial correct counts (int)
+// workspace: targets[rows] | partial sums, one per workgroup | partial correct counts; the backward reads `targets`, the
+// first buffer, from the workspace pointer itself
+struct LossWs { float* targets; double* part_sum; int* part_correct; };
+LossWs carve_loss(Arena& a, size_t rows) {
+  const size_t parts = (rows + kThreads - 1) / kThreads;
+  LossWs w;
+  w.targets = a.take<float>(rows);
+  w.part_sum = a.take<double>(parts);
+  w.part_correct = a.take<int>(parts);
+  return w;
+}
+
 __global__ __launch_bounds__(kThreads) void loss_forward_kernel(const float* __restrict__ logits, long ld, int C,
                                                                 const long* __restrict__ classes, Masks m,
                                                                 const int* __restrict__ roi_image,
@@ -374,29 +387,17 @@ __global__ __launch_bounds__(kThreads) void loss_backward_kernel(const float* __
 }
 
 // ---- e. subdivision ---------------------------------------------------------------------------------------------------
-// F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) along one axis of length n: the two source
-// indices and weights of destination d.
-__device__ __forceinline__ void bilinear_taps(int d, int n, int& i0, int& i1, float& l0, float& l1) {
-  const float s = fmaxf(0.5f * ((float)d + 0.5f) - 0.5f, 0.f);
-  i0 = (int)s;
-  i1 = min(i0 + 1, n - 1);
-  l1 = s - (float)i0;
-  l0 = 1.f - l1;
-}
-
+// F.interpolate(scale_factor=2, mode="bilinear", align_corners=False): lerp_scale at 1 / 2 along each axis
 __device__ __forceinline__ float upsampled(const float* __restrict__ tile, int H, int W, int p) {
   const int OW = 2 * W;
   const int Y = p / OW, X = p - Y * OW;
-  int a0, a1, b0, b1;
-  float la0, la1, lb0, lb1;
-  bilinear_taps(Y, H, a0, a1, la0, la1);
-  bilinear_taps(X, W, b0, b1, lb0, lb1);
-  return la0 * (lb0 * tile[a0 * W + b0] + lb1 * tile[a0 * W + b1]) +
-         la1 * (lb0 * tile[a1 * W + b0] + lb1 * tile[a1 * W + b1]);
+  const Lerp a = lerp_scale(Y, H, 0.5f), b = lerp_scale(X, W, 0.5f);
+  return blend(a, b, tile[a.i0 * W + b.i0], tile[a.i0 * W + b.i1], tile[a.i1 * W + b.i0], tile[a.i1 * W + b.i1]);
 }
 
 // One workgroup per roi.  The H x W map sits in LDS; the 2H x 2W values are formed from it on every pass.  The n most
-// uncertain cells are found by a radix select over the four bytes of ordered_bits(-|v|), ties at the cut going to the
+// uncertain cells are found by a radix select over the four bytes of ordered_bits(-|v|) (one histogram in LDS; the bin
+// rule is select.h's top_bin), ties at the cut going to the
 // lower cell index, and put into (uncertainty descending, index ascending) by counting.  `direct`: `in` is a given
 // (R, H, W) uncertainty map, read from memory and ranked as it is (get_uncertain_point_coords_on_grid on its own);
 // nothing is up-sampled or written to `out`.
@@ -423,8 +424,7 @@ __global__ __launch_bounds__(kSubThreads) void subdivide_kernel(const float* __r
     for (int p = threadIdx.x; p < total; p += kSubThreads) out[(long)r * total + p] = upsampled(tile, H, W, p);
   }
   if (n <= 0) return;                                   // (uniform: the skip rule, only up-sample)
-  unsigned prefix = 0, mask = 0;
-  int need = n;
+  unsigned prefix = 0, mask = 0, need = (unsigned)n;
   for (int shift = 24; shift >= 0; shift -= 8) {
     __syncthreads();                                    // the previous digit's readers are done
     if (threadIdx.x < 256) hist[threadIdx.x] = 0;
@@ -434,12 +434,8 @@ __global__ __launch_bounds__(kSubThreads) void subdivide_kernel(const float* __r
       if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
     }
     __syncthreads();
-    int above = 0, b = 255;                             // (every thread walks the same bins: uniform)
-    for (; b > 0; --b) {
-      const int c = (int)hist[b];
-      if (above + c >= need) break;
-      above += c;
-    }
+    unsigned above;
+    const int b = top_bin(hist, need, above);           // (every thread walks the same bins: uniform)
     need -= above;
     prefix |= (unsigned)b << shift;
     mask |= 255u << shift;
@@ -452,7 +448,7 @@ __global__ __launch_bounds__(kSubThreads) void subdivide_kernel(const float* __r
     const bool at = p < total && k == prefix;
     int n_at, n_take;
     const int slot_at = compact_wg<kSubWaves>(at, wave_count, n_at);
-    const bool take = p < total && (k > prefix || (at && seen + slot_at < need));
+    const bool take = p < total && (k > prefix || (at && (unsigned)(seen + slot_at) < need));
     const int slot = compact_wg<kSubWaves>(take, wave_count, n_take);
     if (take && filled + slot < kMaxChosen) chosen[filled + slot] = index_key(k, (unsigned)p);
     seen += n_at;
@@ -629,8 +625,9 @@ int jtsm_point_select_f32(const float* coarse_logits, int R, int C, int S, const
 
 size_t jtsm_point_loss_workspace_bytes(int R, int P) {
   const size_t rows = (size_t)(R > 0 ? R : 0) * (size_t)(P > 0 ? P : 0);
-  const size_t parts = (rows + kThreads - 1) / kThreads;
-  return align256(rows * sizeof(float)) + align256(parts * sizeof(double)) + align256(parts * sizeof(int)) + 256;
+  Arena a{nullptr};
+  carve_loss(a, rows);
+  return a.off + 256;
 }
 
 int jtsm_point_loss_forward_f32(const float* logits, int64_t ld, int R, int P, int C, const int64_t* classes,
@@ -643,9 +640,8 @@ int jtsm_point_loss_forward_f32(const float* logits, int64_t ld, int R, int P, i
   const long rows = (long)R * P;
   JTSM_REQUIRE(rows < (1L << 31) - kThreads, "point_loss: %ld rows", rows);
   const int parts = ceil_div(rows, kThreads);
-  float* targets = (float*)workspace;
-  double* part_sum = (double*)((char*)workspace + align256(rows * sizeof(float)));
-  int* part_correct = (int*)((char*)part_sum + align256((size_t)parts * sizeof(double)));
+  Arena arena{static_cast<char*>(workspace)};
+  const LossWs w = carve_loss(arena, (size_t)rows);
   if (rows) {
     JTSM_REQUIRE(logits && (C == 1 || classes) && roi_image && matched && coords_wrt_image && (N == 0 || (masks && mask_geom)),
                  "point_loss: null pointer");
@@ -658,12 +654,12 @@ int jtsm_point_loss_forward_f32(const float* logits, int64_t ld, int R, int P, i
                    "point_loss: image %d: %d masks of %d x %d", n, m.count[n], m.h[n], m.w[n]);
     }
     hipLaunchKernelGGL(loss_forward_kernel, dim3(parts), dim3(kThreads), 0, as_stream(stream), logits, (long)ld, C,
-                       (const long*)classes, m, roi_image, matched, coords_wrt_image, rows, P, targets, part_sum,
-                       part_correct);
+                       (const long*)classes, m, roi_image, matched, coords_wrt_image, rows, P, w.targets, w.part_sum,
+                       w.part_correct);
     JTSM_CHECK_LAUNCH("point_loss forward");
   }
-  hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(kThreads), 0, as_stream(stream), part_sum, part_correct, parts,
-                     rows, loss, stats);
+  hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(kThreads), 0, as_stream(stream), w.part_sum, w.part_correct,
+                     parts, rows, loss, stats);
   JTSM_CHECK_LAUNCH("point_loss total");
   return JTSM_OK;
 }

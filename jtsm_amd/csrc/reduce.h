@@ -1,7 +1,11 @@
 // Wavefront and workgroup reductions, one definition each.  The order is part of the contract: a butterfly inside the
 // wavefront from offset 32 down to 1 (both partners form the same value, so every lane ends with it), then the
 // per-wave values folded in wave order — float sums that go through here are the same bits on every run and in every
-// kernel.  No helper here multiplies and adds, so none carries a contraction pragma.
+// kernel.  Two more orders are part of the contract, for the sums that have always had them: the LDS halving tree
+// (wg_tree_sum: s[t] += s[t + o] for o = THREADS / 2 ... 1) and the fold over a chunked pass's partials (fold_chunks:
+// thread t owns consecutive chunks, the threads' sums are added in thread order).  Neither may be swapped for the
+// butterfly: the last bits of the fp64 sums would change.  No helper here multiplies and adds, so none carries a
+// contraction pragma.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,6 +43,64 @@ __device__ __forceinline__ T wg_reduce(T v, Op op, T* __restrict__ slot) {
   const int nw = NW ? NW : blockDim.x >> 6;
   for (int w = 1; w < nw; ++w) r = op(r, slot[w]);
   return r;
+}
+
+// ---- the LDS halving tree over a workgroup of THREADS (a power of two): the sum is valid in thread 0.  `s`, `sa`, `sb`:
+// __shared__ arrays of THREADS values.  The pair form sums two values behind the same barriers.
+template <int THREADS, class T>
+__device__ __forceinline__ T wg_tree_sum(T v, T* __restrict__ s) {
+  const int t = threadIdx.x;
+  s[t] = v;
+  __syncthreads();
+  for (int o = THREADS / 2; o > 0; o >>= 1) {
+    if (t < o) s[t] += s[t + o];
+    __syncthreads();
+  }
+  return s[0];
+}
+template <int THREADS, class A, class B>
+__device__ __forceinline__ void wg_tree_sum(A& a, A* __restrict__ sa, B& b, B* __restrict__ sb) {
+  const int t = threadIdx.x;
+  sa[t] = a; sb[t] = b;
+  __syncthreads();
+  for (int o = THREADS / 2; o > 0; o >>= 1) {
+    if (t < o) { sa[t] += sa[t + o]; sb[t] += sb[t + o]; }
+    __syncthreads();
+  }
+  a = sa[0]; b = sb[0];
+}
+
+// ---- the fold over the `wgs` per-workgroup partials of a chunked pass, by one workgroup of THREADS, for a pair of
+// partials (pa[b * stride], pb[b * stride]: those of chunk b): thread t sums its ceil(wgs / THREADS) consecutive
+// chunks [fold_span), then thread 0 adds the threads' sums in thread order, in one walk for both.  Thread 0 gets the
+// totals (the other threads 0); sa[t], sb[t] (__shared__, THREADS values each) are left holding the sum of the threads
+// BEFORE t, the exclusive scan in chunk order that an ordered compaction starts from — valid after the caller's next
+// barrier.
+struct FoldSpan { int b0, b1; };
+template <int THREADS>
+__device__ __forceinline__ FoldSpan fold_span(int wgs) {
+  const int per = (wgs + THREADS - 1) / THREADS;
+  FoldSpan f;
+  f.b0 = threadIdx.x * per;
+  f.b1 = min(wgs, f.b0 + per);
+  return f;
+}
+template <int THREADS, class A, class B>
+__device__ __forceinline__ void fold_chunks(const A* __restrict__ pa, const B* __restrict__ pb, int stride, int wgs,
+                                            A* __restrict__ sa, B* __restrict__ sb, A& total_a, B& total_b) {
+  const FoldSpan f = fold_span<THREADS>(wgs);
+  A a = 0;
+  B b = 0;
+  for (int c = f.b0; c < f.b1; ++c) { a += pa[(size_t)c * stride]; b += pb[(size_t)c * stride]; }
+  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
+  __syncthreads();
+  total_a = 0; total_b = 0;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < THREADS; ++i) {
+      a = sa[i]; b = sb[i];
+      sa[i] = total_a; sb[i] = total_b;
+      total_a += a; total_b += b;
+    }
 }
 
 // ---- arg-best over (float value, int index): the larger value wins, the lower index among equal values.  The pair

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "planes.h"
 #include "reduce.h"
+#include "workspace.h"
 
 namespace jtsm {
 namespace {
@@ -465,13 +466,6 @@ __global__ __launch_bounds__(256) void ups_bwd_kernel(const float* __restrict__ 
 // (wavefront per pixel, lanes = classes, C <= 64), reduced to a log-sum-exp with wavefront shuffles, and
 // only lse (4 B per pixel) is kept for the backward, which is a GATHER over the <= (2S)^2 output pixels
 // that touch each source pixel (no atomics, deterministic).
-__device__ __forceinline__ float interp_logit(const float* __restrict__ zn, int Ws, int ldc, const Lerp& a,
-                                              const Lerp& b, int c) {
-  const float v00 = zn[((size_t)a.i0 * Ws + b.i0) * ldc + c], v01 = zn[((size_t)a.i0 * Ws + b.i1) * ldc + c];
-  const float v10 = zn[((size_t)a.i1 * Ws + b.i0) * ldc + c], v11 = zn[((size_t)a.i1 * Ws + b.i1) * ldc + c];
-  return a.l0 * (b.l0 * v00 + b.l1 * v01) + a.l1 * (b.l0 * v10 + b.l1 * v11);   // ATen's association
-}
-
 // Forward: one THREAD per output pixel (neighbouring pixels share their four taps, so the tap loads of a
 // wave collapse onto a few cache lines); the <= 64 interpolated logits stay in registers.
 __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const float* __restrict__ z, int ldc, int C,
@@ -505,21 +499,16 @@ __global__ __launch_bounds__(256) void ce_up_fwd_kernel(const float* __restrict_
     part[blockIdx.x * 2 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// out[0] = mean loss over non-ignored pixels, out[1] = their count (fixed-order tree, deterministic)
+// out[0] = mean loss over non-ignored pixels, out[1] = their count (wg_tree_sum: fixed order, deterministic)
 __global__ __launch_bounds__(256) void ce_finish_kernel(const float* __restrict__ part, int nblocks,
                                                         float* __restrict__ out) {
   __shared__ double sl[256], sc[256];
   double l = 0.0, c = 0.0;
   for (int b = threadIdx.x; b < nblocks; b += 256) { l += part[2 * b]; c += part[2 * b + 1]; }
-  sl[threadIdx.x] = l; sc[threadIdx.x] = c;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) { sl[threadIdx.x] += sl[threadIdx.x + o]; sc[threadIdx.x] += sc[threadIdx.x + o]; }
-    __syncthreads();
-  }
+  wg_tree_sum<256>(l, sl, c, sc);
   if (threadIdx.x == 0) {
-    out[0] = (float)(sl[0] / sc[0]);
-    out[1] = (float)sc[0];
+    out[0] = (float)(l / c);
+    out[1] = (float)c;
   }
 }
 
@@ -717,7 +706,6 @@ __global__ __launch_bounds__(512) void ce_up_bwd_tiled_kernel(const float* __res
     // (gs is next written after the next tile's first barrier)
   }
 }
-inline size_t a16(size_t b) { return (b + 15) & ~(size_t)15; }
 inline int gn_slabs(long HW) { return (int)((HW + GN_SLAB_ROWS - 1) / GN_SLAB_ROWS); }
 
 int gn_check(int N, long HW, int C, int G) {

@@ -1,14 +1,15 @@
 // One arena for the caller-owned workspaces: an entry point's `carve(Arena&, dims...)` names every buffer once, with its
 // element type and count, and is run twice — over a null base by `*_workspace_bytes` (measure: `off` is the answer) and
 // over the caller's buffer by the call itself.  Buffers start on multiples of `granule` bytes: 256 everywhere but in
-// the two oldest layouts (the MIL and PCL workspaces), whose published byte counts are sums of 16-byte pieces.
-// Host code only.
+// the layouts whose published byte counts are sums of 16-byte pieces (the MIL and PCL workspaces, the DeepLab loss, the
+// Panoptic-DeepLab centres and merge).  Host code only.
 #pragma once
 #include <cstddef>
 
 namespace jtsm {
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline size_t a16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 struct Arena {
   char* base;               // nullptr: measure only

@@ -60,18 +60,7 @@ __device__ __forceinline__ RowStats row_softmax(const float* __restrict__ row, i
   return s;
 }
 
-// Sum over a workgroup of 256 through an LDS halving tree (NOT the butterfly order of wave_sum: these sums keep the
-// order they have always had); the result is valid in thread 0.
-template <class T>
-__device__ __forceinline__ T tree_sum_256(T v, T* __restrict__ red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  return red[0];
-}
+// (sums over a workgroup of 256 that keep the LDS halving tree's order, not the butterfly's — wg_tree_sum: reduce.h)
 
 struct SlabRange { int bag, r0, r1; };
 
@@ -252,7 +241,7 @@ __global__ __launch_bounds__(256) void mil_finish(const float* __restrict__ psum
     const bool pass = sum >= kTiny && sum <= 1.f - kTiny;
     gp[idx] = pass ? (p - y) / (p * (1.f - p)) * norm : 0.f;
   }
-  part = tree_sum_256(part, red);
+  part = wg_tree_sum<256>(part, red);
   if (threadIdx.x == 0) *loss = part * norm;
 }
 
@@ -454,7 +443,7 @@ __global__ __launch_bounds__(256) void mask_bce_fwd(const float* __restrict__ z,
     const float t = target[i] ? 1.f : 0.f;
     s += fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
   }
-  s = tree_sum_256(s, red);
+  s = wg_tree_sum<256>(s, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -463,7 +452,7 @@ __global__ __launch_bounds__(256) void mask_bce_finish(const float* __restrict__
   __shared__ double red[256];
   double s = 0.0;
   for (int b = threadIdx.x; b < nblocks; b += 256) s += part[b];
-  s = tree_sum_256(s, red);
+  s = wg_tree_sum<256>(s, red);
   if (threadIdx.x == 0) out[0] = (float)(s / (double)npix);
 }
 

@@ -81,6 +81,29 @@ def test_ties_at_the_cut_take_the_lower_flat_index_first(cuda):
     assert R.max_rel(grad[:, :c], dz) <= REL
 
 
+def test_ties_at_the_cut_above_256_workgroups(cuda):
+    """304 x 432 = 131328 pixels are 513 tiles of 256: chunks of 512 pixels and 257 workgroups, so the finishing kernel's
+    first thread folds two chunks and the tie scan crosses them.  Zero logits and weights of 2 and 1 give two loss
+    values, 2 log 3 and log 3, and the cut lies inside the second."""
+    shape = (1, 3, 19, 27, 16)
+    c, scale = shape[1], shape[4]
+    wide, target, _ = _inputs(shape, 7, zero_logits=True)
+    g = torch.Generator().manual_seed(8)
+    heavy = torch.rand(target.shape, generator=g) < 0.1
+    weights = torch.where(heavy, 2.0, 1.0)
+    k = int(0.2 * target.numel())
+    valid = (target != IGNORE).view(-1)
+    two, one = valid & heavy.view(-1), valid & ~heavy.view(-1)
+    m = int(two.sum())
+    assert target.numel() == 131328 and m < k < m + int(one.sum()), (m, k, int(one.sum()))
+    chosen = two | (one & (torch.cumsum(one.long(), 0) <= k - m))  # every 2 log 3, then the first k - m log 3 in flat order
+    want, dz, _, _ = R.deeplab_ce(wide[:, :c], target, scale, IGNORE, 0.2, weights, selected=chosen)
+    loss, grad, maps = _device_run(wide, c, target, weights, scale, 0.2, cuda)
+    assert torch.equal((maps[2] != 0).view(-1).cpu(), chosen)
+    assert R.max_rel(loss, want) <= REL
+    assert R.max_rel(grad[:, :c], dz) <= REL
+
+
 def test_cut_inside_the_zeros(cuda):
     shape = (2, 19, 8, 12, 4)
     c, scale = shape[1], shape[4]

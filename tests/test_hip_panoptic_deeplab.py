@@ -32,9 +32,19 @@ def _check_centres(heat, kernel, top_k, cuda, threshold=0.1):
     return want
 
 
-@pytest.mark.parametrize("shape", [(64, 96), (37, 53)])
-@pytest.mark.parametrize("kernel", [3, 7])
-@pytest.mark.parametrize("top_k", [5, 20, 200])
+# 304 x 432 = 131328 pixels are 513 tiles of 256: the chunked passes run 257 workgroups of two tiles each, the regime of
+# every map above 131072 pixels (the smaller shapes run one tile per workgroup)
+ABOVE_256_WORKGROUPS = (304, 432)
+
+
+def _random_map_cases():
+    """Every small shape with every kernel and top_k (under the ids they have always had), and the large one once."""
+    small = [pytest.param(shape, kernel, top_k, id="%d-%d-shape%d" % (top_k, kernel, i))
+             for top_k in (5, 20, 200) for kernel in (3, 7) for i, shape in enumerate([(64, 96), (37, 53)])]
+    return small + [pytest.param(ABOVE_256_WORKGROUPS, 3, 200, id="200-3-above_256_workgroups")]
+
+
+@pytest.mark.parametrize("shape,kernel,top_k", _random_map_cases())
 def test_centres_random_map(cuda, shape, kernel, top_k):
     g = torch.Generator().manual_seed(shape[0] * 100 + kernel * 10 + top_k)
     heat = torch.rand(1, *shape, generator=g)
@@ -56,8 +66,9 @@ def test_centres_few_candidates(cuda, shape, kernel):
     assert want.shape[0] == 4
 
 
-@pytest.mark.parametrize("shape", [(64, 96), (37, 53)])
-@pytest.mark.parametrize("kernel", [3, 7])
+@pytest.mark.parametrize("shape,kernel", [pytest.param(shape, kernel, id="%d-shape%d" % (kernel, i))
+                                          for kernel in (3, 7) for i, shape in enumerate([(64, 96), (37, 53)])]
+                         + [pytest.param(ABOVE_256_WORKGROUPS, 3, id="3-above_256_workgroups")])
 def test_centres_ties_at_the_cut(cuda, shape, kernel):
     """Eighths: the largest value is held by more than top_k pixels, all of them their window's maximum, so the
     top_k-th value is the largest one and nothing lies strictly above it."""
@@ -336,14 +347,16 @@ def _device_loss(fn, wide, c, target, weights, scale, cuda):
 
 
 @pytest.mark.parametrize("kind", ["center", "offset"])
-@pytest.mark.parametrize("hw", [(8, 12), (1, 5), (5, 7)])
+@pytest.mark.parametrize("hw", [(8, 12), (1, 5), (5, 7), (19, 27, 16)])      # (h, w) at stride 4, or (h, w, stride)
 def test_losses(cuda, kind, hw):
+    """(19, 27) at stride 16: 2 x 304 x 432 pixels are 342 chunks, so the finishing kernel folds two chunks per thread."""
     fn, ref, _ = LOSSES[kind]
-    wide, c, target, weights = _loss_inputs(kind, hw[0], hw[1], seed=hw[0] * 10 + hw[1])
+    scale = hw[2] if len(hw) > 2 else 4
+    wide, c, target, weights = _loss_inputs(kind, hw[0], hw[1], seed=hw[0] * 10 + hw[1], scale=scale)
     pred = wide[:, :c]
-    loss64, grad64 = R.loss_and_grad(ref, pred, target, weights, 4, torch.float64)
-    loss32, grad32 = R.loss_and_grad(ref, pred, target, weights, 4, torch.float32)
-    loss, grad = _device_loss(fn, wide, c, target, weights, 4, cuda)
+    loss64, grad64 = R.loss_and_grad(ref, pred, target, weights, scale, torch.float64)
+    loss32, grad32 = R.loss_and_grad(ref, pred, target, weights, scale, torch.float32)
+    loss, grad = _device_loss(fn, wide, c, target, weights, scale, cuda)
     assert bool((grad[:, c:] == 0).all())                       # the padding channels get no gradient
     bar_l = 4 * float((loss32.double() - loss64).abs())
     bar_g = 4 * float((grad32.double() - grad64).abs().max())
@@ -353,7 +366,7 @@ def test_losses(cuda, kind, hw):
           % (kind, hw, float(loss64), err_l, bar_l, err_g, bar_g))
     assert bar_g > 0 and err_g <= bar_g
     assert err_l <= bar_l
-    again, grad_again = _device_loss(fn, wide, c, target, weights, 4, cuda)
+    again, grad_again = _device_loss(fn, wide, c, target, weights, scale, cuda)
     assert torch.equal(again, loss) and torch.equal(grad_again, grad)
 
 
