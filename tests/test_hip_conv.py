@@ -304,13 +304,15 @@ def test_fused_upsample_cross_entropy_vs_torch_cpu(cuda):
     from jtsm_amd.layers.elementwise import semseg_cross_entropy
 
     g = torch.Generator().manual_seed(11)
-    # (x4 runs the LDS-tiled backward: whole tiles, ragged tiles on both edges, maps smaller than one tile)
+    # (x4 runs the LDS-tiled backward: whole tiles, ragged tiles on both edges, maps smaller than one tile; every other
+    # scale the general gather — x3, x5, x6, x7: 1 / scale is not exact in fp32, and odd scales use the window's spares)
     for (n, c, hs, ws, scale) in [(2, 54, 16, 24, 4), (1, 7, 5, 3, 2), (1, 54, 8, 8, 4), (2, 54, 5, 7, 4),
-                                  (1, 54, 3, 1, 4), (1, 13, 9, 2, 4), (1, 54, 1, 1, 4)]:
+                                  (1, 54, 3, 1, 4), (1, 13, 9, 2, 4), (1, 54, 1, 1, 4),
+                                  (1, 7, 5, 3, 3), (2, 54, 4, 6, 5), (1, 13, 3, 2, 6), (1, 54, 2, 1, 3), (1, 54, 1, 1, 7)]:
         z = torch.randn(n, c, hs, ws, generator=g) * 3
         t = torch.randint(0, c, (n, hs * scale, ws * scale), generator=g)
         t[:, :2] = 255
-        t[0, 5:, 3] = 255
+        t[0, 5:, 3:4] = 255                                         # (column 3, where the map has one)
         zr = z.clone().requires_grad_()
         l0 = F.cross_entropy(F.interpolate(zr, scale_factor=scale, mode="bilinear", align_corners=False), t,
                              reduction="mean", ignore_index=255)

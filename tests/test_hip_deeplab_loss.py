@@ -40,7 +40,9 @@ def _device_run(wide, c, target, weights, scale, frac, cuda):
     return loss.detach(), w.grad, maps
 
 
-PARITY = [(2, 19, 8, 12, 4), (2, 19, 2, 3, 16), (1, 7, 5, 3, 2), (1, 19, 1, 1, 4)]        # (N, C, Hs, Ws, scale)
+PARITY = [(2, 19, 8, 12, 4), (2, 19, 2, 3, 16), (1, 7, 5, 3, 2), (1, 19, 1, 1, 4),        # (N, C, Hs, Ws, scale)
+          # scales whose reciprocal is not exact in fp32, odd ones among them (the gather window's spare rows and columns)
+          (1, 7, 5, 3, 3), (2, 19, 4, 6, 5), (1, 19, 3, 5, 6), (1, 5, 2, 3, 7), (1, 19, 1, 1, 3), (1, 7, 1, 4, 5)]
 
 
 @pytest.mark.parametrize("weighted", [False, True])

@@ -1,6 +1,7 @@
 """The two mining entry points that were only ever run through the whole model — jtsm_near_targets_f32 and the rectangle
 painter jtsm_paint_sem_seg (csrc/mining.hip) — against torch-CPU restatements of their rules, bit for bit.  Both decide
-integers, and the inputs are built so that the tie-break rules decide some of them."""
+integers, and the inputs are built so that the tie-break rules decide some of them.  With them the rectangle mask
+targets, jtsm_rect_mask_targets_f32 (csrc/roi_align.hip), against rasterise-then-ROIAlign of the oracle, bit for bit."""
 import pytest
 import torch
 
@@ -147,3 +148,65 @@ def test_paint_sem_seg_rectangles_and_missing_rule(cuda):
 
     got = paint_sem_seg(boxes.to(cuda), classes.to(cuda), scores.to(cuda), counts.to(cuda), base, H, W, erode)
     assert got.dtype == torch.int64 and torch.equal(got.cpu(), want), (got.cpu() != want).nonzero()[:5]
+
+
+# ---- rect_mask_targets (csrc/roi_align.hip: rect_mask_targets_kernel) ------------------------------------------------------
+RECT_H, RECT_W = 300, 340
+
+
+def _rect_inputs(seed=31):
+    """24 rois in a 300 x 340 image with the pseudo-GT rectangle matched to each: mostly the roi moved by a few pixels,
+    so that the shrunk rectangle's edge crosses the roi's bins."""
+    g = torch.Generator().manual_seed(seed)
+    n = 24
+    wh = torch.rand(n, 2, generator=g) * 197 + 3                    # sides of 3 to 200 pixels
+    xy = torch.rand(n, 2, generator=g) * (torch.tensor([RECT_W, RECT_H]) - wh)
+    rois = torch.cat([xy, xy + wh], 1)
+    rois[0] = torch.tensor([-40.0, -30.0, 90.5, 120.25])            # partly outside
+    rois[1] = torch.tensor([5.0, 6.0, 7.5, 9.0])                    # tiny
+    rois[2] = torch.tensor([4.0, 3.0, 336.5, 297.25])               # nearly the whole image
+    rects = rois + (torch.rand(n, 4, generator=g) * 12 - 6)
+    rects[1] = torch.tensor([1.0, 2.0, 8.5, 9.5])                   # (shrunk by 2, its corner lies inside the tiny roi)
+    rects[3] = rois[3]
+    rects[3, 2] = rois[3, 0] + 3.0                                  # narrower than 2 * erode
+    rects[4] = torch.tensor([300.0, 250.0, 335.0, 295.0])           # disjoint from its roi ...
+    rois[4] = torch.tensor([20.0, 30.0, 120.0, 90.0])               # ... which is this
+    rects[5] = torch.tensor([0.0, 0.0, float(RECT_W), float(RECT_H)])   # the whole image
+    return rois, rects
+
+
+def _rect_reference(rois, rects, side, erode):
+    """The rectangle rasterised (oracle/model.py: eroded_rect_masks) and cropped by the C restatement of ROIAlign, as
+    BitMasks.crop_and_resize does it: scale 1, adaptive sampling, aligned, >= 0.5."""
+    from oracle import model as OM
+    from oracle import pooling as P
+
+    masks = OM.eroded_rect_masks(rects, RECT_H, RECT_W, erode)
+    rr = torch.cat([torch.arange(rois.shape[0], dtype=torch.float32)[:, None], rois], 1)
+    return torch.from_numpy(P.roi_align_forward(masks[:, None].numpy(), rr.numpy(), 1.0, side, side, 0, True))[:, 0] >= 0.5
+
+
+@pytest.mark.parametrize("side,erode", [(28, 2.0), (28, 0.0), (7, 2.0)], ids=["28-erode2", "28-erode0", "7-erode2"])
+def test_rect_mask_targets_bit_exact_vs_rasterise_then_roi_align(cuda, side, erode):
+    """The kernel evaluates the shrunk rectangle analytically at every ROIAlign tap (nothing is rasterised); the oracle
+    rasterises it and crops.  Bits must agree exactly, as for its siblings paste_crop_targets and sp_mask_targets
+    (test_hip_losses.py)."""
+    from jtsm_amd.layers.mining import rect_mask_targets
+
+    rois, rects = _rect_inputs()
+    want = _rect_reference(rois, rects, side, erode)
+    if erode > 0:
+        assert not want[3].any()                                    # narrower than 2 * erode: an empty mask
+    assert not want[4].any() and want[5].all()                      # disjoint; the whole image (eroded: less than a bin)
+    if (side, erode) == (28, 2.0):
+        assert 0.1 < float(want.float().mean()) < 0.9
+    got = rect_mask_targets(rois.to(cuda), rects.to(cuda), side, RECT_H, RECT_W, erode).cpu()
+    assert got.shape == want.shape and got.dtype == torch.bool
+    assert torch.equal(got, want), (got != want).nonzero()[:5]
+
+
+def test_rect_mask_targets_of_no_roi(cuda):
+    from jtsm_amd.layers.mining import rect_mask_targets
+
+    got = rect_mask_targets(torch.zeros(0, 4, device=cuda), torch.zeros(0, 4, device=cuda), 28, RECT_H, RECT_W)
+    assert got.shape == (0, 28, 28) and got.dtype == torch.bool

@@ -347,9 +347,11 @@ def _device_loss(fn, wide, c, target, weights, scale, cuda):
 
 
 @pytest.mark.parametrize("kind", ["center", "offset"])
-@pytest.mark.parametrize("hw", [(8, 12), (1, 5), (5, 7), (19, 27, 16)])      # (h, w) at stride 4, or (h, w, stride)
+@pytest.mark.parametrize("hw", [(8, 12), (1, 5), (5, 7), (19, 27, 16),       # (h, w) at stride 4, or (h, w, stride)
+                                (5, 7, 3), (4, 3, 5), (3, 5, 6), (1, 2, 7)])
 def test_losses(cuda, kind, hw):
-    """(19, 27) at stride 16: 2 x 304 x 432 pixels are 342 chunks, so the finishing kernel folds two chunks per thread."""
+    """(19, 27) at stride 16: 2 x 304 x 432 pixels are 342 chunks, so the finishing kernel folds two chunks per thread.
+    Strides 3, 5, 6 and 7: 1 / stride is not exact in fp32, and the odd ones run the gather window's spare rows and columns."""
     fn, ref, _ = LOSSES[kind]
     scale = hw[2] if len(hw) > 2 else 4
     wide, c, target, weights = _loss_inputs(kind, hw[0], hw[1], seed=hw[0] * 10 + hw[1], scale=scale)
