@@ -28,53 +28,83 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 #endif
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
-// ---- forward statistics: part[n][slab][chunk] = (sum, sumsq) over the slab's pixels of the chunk's 4
-// channels.  Requires 256 % (C/4) == 0 so that a thread always visits the same chunk.
+// (count, mean, M2 = sum (x - mean)^2) of a and b together, into a (the pairwise update of Chan et al.)
+__device__ __forceinline__ void gn_merge(double& na, double& ma, double& qa, double nb, double mb, double qb) {
+  if (nb == 0.0) return;
+  if (na == 0.0) { na = nb; ma = mb; qa = qb; return; }
+  const double n = na + nb, d = mb - ma;
+  ma += d * (nb / n);
+  qa += qb + d * d * (na * nb / n);
+  na = n;
+}
+
+// ---- forward statistics: part[n][slab][chunk] = (mean, M2) over the slab's pixels of the chunk's 4 channels (their
+// count, 4 * the slab's pixels, follows from the geometry).  Requires 256 % (C/4) == 0 so that a thread always visits
+// the same chunk.  Every thread of a chunk sums (x - K) and (x - K)^2 with K = THE CHUNK'S VALUES AT THE SLAB'S FIRST
+// PIXEL, so the sums are of the size of the spread, not of the mean: a map whose mean is large against its spread keeps
+// its variance (one-pass fp32 E[x^2] - E[x]^2 loses it, as csrc/batch_norm.hip's header says of batch norm).  One K per
+// chunk and slab, so the threads' sums still add as plain fp32 in the fixed order they always had.
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, float2* __restrict__ part,
                                                        int HW, int C, int slabs) {
-  __shared__ float2 red[256];
+  __shared__ float4 rs[256], rq[256];
   const int C4 = C / 4, n = blockIdx.y, slab = blockIdx.x;
   const int p0 = slab * GN_SLAB_ROWS, p1 = min(HW, p0 + GN_SLAB_ROWS);
   const float* base = x + (size_t)n * HW * C;
-  float s = 0.f, q = 0.f;
+  const float4 K = ld4(base + ((long)p0 * C4 + threadIdx.x % C4) * 4);
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
   for (long it = (long)p0 * C4 + threadIdx.x; it < (long)p1 * C4; it += 256) {
     const float4 v = ld4(base + it * 4);
-    s += (v.x + v.y) + (v.z + v.w);
-    q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+    const float dx = v.x - K.x, dy = v.y - K.y, dz = v.z - K.z, dw = v.w - K.w;
+    s.x += dx; s.y += dy; s.z += dz; s.w += dw;
+    q.x += dx * dx; q.y += dy * dy; q.z += dz * dz; q.w += dw * dw;
   }
-  red[threadIdx.x] = make_float2(s, q);
+  rs[threadIdx.x] = s; rq[threadIdx.x] = q;
   __syncthreads();
   if (threadIdx.x < C4) {
-    float2 a = make_float2(0.f, 0.f);
-    for (int t = threadIdx.x; t < 256; t += C4) { a.x += red[t].x; a.y += red[t].y; }
-    part[((size_t)n * slabs + slab) * C4 + threadIdx.x] = a;
+    float sa[4] = {0.f, 0.f, 0.f, 0.f}, qa[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int t = threadIdx.x; t < 256; t += C4) {
+      sa[0] += rs[t].x; sa[1] += rs[t].y; sa[2] += rs[t].z; sa[3] += rs[t].w;
+      qa[0] += rq[t].x; qa[1] += rq[t].y; qa[2] += rq[t].z; qa[3] += rq[t].w;
+    }
+    const float Ke[4] = {K.x, K.y, K.z, K.w};
+    // the four channels have the same count: their mean is the mean of their means, and M2 gains count * (distance)^2 each
+    const double cnt = (double)(p1 - p0), inv = 1.0 / cnt;
+    double me[4], ma = 0.0, m2 = 0.0;
+    for (int e = 0; e < 4; ++e) {
+      const double sd = (double)sa[e], qe = (double)qa[e] - sd * sd * inv;
+      me[e] = (double)Ke[e] + sd * inv;
+      ma += me[e];
+      m2 += qe > 0.0 ? qe : 0.0;
+    }
+    ma *= 0.25;
+    for (int e = 0; e < 4; ++e) m2 += cnt * (me[e] - ma) * (me[e] - ma);
+    part[((size_t)n * slabs + slab) * C4 + threadIdx.x] = make_float2((float)ma, (float)m2);
   }
 }
 
-// mean / rstd per (n, group) from the partials, folded in slab order in double.
+// mean / rstd per (n, group) from the partials' (mean, M2), merged pairwise in double in slab order.
 __global__ void gn_fold_kernel(const float2* __restrict__ part, float* __restrict__ mean,
                                float* __restrict__ rstd, int HW, int C, int G, int slabs, float eps) {
-  // blockDim = 64 * S: slice j of group g folds slabs j, j+S, ... in double; the slices are added in slice order
-  __shared__ double rs[16][64], rq[16][64];
+  // blockDim = 64 * S: slice j of group g merges slabs j, j+S, ...; the slices are merged in slice order
+  __shared__ double rn[16][64], rm[16][64], rq[16][64];
   const int n = blockIdx.x, g = threadIdx.x & 63, j = threadIdx.x >> 6, S = blockDim.x >> 6;
   const int C4 = C / 4, cpg4 = C4 / G;
-  double s = 0.0, q = 0.0;
+  double cn = 0.0, m = 0.0, q = 0.0;
   if (g < G)
-    for (int sl = j; sl < slabs; sl += S)
+    for (int sl = j; sl < slabs; sl += S) {
+      const int p0 = sl * GN_SLAB_ROWS, p1 = min(HW, p0 + GN_SLAB_ROWS);
       for (int k = 0; k < cpg4; ++k) {
         const float2 v = part[((size_t)n * slabs + sl) * C4 + g * cpg4 + k];
-        s += v.x; q += v.y;
+        gn_merge(cn, m, q, 4.0 * (double)(p1 - p0), (double)v.x, (double)v.y);
       }
-  rs[j][g] = s; rq[j][g] = q;
+    }
+  rn[j][g] = cn; rm[j][g] = m; rq[j][g] = q;
   __syncthreads();
   if (j != 0 || g >= G) return;
-  s = 0.0; q = 0.0;
-  for (int jj = 0; jj < S; ++jj) { s += rs[jj][g]; q += rq[jj][g]; }
-  const double m = (double)HW * (C / G);
-  const double mu = s / m;
-  double var = q / m - mu * mu;
+  for (int jj = 1; jj < S; ++jj) gn_merge(cn, m, q, rn[jj][g], rm[jj][g], rq[jj][g]);
+  double var = q / cn;
   if (var < 0.0) var = 0.0;
-  mean[n * G + g] = (float)mu;
+  mean[n * G + g] = (float)m;
   rstd[n * G + g] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
@@ -712,6 +742,7 @@ int gn_check(int N, long HW, int C, int G) {
   JTSM_REQUIRE(N >= 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && (C / G) % 4 == 0,
                "group_norm: channels per group must be a multiple of 4 (C=%d G=%d)", C, G);
   JTSM_REQUIRE(256 % (C / 4) == 0 && C <= 1024, "group_norm: C/4 must divide 256 (C=%d)", C);
+  JTSM_REQUIRE(G <= 64, "group_norm: at most 64 groups (G=%d)", G);
   return JTSM_OK;
 }
 
@@ -739,7 +770,6 @@ int jtsm_group_norm_forward_f32(const float* x, const float* gamma, const float*
   const int slabs = gn_slabs(HW);
   float2* part = reinterpret_cast<float2*>(workspace);
   hipLaunchKernelGGL(gn_stats_kernel, dim3(slabs, N), dim3(256), 0, st, x, part, (int)HW, C, slabs);
-  JTSM_REQUIRE(G <= 64, "group_norm: at most 64 groups (G=%d)", G);
   hipLaunchKernelGGL(gn_fold_kernel, dim3(N), dim3(64 * 16), 0, st, part, mean, rstd, (int)HW, C, G, slabs, eps);
   const long total4 = (long)N * HW * (C / 4);
   hipLaunchKernelGGL(gn_apply_kernel, dim3(grid_for(total4)), dim3(256), 0, st, x, mean, rstd, gamma, beta, y, HW,
